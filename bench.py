@@ -34,6 +34,9 @@ then — as the LAST line, the one the driver parses — a compact object of < 4
   parity_check  the rows the CPU baseline rendered, compared with an fp64 GPU frame of the same
                 configuration (1e-9 per channel); a mismatch makes the bench fail.
   workloads     (N=1) the other single-GPU workloads, each with its own roofline / parity entry.
+
+`--dump-outputs DIR` writes what the headline workload's last timed step computed to DIR/<name>.npy (see dump_outputs):
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -89,6 +92,10 @@ RAY_WORKLOADS = {
 EXTRA_AT_N1 = ["veach-mis", "bathroom2", "bathroom2-spp500", "cornell-ct", "s0-rays-cornell", "s0-rays-cornell-coherent", "s4-rays-soup8m",
                "cornell-box-f32", "veach-mis-f32", "bathroom2-f32"]
 TOL = 1e-9  # per channel, relative to max(1, |x|): fp64 on both sides, differences = FMA contraction + libm ulps
+# --dump-outputs: at most 64 MB in all; a ray workload's 2^24 hits are sampled at DUMP_RAYS fixed, seeded rays (6 x 8 MB)
+DUMP_LIMIT = 64 << 20
+DUMP_RAYS = 1 << 20
+DUMP_SEED = 20240601
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -344,8 +351,20 @@ class Ctx:
     pass
 
 
-def time_render(ctx, name, steps, warmup, spp_override=0, with_cpu=True, cpu_target_s=8.0):
-    """Times `steps` frames of a render workload on the current rank set; returns the JSON object of the workload."""
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only, DUMP_LIMIT bytes in all)."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
+def time_render(ctx, name, steps, warmup, spp_override=0, with_cpu=True, cpu_target_s=8.0, dump_dir=None):
+    """Times `steps` frames of a render workload on the current rank set; returns the JSON object of the workload.
+    With `dump_dir`: rank 0 writes the framebuffer of the last timed frame (after the reduce) as framebuffer.npy."""
     torch, dist, api, scenes, distributed = ctx.torch, ctx.dist, ctx.api, ctx.scenes, ctx.distributed
     rank, nranks, rehearsal = ctx.rank, ctx.nranks, ctx.rehearsal
     fn, kw, spp, depth = WORKLOADS[name][:4]
@@ -403,6 +422,8 @@ def time_render(ctx, name, steps, warmup, spp_override=0, with_cpu=True, cpu_tar
     rays = (c["rays_closest"] + c["rays_shadow"]) * steps
     samples = c["samples"] * steps
     fb = fbs[(steps - 1) % 2]
+    if dump_dir and rank == 0:  # before the checks below render into fb again
+        dump_outputs(dump_dir, {"framebuffer": fb.cpu().numpy()})
 
     if nranks > 1:
         t = torch.tensor([elapsed, float(rays), float(samples)], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
@@ -484,8 +505,10 @@ def time_render(ctx, name, steps, warmup, spp_override=0, with_cpu=True, cpu_tar
     return out
 
 
-def time_rays(ctx, name, steps, warmup):
-    """One step = one K1 launch over 2^24 rays (rays and hits stay in HBM)."""
+def time_rays(ctx, name, steps, warmup, dump_dir=None):
+    """One step = one K1 launch over 2^24 rays (rays and hits stay in HBM).
+    With `dump_dir`: the hits of the last timed launch at a fixed, seeded sample of DUMP_RAYS rays, one .npy per field
+    (hit_t is +inf and hit_prim -1 on a miss, as prt.h defines them)."""
     import numpy as np
     torch, api, scenes = ctx.torch, ctx.api, ctx.scenes
     fn, kw, device_bvh = RAY_WORKLOADS[name]
@@ -511,6 +534,11 @@ def time_rays(ctx, name, steps, warmup):
         ms.append(sc.counters()["kernel_ms"])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir:  # before the counting launch below writes d_h again
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_RAYS, replace=False))
+        sel = d_h.index_select(0, torch.from_numpy(idx).cuda()).cpu().numpy()
+        sel = sel.view(np.dtype([("t", "<f8"), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"), ("front", "<i4")])).reshape(-1)
+        dump_outputs(dump_dir, {"ray_index": idx.astype(np.float64), **{"hit_" + f: sel[f].astype(np.float64) for f in sel.dtype.names}})
     sc.trace_closest_device(d_r.data_ptr(), n, d_h.data_ptr(), count_work=True)
     torch.cuda.synchronize()
     cc = sc.counters()
@@ -721,9 +749,14 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="headline workload only (no `workloads` / `config5` entries)")
     ap.add_argument("--no-pipeline", action="store_true", help="one stream, one framebuffer: frames strictly back to back")
     ap.add_argument("--pipeline", action="store_true", help="alternate two streams / framebuffers also at N=1 (default: only for N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed as DIR/<name>.npy "
+                         "(render: framebuffer.npy, the fp32 frame; ray workloads: the hits of a fixed, seeded sample of rays)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.precision == "f32" and not args.workload.endswith("-f32"):
         if args.workload + "-f32" not in WORKLOADS:
@@ -778,7 +811,7 @@ def main():
     if args.workload in RAY_WORKLOADS:
         if nranks != 1:
             raise SystemExit("ray microbenchmarks are single-GPU")
-        w = time_rays(ctx, args.workload, args.steps, args.warmup)
+        w = time_rays(ctx, args.workload, args.steps, args.warmup, dump_dir=args.dump_outputs)
         out = {"metric": "Mrays/s (closest-hit, %s rays)" % ("coherent camera" if args.workload.endswith("-coherent") else "incoherent"), "value": w["value"], "unit": "Mrays/s", "n_gpus": 1,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": w["ms_per_step"], "higher_is_better": True,
                "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -791,7 +824,7 @@ def main():
         out["checks_ok"] = bool(ok)
         emit(out)
     else:
-        w = time_render(ctx, args.workload, args.steps, args.warmup, spp_override=args.spp)
+        w = time_render(ctx, args.workload, args.steps, args.warmup, spp_override=args.spp, dump_dir=args.dump_outputs)
         extras, config5 = [], None
         if not args.no_extra and args.workload in ("cornell-box", "cornell-box-f32") and args.spp == 0:
             if nranks > 1:

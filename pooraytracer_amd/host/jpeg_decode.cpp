@@ -1,7 +1,7 @@
 // jpeg_decode.cpp — JPEG reader for ImageTexture ingestion.
 //
 // The reference decodes textures with stb_image's stbi_load(path, &w, &h, &channels, 0)
-// (Source/Texture.cpp:10-21); stb_image is a git submodule that is absent from /root/reference
+// (Source/Texture.cpp:10-21); stb_image is a git submodule that is absent from the reference's tree
 // (nothings/stb, version unpinned), so this file restates its *published* JPEG pipeline — the choices
 // that decide the texel values — rather than any source:
 //   * baseline (SOF0/SOF1, 8-bit) and progressive (SOF2) Huffman JPEG, restart intervals, 1 or 3

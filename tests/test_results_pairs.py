@@ -1,7 +1,8 @@
 """The output stage against the ONLY golden data the reference holds: the `.hdr` + `.png` pairs in its Results/ directory,
 both written by `Camera::WriteColorAttachment` (reference Source/Camera.cpp:279-331; `LinearToSRGB` :206-221) from the
-same `colorAttachment`.  tests/golden/results_pairs.npz holds crops and scanlines cut from them by
-tests/golden/make_results_pairs.py (data: pixel bytes, encoded bytes, checksums).
+same `colorAttachment`.  tests/golden/results_pairs.npz holds crops and scanlines cut from them, and
+tests/golden/results_cuts.npz smaller whole files cut from them, both by tests/golden/make_results_pairs.py (data: pixel
+bytes, encoded bytes, checksums).
 
 What they pin (SURVEY.md Â§8 rows f2 / f3; the hot path itself stays unpinned â€” the scenes that produced them are absent):
   * the .hdr stores every linear float v as a byte m = trunc(v * 2^(136-e)) under the pixel's shared exponent e, so
@@ -10,9 +11,9 @@ What they pin (SURVEY.md Â§8 rows f2 / f3; the hot path itself stays unpinned â€
     fed the two ends of that interval it must BRACKET the reference's byte, and fed the lower end it must reproduce most
     bytes exactly (wherever the quantum does not straddle an 8-bit step);
   * the product's .hdr writer, fed the decoded floats, must write the reference's bytes back: same header, same
-    per-component run-length coding (stb_image_write's) â€” scanline by scanline here, whole files where the reference is present;
-  * the product's PNG reader must decode the reference's stb-written PNGs exactly as Pillow does (run where the reference
-    is present; the checksums of Pillow's decodes travel in the fixture).
+    per-component run-length coding (stb_image_write's) â€” scanline by scanline, and whole files of a band of scanlines;
+  * the product's PNG reader must decode the reference's stb-written PNGs, cut to their first rows with stb's own deflate
+    bits, exactly as Pillow does (the checksums of Pillow's decodes travel in the fixture).
 """
 import hashlib
 import os
@@ -25,13 +26,18 @@ import pytest
 from pooraytracer_amd import build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RESULTS = "/root/reference/Results"
 FIX = os.path.join(ROOT, "tests", "golden", "results_pairs.npz")
+CUTS = os.path.join(ROOT, "tests", "golden", "results_cuts.npz")
 
 
 @pytest.fixture(scope="module")
 def fx():
     return np.load(FIX)
+
+
+@pytest.fixture(scope="module")
+def cuts():
+    return np.load(CUTS)
 
 
 @pytest.fixture(scope="module")
@@ -139,34 +145,46 @@ def test_host_hdr_writer_reproduces_the_reference_scanlines_byte_for_byte(fx, to
         assert hdr[len(want_header):] == blob[offs[k]:offs[k + 1]], k
 
 
-@pytest.mark.skipif(not os.path.isdir(RESULTS), reason="the reference's Results/ exists in the build container only")
-def test_whole_reference_hdr_files_round_trip_through_the_product_writer(fx, tools):
-    """Where the reference is present: decode each .hdr, hand the floats to Camera::WriteColorAttachment, and the file it
-    writes has the reference file's sha256; its PNG brackets / mostly equals the reference's PNG over the WHOLE frame."""
-    from PIL import Image
-    for name, sha in zip(fx["pairs"], fx["file_sha256"]):
-        data = open(os.path.join(RESULTS, str(name) + ".hdr"), "rb").read()
-        assert hashlib.sha256(data).hexdigest() == str(sha)
+def test_reference_hdr_bands_round_trip_through_the_product_writer(fx, cuts, tools):
+    """Whole .hdr files: of each pair the brightest band of full scanlines as the reference encoded them, with the header
+    of a file of the band's height.  Decoded and handed to Camera::WriteColorAttachment, its floats make the writer write
+    that file back byte for byte; the PNG stage brackets / mostly equals the reference PNG's pixels of the band."""
+    header = bytes(fx["hdr_header"])
+    offs, blob = cuts["band_hdr_offsets"], cuts["band_hdr_bytes"].tobytes()
+    for k, (pair, y0) in enumerate(cuts["band_rows"]):
+        ref = cuts["band_png"][k]
+        band_header = header.replace(b"-Y 720 +X 1280", b"-Y %d +X 1280" % ref.shape[0])
+        assert band_header != header
+        data = band_header + blob[offs[k]:offs[k + 1]]
         _, px, _ = decode_hdr(data)
+        assert px.shape[:2] == ref.shape[:2]
         lo, hi = rgbe_interval(px)
-        p_lo, hdr = run_stage(tools, lo, "full_lo")
-        assert hashlib.sha256(hdr).hexdigest() == str(sha), name
-        p_hi, _ = run_stage(tools, hi, "full_hi")
-        ref = np.asarray(Image.open(os.path.join(RESULTS, str(name) + ".png")).convert("RGB"))
+        p_lo, hdr = run_stage(tools, lo, f"band{k}_lo")
+        assert hashlib.sha256(hdr).hexdigest() == hashlib.sha256(data).hexdigest(), (str(fx["pairs"][pair]), int(y0))
+        p_hi, _ = run_stage(tools, hi, f"band{k}_hi")
         check_bracket(p_lo, p_hi, ref, 0.70, max_width=40)
 
 
-@pytest.mark.skipif(not os.path.isdir(RESULTS), reason="the reference's Results/ exists in the build container only")
-def test_png_reader_decodes_the_reference_pngs_like_pillow(fx, tools):
-    """host/png_decode.cpp on the twelve stb-written PNGs of Results/ (8-bit RGB, stb's own deflate and filter choice):
-    same size and the checksum of Pillow's decode (stored in the fixture; Pillow is not consulted here)."""
-    for name, crc, size in zip(fx["png_names"], fx["png_crc32"], fx["png_size"]):
-        out = subprocess.run([tools["png_check"], os.path.join(RESULTS, str(name))], capture_output=True, timeout=120)
+def test_png_reader_decodes_cut_reference_pngs_like_pillow(cuts, tools, tmp_path):
+    """host/png_decode.cpp on stb-written PNGs (8-bit RGB, stb's own deflate and filter choice): reference PNGs cut to their
+    first rows with the encoder's bits kept (make_results_pairs.cut_png), rows of all five filter types among them.
+    Same size and the checksum of Pillow's decode (stored in the fixture; Pillow is not consulted here)."""
+    offs, blob = cuts["png_cut_offsets"], cuts["png_cut_bytes"].tobytes()
+    filters = set()
+    for k, (name, crc, size) in enumerate(zip(cuts["png_cut_names"], cuts["png_cut_crc32"], cuts["png_cut_size"])):
+        png = blob[offs[k]:offs[k + 1]]
+        idat = png.index(b"IDAT")
+        raw = zlib.decompress(png[idat + 4:idat + 4 + int.from_bytes(png[idat - 4:idat], "big")])
+        filters |= set(raw[::1 + 3 * int(size[1])])
+        path = tmp_path / f"cut{k}.png"
+        path.write_bytes(png)
+        out = subprocess.run([tools["png_check"], str(path)], capture_output=True, timeout=120)
         assert out.returncode == 0, name
         head, raw = out.stdout.split(b"\n", 1)
         w, h, c = (int(x) for x in head.split())
         assert (h, w, c) == tuple(int(v) for v in size), name
         assert zlib.crc32(raw) == int(crc), name
+    assert filters == {0, 1, 2, 3, 4}, filters
 
 
 @pytest.mark.gpu
