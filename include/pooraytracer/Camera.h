@@ -2,11 +2,15 @@
 // colorAttachment.  Render flattens `world` (cached per object graph), uploads it once, and runs the
 // HIP path tracer through the C ABI (prt_render); colorAttachment receives the fp64 framebuffer.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "HittableList.h"
 #include "Math.h"
+
+struct PrtCamera;
+struct PrtRenderParams;
 
 namespace Pooraytracer {
 class Camera {
@@ -25,6 +29,16 @@ public:
 
     std::vector<color> colorAttachment;
     void Render(Hittable& world, Hittable& lights);
+    // Addition (not in the reference): one progressive render for a whole spp ladder instead of one Render per rung.
+    // sppLadder must be strictly increasing and >= 1.  The frame of rung k is the frame Render would make with
+    // samplesPerPixel = sppLadder[k] (within ~1e-13: summation order, prt.h prt_accum_*), at the cost of the last rung
+    // alone.  Before each onSnapshot call colorAttachment holds that frame and samplesPerPixel equals the rung, so
+    // GetParametersStr() / WriteColorAttachment() name and write it as main.cpp:52 does; `seconds` is the wall clock
+    // since the call began (the first call on a world includes its scene build and upload).  On return
+    // samplesPerPixel is the last rung.  Single device only: a `devices` list of more than one throws
+    // std::invalid_argument.
+    void RenderProgressive(Hittable& world, Hittable& lights, const std::vector<int>& sppLadder,
+                           const std::function<void(int spp, double seconds)>& onSnapshot);
     // 8-bit sRGB PNG (+ Radiance .hdr), Camera.cpp:279-331
     void WriteColorAttachment(const std::string& outputPath, bool bWriteHDR = true) const;
     std::string GetParametersStr() const;
@@ -43,5 +57,11 @@ public:
     std::vector<int> devices; // non-empty: cut the frame into tiles over these GPUs (one host thread each); overrides `device`
     unsigned long long lastRays = 0;
     double lastKernelMs = 0.0;
+
+private:
+    // Render / RenderProgressive: world's scene with the `lights` list, uploaded to devs (cached on world), and this
+    // camera's fields as the C ABI takes them
+    Hittable::DeviceCache& PrepareScene(Hittable& world, Hittable& lights, const std::vector<int>& devs, PrtCamera& c,
+                                        PrtRenderParams& p);
 };
 } // namespace Pooraytracer

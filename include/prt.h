@@ -19,6 +19,8 @@
  *   prt_sample_lights     replaces lights.Sample(origin, record, pdf) (Source/HittableList.h:44-59,
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
  *   prt_get_counters      rays / node fetches / triangle tests / kernel ms of the last call
+ *   prt_accum_*           progressive, resumable rendering: the same frame built up over several calls
+ *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel)
  *
  * Conventions: every function returns 0 on success or a negative PRT_E_* code and never throws;
  * prt_last_error() returns a thread-local message for the last failure.  All input buffers are
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PRT_ABI_VERSION 5
+#define PRT_ABI_VERSION 6
 
 /* error codes */
 #define PRT_OK 0
@@ -333,6 +335,61 @@ int prt_get_counters(PrtScene* scene, PrtCounters* out);
 /* K5 "next" row: NaN scrub + linear->sRGB + clamp -> 8-bit RGB (Camera.cpp:206-221,279-301). */
 int prt_tonemap_srgb8(PrtScene* scene, const void* d_rgb_f32, int width, int height,
                       void* d_rgb_u8, void* hip_stream);
+
+/*
+ * Progressive, resumable rendering.  Camera::Render adds every sample's RayColor * (1/spp) into colorAttachment as it
+ * goes (Source/Camera.cpp:46-83; pixelSamplesScale, :83).  An accumulator reorders that scale: it keeps the RAW fp64
+ * sum of every sample rendered so far per pixel and channel, and divides by the sample count only when a frame is
+ * resolved.  Sample s of pixel (i, j) draws from the stream keyed (seed, j*W+i, s) whatever the pass, so after n samples
+ * the resolved frame is prt_render's frame at spp = n: the same samples, summed in another order (prt_render scales each
+ * term by 1/n and sums per sample chunk; the accumulator sums raw terms per pass chunk, then per pass, then divides) —
+ * about 1e-13 relative apart, not bit for bit.  A ladder of spp 10/50/100/500 frames costs one spp-500 render plus four
+ * resolves instead of the sum of the rungs, a render can be previewed while it runs, stopped, and continued later.
+ *
+ * Camera and render parameters are frozen at create time; params->spp is ignored (the pass size is the argument of
+ * prt_accum_render) and params->reserved must be 0.  sample_chunks applies to each pass; both precisions are supported
+ * (PRT_PRECISION_F32 renders in fp32 and still accumulates in fp64); pixel_jitter, tile_size, rank and nranks behave as
+ * in prt_render: pixels of other ranks' tiles are never touched and stay 0, so the sums of the ranks' accumulators add
+ * up to the single-rank one.  Each pass goes through the scene's two per-call slots like prt_render_device:
+ * prt_get_counters afterwards reports that pass (K3 time only), and two accumulators on two streams behave like two
+ * prt_render_device calls.  Passes and resolves of ONE accumulator are ordered by the library (each waits on its stream
+ * for the previous use of the sums), whatever streams they are issued on.  Each pass retraces the camera ray of every
+ * work item once (the parked primary hit is not kept between passes).
+ *
+ * The sums belong to one geometry: prt_scene_update_vertices bumps a generation counter of the scene, and a pass on
+ * sums of an older generation fails with PRT_E_INVALID until prt_accum_reset.  The fingerprint is a 64-bit hash of the
+ * camera, every parameter that changes a sample's value or a pixel's owner (max_depth, russian_roulette, sample_lights,
+ * precision, background, seed, tile size, rank, nranks, pixel_jitter) and the scene's triangle, mesh and material
+ * COUNTS.  It does NOT detect a different scene that happens to have the same counts: importing a checkpoint into such
+ * a scene silently mixes two scenes.
+ *
+ * LIFETIME: an accumulator holds its scene's pointer and device memory on the scene's device; destroy it before the
+ * scene.  The scene must stay uploaded to the same device (PRT_E_INVALID otherwise).
+ */
+typedef struct PrtAccum PrtAccum;
+/* Zeroed sums (W*H*3 doubles on the scene's device) and 0 samples.  PRT_E_NO_DEVICE if the scene is not uploaded. */
+int prt_accum_create(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* params, PrtAccum** out);
+/* Waits for the accumulator's last pass or resolve, then frees it.  NULL is a no-op. */
+void prt_accum_destroy(PrtAccum* acc);
+/* Asynchronous on hip_stream: adds samples [n, n + n_samples) of every owned pixel, n = prt_accum_samples before the
+ * call.  PRT_E_INVALID for n_samples < 1 or sums of an older scene generation; PRT_E_LIMIT if n + n_samples > INT32_MAX. */
+int prt_accum_render(PrtAccum* acc, int32_t n_samples, void* hip_stream);
+/* Samples per pixel accumulated so far (counted when a pass is issued). */
+int prt_accum_samples(const PrtAccum* acc, uint64_t* n);
+/* Synchronous: zero sums, 0 samples, and the scene's current geometry generation. */
+int prt_accum_reset(PrtAccum* acc);
+/* Asynchronous on hip_stream: the frame of the samples so far into W*H*3 device buffers (any may be NULL, not all):
+ * rgb_f64 = sum / n, rgb_f32 = its float rounding, rgb_u8 = exactly the bytes prt_tonemap_srgb8 makes of rgb_f32 (the
+ * same device code).  With 0 samples the frame is all zeros. */
+int prt_accum_resolve(PrtAccum* acc, void* d_rgb_f64, void* d_rgb_f32, void* d_rgb_u8, void* hip_stream);
+/* Synchronous: the resolved frame into W*H*3 host buffers (either may be NULL, not both). */
+int prt_accum_read(PrtAccum* acc, double* rgb_f64, float* rgb_f32);
+/* Synchronous checkpoint: the W*H*3 raw sums, the sample count and the fingerprint. */
+int prt_accum_export(const PrtAccum* acc, double* sums, uint64_t* samples, uint64_t* fingerprint);
+/* Resume from a checkpoint, in another process or on another PrtScene built from the same description: PRT_E_INVALID if
+ * the fingerprint differs from this accumulator's, PRT_E_LIMIT above INT32_MAX samples.  The sums are taken to belong to
+ * the scene's current geometry. */
+int prt_accum_import(PrtAccum* acc, const double* sums, uint64_t samples, uint64_t fingerprint);
 
 #ifdef __cplusplus
 }

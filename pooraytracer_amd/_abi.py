@@ -5,7 +5,7 @@ tests/test_abi.py checks sizes and that every declared symbol is exported.
 """
 import ctypes as C
 
-PRT_ABI_VERSION = 5
+PRT_ABI_VERSION = 6
 TRACE_WORDS, TRACE_VERTS = 64, 31           # prt.h PRT_TRACE_*
 TRACE_NEE, TRACE_VISIBLE, TRACE_ROULETTE, TRACE_SCATTER = 1, 2, 4, 8
 PRECISION_F64, PRECISION_F32 = 0, 1
@@ -212,6 +212,15 @@ EXPORTS = [
     "prt_material_eval",
     "prt_material_scatter",
     "prt_texture_value",
+    "prt_accum_create",
+    "prt_accum_destroy",
+    "prt_accum_render",
+    "prt_accum_samples",
+    "prt_accum_reset",
+    "prt_accum_resolve",
+    "prt_accum_read",
+    "prt_accum_export",
+    "prt_accum_import",
 ]
 
 

@@ -69,6 +69,16 @@ def load():
     L.prt_texture_value.argtypes = [vp, i32, sz, vp, vp]
     L.prt_render_samples.argtypes = [vp, vp, vp, vp, sz, i32, i32, vp, vp]
     L.prt_render_multi.argtypes = [vp, i32, vp, vp, vp]
+    L.prt_accum_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.prt_accum_destroy.argtypes = [vp]
+    L.prt_accum_destroy.restype = None
+    L.prt_accum_render.argtypes = [vp, C.c_int32, vp]
+    L.prt_accum_samples.argtypes = [vp, C.POINTER(u64)]
+    L.prt_accum_reset.argtypes = [vp]
+    L.prt_accum_resolve.argtypes = [vp, vp, vp, vp, vp]
+    L.prt_accum_read.argtypes = [vp, vp, vp]
+    L.prt_accum_export.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.prt_accum_import.argtypes = [vp, vp, u64, u64]
     if L.prt_abi_version() != _abi.PRT_ABI_VERSION and os.environ.get("PRT_ABI_ANY") != "1":  # (PRT_ABI_ANY: A/B tools timing an older build)
         raise PrtError(-101, "ABI version mismatch between _abi.py and libprt_hip.so")
     try:
@@ -250,6 +260,97 @@ class Scene:
         c = _abi.PrtCounters()
         _check(self._L.prt_get_counters(self._h, C.byref(c)), self._L)
         return {f: getattr(c, f) for f, _ in _abi.PrtCounters._fields_}
+
+
+class Accumulator:
+    """Progressive, resumable rendering (prt_accum_*, include/prt.h): running fp64 sums of every sample rendered so far.
+    After n samples, image() is Scene.render(spp=n) of the same camera and keywords (within ~1e-13: summation order).
+    Keywords as for Scene.render, minus spp (the pass size is add()'s argument); they are frozen here.  Destroy (close, or
+    leave the `with` block) before the scene is closed."""
+
+    def __init__(self, scene, camera=None, **kw):
+        if "spp" in kw:
+            raise TypeError("Accumulator: spp is not a parameter (the pass size is add()'s argument)")
+        self.scene = scene
+        self._L = scene._L
+        self.camera = camera or scene.data.camera
+        self._shape = (self.camera.height, self.camera.width, 3)
+        c, p = _abi.make_camera(self.camera), _abi.make_params(**kw)
+        h = C.c_void_p()
+        _check(self._L.prt_accum_create(scene._h, C.byref(c), C.byref(p), C.byref(h)), self._L)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.prt_accum_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, n, stream=None):
+        """Asynchronous: render the next n samples of every owned pixel and add them to the sums."""
+        if int(n) != n or n < 1:
+            raise ValueError(f"Accumulator.add: n must be an integer >= 1, got {n!r}")
+        _check(self._L.prt_accum_render(self._h, int(n), stream), self._L)
+        return self
+
+    @property
+    def samples(self):
+        n = C.c_uint64(0)
+        _check(self._L.prt_accum_samples(self._h, C.byref(n)), self._L)
+        return n.value
+
+    def image(self, f32=False):
+        """The frame of the samples so far: (H, W, 3) float64, or float32 with f32=True."""
+        out = np.zeros(self._shape, dtype=np.float32 if f32 else np.float64)
+        _check(self._L.prt_accum_read(self._h, None if f32 else out.ctypes.data, out.ctypes.data if f32 else None), self._L)
+        return out
+
+    def resolve(self, d_f64_ptr=None, d_f32_ptr=None, d_u8_ptr=None, stream=None):
+        """Asynchronous resolve into device buffers (raw device pointers, e.g. torch tensor.data_ptr())."""
+        _check(self._L.prt_accum_resolve(self._h, d_f64_ptr, d_f32_ptr, d_u8_ptr, stream), self._L)
+
+    def srgb8(self):
+        """The frame of the samples so far as 8-bit sRGB, (H, W, 3) uint8 (the bytes Scene.tonemap_srgb8 makes of image(f32=True))."""
+        import torch
+        dev = torch.device("cuda", self.scene.device or 0)
+        d = torch.empty(self._shape, dtype=torch.uint8, device=dev)
+        self.resolve(d_u8_ptr=d.data_ptr())
+        torch.cuda.synchronize(dev)
+        return d.cpu().numpy()
+
+    def reset(self):
+        _check(self._L.prt_accum_reset(self._h), self._L)
+        return self
+
+    def state(self):
+        """Checkpoint: (sums (H, W, 3) float64, samples, fingerprint)."""
+        sums = np.zeros(self._shape, dtype=np.float64)
+        n, fp = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.prt_accum_export(self._h, sums.ctypes.data, C.byref(n), C.byref(fp)), self._L)
+        return sums, n.value, fp.value
+
+    def restore(self, sums, samples, fingerprint):
+        """Resume from state() of an accumulator with the same camera, keywords and scene counts (another process or scene)."""
+        sums = np.asarray(sums)
+        if sums.shape != self._shape:
+            raise ValueError(f"Accumulator.restore: sums must have shape {self._shape}, got {sums.shape}")
+        if int(samples) != samples or samples < 0:
+            raise ValueError(f"Accumulator.restore: samples must be an integer >= 0, got {samples!r}")
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        _check(self._L.prt_accum_import(self._h, sums.ctypes.data, int(samples), int(fingerprint)), self._L)
+        return self
 
 
 def render_multi(scene_list, camera=None, **kw):

@@ -35,6 +35,8 @@ void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, do
                    bool count, int feat, unsigned grid, hipStream_t st);
 void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d64, float* d32,
                      hipStream_t st);
+void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st);
+void launch_resolve(const double* d_sum, size_t n, uint64_t samples, double* d64, float* d32, uint8_t* d8, hipStream_t st);
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
                           hipStream_t st);
 void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
@@ -110,6 +112,7 @@ struct PrtScene {
     std::vector<int32_t> light_meshes; // PrtSceneDesc.light_meshes when given
     bool explicit_lights = false;
     bool device_bvh = false; // PRT_SCENE_DEVICE_BVH: the tree is built in prt_scene_upload, on the GPU
+    uint64_t generation = 0; // bumped by every prt_scene_update_vertices: an accumulator's sums belong to one geometry
     PrtBvhInfo bvh_info{};
     // device side
     int device = -1;
@@ -662,6 +665,7 @@ int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double*
     if (!s || (!vertices && !s->tris.empty())) return fail(PRT_E_INVALID, "prt_scene_update_vertices: null argument");
     for (size_t i = 0; i < s->tris.size() * 9; ++i)
         if (!(std::fabs(vertices[i]) <= 1e18)) return fail(PRT_E_INVALID, "prt_scene_update_vertices: vertex coordinate is not finite (or beyond 1e18)");
+    ++s->generation; // the geometry changes from here on, even if the update fails half way
     try {
         prt::update_triangles(vertices, normals, s->tris);
         PrtSceneDesc d;
@@ -1028,6 +1032,19 @@ int prt_texture_value(PrtScene* s, int32_t texture, size_t n, const double* uv, 
     return PRT_OK;
 }
 
+// What one K3 launch renders and where its item sums go.  prt_render_device: samples [0, spp) of a frame, scaled by 1/spp
+// (Camera.cpp:83) and written by K5 into cleared framebuffers.  prt_accum_render: samples [first, first + spp), unscaled
+// (the launch runs with spp = 1, so an item's partial sum is the raw sum of its samples' RayColor), added by k_accumulate
+// into an accumulator's running sums; the chunks of the launch are sized for `spp` samples either way.
+struct RenderPass {
+    int spp;
+    int32_t first = 0;
+    double* d_sum = nullptr;
+};
+
+static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const PrtRenderParams* p, const RenderPass& pass,
+                       void* d_rgb_f64, void* d_rgb_f32, int count_work, hipStream_t st);
+
 int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, void* d_rgb_f64, void* d_rgb_f32,
                       int count_work, void* stream) {
     int rc = require_uploaded(s, "prt_render_device");
@@ -1035,17 +1052,25 @@ int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* 
     if (!cam || !p) return fail(PRT_E_INVALID, "prt_render_device: null argument");
     if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, "prt_render_device: bad image size");
     if (p->spp < 1) return fail(PRT_E_INVALID, "prt_render_device: spp must be >= 1");
-    if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, "prt_render_device: unsupported precision");
+    RenderPass pass;
+    pass.spp = p->spp;
+    return render_impl(s, "prt_render_device", cam, p, pass, d_rgb_f64, d_rgb_f32, count_work, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const PrtRenderParams* p, const RenderPass& pass,
+                       void* d_rgb_f64, void* d_rgb_f32, int count_work, hipStream_t st) {
+    int rc = PRT_OK;
+    const std::string w(who);
+    if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
     const bool f32 = p->precision == PRT_PRECISION_F32;
     if (f32 && (rc = ensure_f32(s))) return rc;
-    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, "prt_render_device: bad rank/nranks");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, w + ": bad rank/nranks");
 
     DCamera C;
     prt::setup_camera(*cam, C);
     DRenderParams P;
     std::memset(&P, 0, sizeof(P));
-    P.spp = p->spp;
+    P.spp = pass.d_sum ? 1 : pass.spp;
     P.max_depth = p->max_depth;
     P.sample_lights = p->sample_lights ? 1 : 0;
     P.rr = p->russian_roulette;
@@ -1095,7 +1120,7 @@ int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* 
     //    with per-wave timestamps: 58.3 ms launch, queue dry at 52.5 ms).  Sizes are capped at `body`
     //    samples; the per-item fetch is one wave-aggregated atomic.
     std::vector<int> sizes;
-    const int spp = p->spp;
+    const int spp = pass.spp;
     int want = p->sample_chunks;
     if (const char* e = dev_env("PRT_TUNE_CHUNKS")) want = std::atoi(e);
     if (want > 0) {
@@ -1131,11 +1156,11 @@ int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* 
     sizes.erase(std::remove(sizes.begin(), sizes.end(), 0), sizes.end());
     if (sizes.empty()) sizes.push_back(spp);
     int chunks = (int)sizes.size();
-    P.chunk_begin[0] = 0;
+    P.chunk_begin[0] = pass.first;
     for (int c = 0; c < chunks; ++c) P.chunk_begin[c + 1] = P.chunk_begin[c] + sizes[c];
     P.chunks = chunks;
     P.n_items = P.items_per_chunk * (uint64_t)chunks;
-    if (P.n_items >= 0xffffffffULL) return fail(PRT_E_LIMIT, "prt_render_device: more than 2^32 work items (pixels x sample chunks) in one launch");
+    if (P.n_items >= 0xffffffffULL) return fail(PRT_E_LIMIT, w + ": more than 2^32 work items (pixels x sample chunks) in one launch");
 
     const size_t need = std::max<size_t>(P.n_items * 3, 3);
     hipError_t we;
@@ -1214,7 +1239,8 @@ int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* 
         std::fprintf(stderr, "[prt] dumped %zu of %llu rays to %s\n", nd, h.ray_dump_n, dump_path.c_str());
     }
     if (P.n_items) {
-        prt::launch_finalize(C, P, q.d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
+        if (pass.d_sum) prt::launch_accumulate(C, P, q.d_partial, pass.d_sum, st);
+        else prt::launch_finalize(C, P, q.d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
         PRT_HIP(hipGetLastError());
     }
     PRT_HIP(hipEventRecord(q.done, st));
@@ -1523,6 +1549,204 @@ int prt_get_counters(PrtScene* s, PrtCounters* out) {
     }
     s->last = c;
     *out = c;
+    return PRT_OK;
+}
+
+// ------------------------------------------------------------------ progressive rendering (PrtAccum)
+} // extern "C"
+
+// Running fp64 sums of every sample rendered so far, one per real of the full frame (pixels of other ranks' tiles stay 0).
+// Camera and parameters are frozen at create time.  `done` is recorded behind the last kernel that read or wrote the sums,
+// and every later use of them waits for it first: passes on different streams are ordered, not raced.
+struct PrtAccum {
+    PrtScene* scene = nullptr;
+    PrtCamera cam{};
+    PrtRenderParams params{};
+    int device = -1;
+    uint64_t generation = 0; // the scene geometry (PrtScene::generation) the sums were rendered from
+    uint64_t samples = 0;
+    uint64_t fingerprint = 0;
+    size_t n = 0; // W * H * 3
+    double* d_sum = nullptr;
+    hipEvent_t done = nullptr;
+};
+
+namespace {
+struct Fnv {
+    uint64_t h = 1469598103934665603ULL;
+    template <typename T>
+    void add(const T& v) {
+        unsigned char b[sizeof(T)];
+        std::memcpy(b, &v, sizeof(T));
+        for (unsigned char c : b) h = (h ^ c) * 1099511628211ULL;
+    }
+};
+// Everything that changes a sample's value or a pixel's owner, plus the scene's counts (not its contents).
+uint64_t accum_fingerprint(const PrtScene* s, const PrtCamera& c, const PrtRenderParams& p) {
+    Fnv f;
+    f.add((uint32_t)0x70727461u); // layout tag of this hash
+    f.add(c.width); f.add(c.height); f.add(c.fovy);
+    for (int k = 0; k < 3; ++k) { f.add(c.eye[k]); f.add(c.look_at[k]); f.add(c.up[k]); }
+    f.add(p.max_depth); f.add(p.russian_roulette); f.add((int32_t)(p.sample_lights ? 1 : 0)); f.add(p.precision);
+    for (int k = 0; k < 3; ++k) f.add(p.background[k]);
+    f.add(p.seed);
+    int tile = p.tile_size > 0 ? p.tile_size : 32; // as render_impl rounds it
+    tile = std::max(8, (tile + 7) / 8 * 8);
+    f.add((int32_t)tile); f.add(p.rank); f.add(p.nranks); f.add((int32_t)(p.pixel_jitter ? 1 : 0));
+    f.add((uint64_t)s->tris.size()); f.add((uint64_t)s->mesh_mat.size()); f.add((uint64_t)s->mats.size());
+    return f.h;
+}
+// The accumulator's scene is uploaded, to the device the sums live on.
+int accum_ready(PrtAccum* a, const char* who) {
+    if (!a) return fail(PRT_E_INVALID, std::string(who) + ": null accumulator");
+    int rc = require_uploaded(a->scene, who);
+    if (rc) return rc;
+    if (a->scene->device != a->device) return fail(PRT_E_INVALID, std::string(who) + ": the scene was uploaded to another device since the accumulator was created");
+    return PRT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int prt_accum_create(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, PrtAccum** out) {
+    if (!out) return fail(PRT_E_INVALID, "prt_accum_create: null argument");
+    *out = nullptr;
+    int rc = require_uploaded(s, "prt_accum_create");
+    if (rc) return rc;
+    if (!cam || !p) return fail(PRT_E_INVALID, "prt_accum_create: null argument");
+    if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, "prt_accum_create: bad image size");
+    if (p->reserved != 0) return fail(PRT_E_INVALID, "prt_accum_create: reserved must be 0");
+    if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, "prt_accum_create: unsupported precision");
+    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, "prt_accum_create: bad rank/nranks");
+    if (p->precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
+    PrtAccum* a = new (std::nothrow) PrtAccum();
+    if (!a) return fail(PRT_E_OOM, "prt_accum_create: out of host memory");
+    a->scene = s;
+    a->cam = *cam;
+    a->params = *p;
+    a->params.spp = 0; // the pass size is prt_accum_render's argument
+    a->device = s->device;
+    a->generation = s->generation;
+    a->fingerprint = accum_fingerprint(s, *cam, *p);
+    a->n = (size_t)cam->width * cam->height * 3;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->d_sum), a->n * sizeof(double));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr);
+    if (e == hipSuccess) e = hipEventRecord(a->done, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(a->done);
+    if (e != hipSuccess) {
+        prt_accum_destroy(a);
+        return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_accum_create: ") + hipGetErrorString(e));
+    }
+    *out = a;
+    return PRT_OK;
+}
+
+void prt_accum_destroy(PrtAccum* a) {
+    if (!a) return;
+    if (a->device >= 0) (void)hipSetDevice(a->device);
+    if (a->done) {
+        (void)hipEventSynchronize(a->done);
+        (void)hipEventDestroy(a->done);
+    }
+    if (a->d_sum) (void)hipFree(a->d_sum);
+    delete a;
+}
+
+int prt_accum_render(PrtAccum* a, int32_t n_samples, void* stream) {
+    int rc = accum_ready(a, "prt_accum_render");
+    if (rc) return rc;
+    if (n_samples < 1) return fail(PRT_E_INVALID, "prt_accum_render: n_samples must be >= 1");
+    if (a->samples + (uint64_t)n_samples > (uint64_t)INT32_MAX)
+        return fail(PRT_E_LIMIT, "prt_accum_render: sample indices would pass INT32_MAX");
+    if (a->generation != a->scene->generation)
+        return fail(PRT_E_INVALID, "prt_accum_render: the scene's vertices were updated since these sums were rendered (prt_accum_reset first)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    RenderPass pass;
+    pass.spp = n_samples;
+    pass.first = (int32_t)a->samples;
+    pass.d_sum = a->d_sum;
+    if ((rc = render_impl(a->scene, "prt_accum_render", &a->cam, &a->params, pass, nullptr, nullptr, 0, st))) return rc;
+    PRT_HIP(hipEventRecord(a->done, st));
+    a->samples += (uint64_t)n_samples;
+    return PRT_OK;
+}
+
+int prt_accum_samples(const PrtAccum* a, uint64_t* n) {
+    if (!a || !n) return fail(PRT_E_INVALID, "prt_accum_samples: null argument");
+    *n = a->samples;
+    return PRT_OK;
+}
+
+int prt_accum_reset(PrtAccum* a) {
+    int rc = accum_ready(a, "prt_accum_reset");
+    if (rc) return rc;
+    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr));
+    PRT_HIP(hipEventRecord(a->done, nullptr));
+    PRT_HIP(hipEventSynchronize(a->done));
+    a->samples = 0;
+    a->generation = a->scene->generation;
+    return PRT_OK;
+}
+
+int prt_accum_resolve(PrtAccum* a, void* d_rgb_f64, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
+    int rc = accum_ready(a, "prt_accum_resolve");
+    if (rc) return rc;
+    if (!d_rgb_f64 && !d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, "prt_accum_resolve: no output buffer");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    prt::launch_resolve(a->d_sum, a->n, a->samples, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32),
+                        static_cast<uint8_t*>(d_rgb_u8), st);
+    PRT_HIP(hipGetLastError());
+    PRT_HIP(hipEventRecord(a->done, st));
+    return PRT_OK;
+}
+
+int prt_accum_read(PrtAccum* a, double* rgb_f64, float* rgb_f32) {
+    int rc = accum_ready(a, "prt_accum_read");
+    if (rc) return rc;
+    if (!rgb_f64 && !rgb_f32) return fail(PRT_E_INVALID, "prt_accum_read: no output buffer");
+    void *d64 = nullptr, *d32 = nullptr;
+    hipError_t e = rgb_f64 ? hipMalloc(&d64, a->n * sizeof(double)) : hipSuccess;
+    if (e == hipSuccess && rgb_f32) e = hipMalloc(&d32, a->n * sizeof(float));
+    if (e == hipSuccess) {
+        rc = prt_accum_resolve(a, d64, d32, nullptr, nullptr);
+        if (rc == PRT_OK) {
+            e = hipEventSynchronize(a->done);
+            if (e == hipSuccess && rgb_f64) e = hipMemcpy(rgb_f64, d64, a->n * sizeof(double), hipMemcpyDeviceToHost);
+            if (e == hipSuccess && rgb_f32) e = hipMemcpy(rgb_f32, d32, a->n * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (d64) (void)hipFree(d64);
+    if (d32) (void)hipFree(d32);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_accum_read: ") + hipGetErrorString(e));
+    return PRT_OK;
+}
+
+int prt_accum_export(const PrtAccum* a, double* sums, uint64_t* samples, uint64_t* fingerprint) {
+    if (!a || !sums || !samples || !fingerprint) return fail(PRT_E_INVALID, "prt_accum_export: null argument");
+    PRT_HIP(hipSetDevice(a->device));
+    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipMemcpy(sums, a->d_sum, a->n * sizeof(double), hipMemcpyDeviceToHost));
+    *samples = a->samples;
+    *fingerprint = a->fingerprint;
+    return PRT_OK;
+}
+
+int prt_accum_import(PrtAccum* a, const double* sums, uint64_t samples, uint64_t fingerprint) {
+    int rc = accum_ready(a, "prt_accum_import");
+    if (rc) return rc;
+    if (!sums) return fail(PRT_E_INVALID, "prt_accum_import: null argument");
+    if (fingerprint != a->fingerprint)
+        return fail(PRT_E_INVALID, "prt_accum_import: fingerprint mismatch (other camera, render parameters or scene counts)");
+    if (samples > (uint64_t)INT32_MAX) return fail(PRT_E_LIMIT, "prt_accum_import: more than INT32_MAX samples");
+    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipMemcpy(a->d_sum, sums, a->n * sizeof(double), hipMemcpyHostToDevice));
+    a->samples = samples;
+    a->generation = a->scene->generation;
     return PRT_OK;
 }
 

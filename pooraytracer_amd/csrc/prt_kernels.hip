@@ -748,6 +748,17 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
 
 #if !PRT_F32_TU
 // ------------------------------------------------------------------------------------------- K5
+// Sum over the chunks (fixed order) of owned item oi's partial sums: the one summation k_finalize and k_accumulate share.
+PRT_DEV void chunk_sum(const DRenderParams& P, const double* __restrict__ partial, uint64_t oi, double& r, double& g, double& b) {
+    r = 0, g = 0, b = 0;
+    for (int c = 0; c < P.chunks; ++c) {
+        const double* p = partial + ((uint64_t)c * P.items_per_chunk + oi) * 3;
+        r += p[0];
+        g += p[1];
+        b += p[2];
+    }
+}
+
 // out[pixel] = sum over chunks (fixed order) of the item partial sums; pixels of other ranks' tiles
 // were zeroed by a memset so that the cross-rank sum is exact.
 __global__ void k_finalize(DCamera C, DRenderParams P, const double* __restrict__ partial, double* __restrict__ out64,
@@ -756,13 +767,8 @@ __global__ void k_finalize(DCamera C, DRenderParams P, const double* __restrict_
     if (oi >= P.items_per_chunk) return;
     int px, py;
     if (!owned_to_pixel(P, C, oi, px, py)) return;
-    double r = 0, g = 0, b = 0;
-    for (int c = 0; c < P.chunks; ++c) {
-        const double* p = partial + ((uint64_t)c * P.items_per_chunk + oi) * 3;
-        r += p[0];
-        g += p[1];
-        b += p[2];
-    }
+    double r, g, b;
+    chunk_sum(P, partial, oi, r, g, b);
     const size_t m = ((size_t)py * C.width + px) * 3;
     if (out64) {
         out64[m] = r;
@@ -774,6 +780,22 @@ __global__ void k_finalize(DCamera C, DRenderParams P, const double* __restrict_
         out32[m + 1] = (float)g;
         out32[m + 2] = (float)b;
     }
+}
+
+// Progressive rendering (prt_accum_render): sum[pixel] += the pass's item sum, taken over the chunks exactly as
+// k_finalize takes it.  The pass ran with spp = 1, so items hold raw sums of RayColor.  One thread per owned item, so
+// every pixel has one writer and no atomic is needed (the sums are deterministic); other ranks' pixels are not touched.
+__global__ void k_accumulate(DCamera C, DRenderParams P, const double* __restrict__ partial, double* __restrict__ sum) {
+    const uint64_t oi = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (oi >= P.items_per_chunk) return;
+    int px, py;
+    if (!owned_to_pixel(P, C, oi, px, py)) return;
+    double r, g, b;
+    chunk_sum(P, partial, oi, r, g, b);
+    const size_t m = ((size_t)py * C.width + px) * 3;
+    sum[m] += r;
+    sum[m + 1] += g;
+    sum[m + 2] += b;
 }
 
 __global__ void k_sample_lights(DScene S, const double* __restrict__ origins, size_t n, uint64_t seed,
@@ -827,15 +849,33 @@ __global__ void k_texture_value(DScene S, int texture, const double* __restrict_
 }
 
 // Camera::WriteColorAttachment's per-pixel transform (Camera.cpp:279-301): NaN -> 0, LinearToSRGB
-// (:214-221), clamp to [0, 0.9999], * 255 truncated to uint8.
-__global__ void k_tonemap(const float* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double v = (double)in[i];
+// (:214-221), clamp to [0, 0.9999], * 255 truncated to uint8.  Shared by k_tonemap and k_resolve.
+PRT_DEV uint8_t srgb8_of(float x) {
+    double v = (double)x;
     if (v != v) v = 0.0;
     double sv = (v <= 0.0031308) ? 12.92 * v : 1.055 * pow(v, (1. / 2.4)) - 0.055;
     sv = sv < 0.0 ? 0.0 : (sv > 0.9999 ? 0.9999 : sv);
-    out[i] = (uint8_t)(sv * 255);
+    return (uint8_t)(sv * 255);
+}
+__global__ void k_tonemap(const float* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = srgb8_of(in[i]);
+}
+
+// Progressive rendering (prt_accum_resolve): the frame of `samples` accumulated samples, element-wise over the n
+// reals of the full frame: sum / samples in fp64, the fp32 frame its rounding, the 8-bit sRGB frame k_tonemap's bytes of
+// that fp32 value.  An accumulator without samples resolves to zeros.  Memory-bound: grid-stride over a capped grid.
+__global__ void k_resolve(const double* __restrict__ sum, size_t n, uint64_t samples, double* __restrict__ out64,
+                          float* __restrict__ out32, uint8_t* __restrict__ out8) {
+    const double ns = (double)samples;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const double v = samples ? sum[i] / ns : 0.0;
+        const float f = (float)v;
+        if (out64) out64[i] = v;
+        if (out32) out32[i] = f;
+        if (out8) out8[i] = srgb8_of(f);
+    }
 }
 
 // dst += src (fp32 framebuffers of tile shares that live on ONE device: disjoint tiles, so every element is x + 0)
@@ -986,6 +1026,16 @@ void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_p
     unsigned grid = (unsigned)((P.items_per_chunk + 255) / 256);
     if (grid == 0) return;
     hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, C, P, d_partial, d64, d32);
+}
+void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st) {
+    unsigned grid = (unsigned)((P.items_per_chunk + 255) / 256);
+    if (grid == 0) return;
+    hipLaunchKernelGGL(k_accumulate, dim3(grid), dim3(256), 0, st, C, P, d_partial, d_sum);
+}
+void launch_resolve(const double* d_sum, size_t n, uint64_t samples, double* d64, float* d32, uint8_t* d8, hipStream_t st) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, d_sum, n, samples, d64, d32, d8);
 }
 
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,

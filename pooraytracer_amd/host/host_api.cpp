@@ -2,10 +2,12 @@
 // C++ surface (include/pooraytracer/*.h) implemented on top of the C ABI of libprt_hip.so.
 // Nothing here intersects or shades: scene description, flattening, one-time set-up and file output.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
@@ -327,12 +329,12 @@ void DebugMaterial::Describe(PrtMaterial& o, shared_ptr<Texture>*) const {
 void EmptyMaterial::Describe(PrtMaterial& o, shared_ptr<Texture>*) const { Zero(o, PRT_MAT_EMPTY); }
 
 // ------------------------------------------------------------------ Camera
-void Camera::Render(Hittable& world, Hittable& lights) {
+Hittable::DeviceCache& Camera::PrepareScene(Hittable& world, Hittable& lights, const std::vector<int>& devs, PrtCamera& c,
+                                            PrtRenderParams& p) {
     imageWidth = (imageWidth < 1) ? 1 : imageWidth; // Camera.cpp:77-78
     imageHeight = (imageHeight < 1) ? 1 : imageHeight;
     Hittable::DeviceCache& dc = world.Device();
     const unsigned sceneFlags = bBuildBvhOnDevice ? PRT_SCENE_DEVICE_BVH : 0u;
-    const std::vector<int> devs = devices.empty() ? std::vector<int>{device} : devices;
     // `lights` is honoured as given (Camera.cpp:137-139 samples whatever list the caller passes): it is expressed as
     // the list of world meshes it is made of, in its own order.  The list main.cpp:36-45 builds — every emissive mesh,
     // in mesh order — is the library's default and needs nothing extra.  A lights list holding geometry that is not a
@@ -363,12 +365,10 @@ void Camera::Render(Hittable& world, Hittable& lights) {
     }
     dc.Ensure(world, devs[0], sceneFlags);
     dc.EnsureReplicas(devs, sceneFlags);
-    PrtCamera c;
     c.width = imageWidth; c.height = imageHeight; c.fovy = fovy;
     c.eye[0] = eye.x; c.eye[1] = eye.y; c.eye[2] = eye.z;
     c.look_at[0] = lookAt.x; c.look_at[1] = lookAt.y; c.look_at[2] = lookAt.z;
     c.up[0] = up.x; c.up[1] = up.y; c.up[2] = up.z;
-    PrtRenderParams p;
     std::memset(&p, 0, sizeof(p));
     p.spp = samplesPerPixel;
     p.max_depth = maxDepth;
@@ -381,6 +381,14 @@ void Camera::Render(Hittable& world, Hittable& lights) {
     p.rank = 0;
     p.nranks = 1;
     p.pixel_jitter = bPixelJitter ? 1 : 0;
+    return dc;
+}
+
+void Camera::Render(Hittable& world, Hittable& lights) {
+    const std::vector<int> devs = devices.empty() ? std::vector<int>{device} : devices;
+    PrtCamera c;
+    PrtRenderParams p;
+    Hittable::DeviceCache& dc = PrepareScene(world, lights, devs, c, p);
     std::vector<double> rgb((size_t)imageWidth * imageHeight * 3);
     if (devs.size() == 1) {
         check(prt_render(dc.scene, &c, &p, rgb.data(), nullptr), "prt_render");
@@ -408,6 +416,40 @@ void Camera::Render(Hittable& world, Hittable& lights) {
             lastRays += cnt.rays_closest + cnt.rays_shadow;
             lastKernelMs = std::max(lastKernelMs, cnt.kernel_ms); // the devices run concurrently
         }
+}
+
+void Camera::RenderProgressive(Hittable& world, Hittable& lights, const std::vector<int>& sppLadder,
+                               const std::function<void(int spp, double seconds)>& onSnapshot) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (devices.size() > 1) throw std::invalid_argument("Camera::RenderProgressive: one device only (`devices` lists several)");
+    if (sppLadder.empty()) throw std::invalid_argument("Camera::RenderProgressive: empty spp ladder");
+    for (size_t k = 0; k < sppLadder.size(); ++k)
+        if (sppLadder[k] < 1 || (k > 0 && sppLadder[k] <= sppLadder[k - 1]))
+            throw std::invalid_argument("Camera::RenderProgressive: the spp ladder must be strictly increasing and >= 1");
+    const std::vector<int> devs{devices.empty() ? device : devices[0]};
+    PrtCamera c;
+    PrtRenderParams p;
+    Hittable::DeviceCache& dc = PrepareScene(world, lights, devs, c, p);
+    PrtAccum* acc = nullptr;
+    check(prt_accum_create(dc.scene, &c, &p, &acc), "prt_accum_create");
+    std::unique_ptr<PrtAccum, void (*)(PrtAccum*)> guard(acc, prt_accum_destroy); // destroyed before the scene, on every way out
+    std::vector<double> rgb((size_t)imageWidth * imageHeight * 3);
+    int done = 0;
+    for (const int rung : sppLadder) {
+        // one pass per rung: samples [done, rung) of every pixel are added to the running sums
+        check(prt_accum_render(acc, rung - done, nullptr), "prt_accum_render");
+        done = rung;
+        PrtCounters cnt;
+        if (prt_get_counters(dc.scene, &cnt) == PRT_OK) { // (synchronises with the pass)
+            lastRays = cnt.rays_closest + cnt.rays_shadow;
+            lastKernelMs = cnt.kernel_ms;
+        }
+        check(prt_accum_read(acc, rgb.data(), nullptr), "prt_accum_read");
+        colorAttachment.assign((size_t)imageWidth * imageHeight, color(0., 0., 0.));
+        for (size_t i = 0; i < colorAttachment.size(); ++i) colorAttachment[i] = color(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
+        samplesPerPixel = rung;
+        onSnapshot(rung, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    }
 }
 
 std::string Camera::GetParametersStr() const { // Camera.cpp:332-337
