@@ -1,11 +1,17 @@
 // pooraytracer_main.cpp — the reference's main.cpp (main.cpp:6-55) against the drop-in host API, with
 // the hard-coded scene name / spp / depth turned into arguments:
 //   pooraytracer_main <resources_dir> <scene_name> [spp=100] [depth=100] [out_dir=.] [out.f64] [--ladder=S1,S2,...]
+//                     [--adaptive=REL_TOL [--min-spp=M] [--counts=counts.u32]]
 // Reads <resources_dir>/<scene>/<scene>.obj|.mtl|.xml like the reference, renders on the GPU, writes
 // <scene>_spp<S>-depth<D>_<seconds>s.png + .hdr (main.cpp:52 naming, timestamp omitted).
 // --ladder (anywhere on the line): one progressive render (Camera::RenderProgressive) that writes a .png + .hdr per rung
 // of the strictly increasing spp list, for the cost of the last rung; spp is then ignored, <seconds> is the time since the
 // render began, and out.f64 receives the last rung's frame.
+// --adaptive=REL_TOL (anywhere on the line): adaptive sampling (Camera::RenderAdaptive, abs_tol 0, the library's default
+// batch): spp is then the largest number of samples a pixel may get (max_spp, rounded down to a multiple of the batch),
+// no pixel gets fewer than --min-spp (default 64, capped at max_spp), and every round after the first adds min_spp
+// samples.  The frame is written as <scene>_adaptive<REL_TOL>_spp<S>-depth<D>_<seconds>s.png + .hdr, S = the largest
+// per-pixel count; --counts=FILE receives the W*H per-pixel counts (uint32, row by row) and out.f64 the frame.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -25,9 +31,16 @@ int main(int argc_all, char** argv_all) {
     // --ladder=... may stand anywhere: the positional arguments are the others, in order
     std::vector<int> ladder;
     std::vector<char*> args;
+    std::string adaptive, minSppArg, countsPath;
     for (int i = 0; i < argc_all; ++i) {
         const std::string a = argv_all[i];
-        if (i > 0 && a.rfind("--ladder=", 0) == 0) {
+        if (i > 0 && a.rfind("--adaptive=", 0) == 0) {
+            adaptive = a.substr(11);
+        } else if (i > 0 && a.rfind("--min-spp=", 0) == 0) {
+            minSppArg = a.substr(10);
+        } else if (i > 0 && a.rfind("--counts=", 0) == 0) {
+            countsPath = a.substr(9);
+        } else if (i > 0 && a.rfind("--ladder=", 0) == 0) {
             std::string list = a.substr(9);
             for (size_t at = 0; at <= list.size();) {
                 const size_t comma = std::min(list.find(',', at), list.size());
@@ -47,8 +60,21 @@ int main(int argc_all, char** argv_all) {
     }
     const int argc = (int)args.size();
     char** argv = args.data();
+    double relTol = 0.0;
+    if (!adaptive.empty()) {
+        char* end = nullptr;
+        relTol = std::strtod(adaptive.c_str(), &end);
+        if (*end != '\0' || !(relTol >= 0.0) || relTol > 1e300) {
+            std::fprintf(stderr, "error: --adaptive wants a relative tolerance >= 0, got '%s'\n", adaptive.c_str());
+            return 2;
+        }
+        if (!ladder.empty()) {
+            std::fprintf(stderr, "error: --adaptive and --ladder exclude each other\n");
+            return 2;
+        }
+    }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...]\n", argv_all[0]);
+        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...] [--adaptive=REL_TOL [--min-spp=M] [--counts=FILE]]\n", argv_all[0]);
         return 2;
     }
     try {
@@ -74,6 +100,40 @@ int main(int argc_all, char** argv_all) {
         lights = HittableList(make_shared<BVHNode>(lights));
 
         const std::string outDir = argc > 5 ? argv[5] : ".";
+        if (!adaptive.empty()) {
+            const int batch = PRT_ADAPTIVE_DEFAULT_BATCH;
+            const int maxSpp = camera.samplesPerPixel / batch * batch;
+            int minSpp = minSppArg.empty() ? 64 : std::atoi(minSppArg.c_str());
+            minSpp = std::min(minSpp, maxSpp) / batch * batch;
+            if (maxSpp < 2 * batch || minSpp < 2 * batch) {
+                std::fprintf(stderr, "error: --adaptive needs spp and --min-spp of at least %d (two batches of %d)\n", 2 * batch, batch);
+                return 2;
+            }
+            std::vector<uint32_t> counts;
+            const auto start = std::chrono::steady_clock::now();
+            const int rounds = camera.RenderAdaptive(world, lights, relTol, minSpp, maxSpp, &counts);
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+            char t[64];
+            std::snprintf(t, sizeof(t), "%.2fs", sec);
+            const std::string png = outDir + "/" + fileName + "_adaptive" + adaptive + "_" + camera.GetParametersStr() + "_" + t + ".png";
+            camera.WriteColorAttachment(png);
+            double total = 0;
+            for (const uint32_t n : counts) total += n;
+            std::printf("%s: %dx%d adaptive rel_tol %s, spp %d..%d, %d rounds, mean %.1f samples per pixel, %.3f s (includes BVH build + upload) -> %s\n",
+                        fileName.c_str(), camera.imageWidth, camera.imageHeight, adaptive.c_str(), minSpp, maxSpp, rounds,
+                        total / std::max<size_t>(1, counts.size()), sec, png.c_str());
+            if (!countsPath.empty()) {
+                std::ofstream o(countsPath, std::ios::binary);
+                o.write(reinterpret_cast<const char*>(counts.data()), (std::streamsize)(counts.size() * sizeof(uint32_t)));
+            }
+            if (argc > 6) {
+                std::ofstream o(argv[6], std::ios::binary);
+                o.write(reinterpret_cast<const char*>(camera.colorAttachment.data()),
+                        (std::streamsize)(camera.colorAttachment.size() * sizeof(color)));
+            }
+            prt_shutdown();
+            return 0;
+        }
         if (!ladder.empty()) {
             camera.RenderProgressive(world, lights, ladder, [&](int, double sec) {
                 char t[64];

@@ -2,6 +2,7 @@
 // colorAttachment.  Render flattens `world` (cached per object graph), uploads it once, and runs the
 // HIP path tracer through the C ABI (prt_render); colorAttachment receives the fp64 framebuffer.
 #pragma once
+#include <cstdint>
 #include <functional>
 #include <string>
 #include <vector>
@@ -39,6 +40,15 @@ public:
     // std::invalid_argument.
     void RenderProgressive(Hittable& world, Hittable& lights, const std::vector<int>& sppLadder,
                            const std::function<void(int spp, double seconds)>& onSnapshot);
+    // Addition (not in the reference): adaptive sampling (prt.h prt_accum_*_adaptive).  Every pixel gets samples in rounds
+    // until its noise estimate meets max(relTol * |mean|, absTol), never fewer than minSpp and never more than maxSpp;
+    // a pixel that stopped after n samples holds the value Render gives it at samplesPerPixel = n (within ~1e-13).  The
+    // first round renders minSpp samples, every later one roundSpp (0: minSpp).  minSpp, maxSpp and roundSpp are multiples
+    // of batch (0: the library's default, PRT_ADAPTIVE_DEFAULT_BATCH).  On return colorAttachment holds the frame,
+    // samplesPerPixel the largest per-pixel count, and `counts` (when given) the W*H counts, row by row.  Returns the number
+    // of rounds that rendered.  Single device only, like RenderProgressive.
+    int RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int minSpp, int maxSpp,
+                       std::vector<uint32_t>* counts = nullptr, double absTol = 0.0, int batch = 0, int roundSpp = 0);
     // 8-bit sRGB PNG (+ Radiance .hdr), Camera.cpp:279-331
     void WriteColorAttachment(const std::string& outputPath, bool bWriteHDR = true) const;
     std::string GetParametersStr() const;

@@ -20,7 +20,8 @@
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
  *   prt_get_counters      rays / node fetches / triangle tests / kernel ms of the last call
  *   prt_accum_*           progressive, resumable rendering: the same frame built up over several calls
- *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel)
+ *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel);
+ *                         the *_adaptive ones stop each pixel once its noise estimate meets a tolerance
  *
  * Conventions: every function returns 0 on success or a negative PRT_E_* code and never throws;
  * prt_last_error() returns a thread-local message for the last failure.  All input buffers are
@@ -390,6 +391,63 @@ int prt_accum_export(const PrtAccum* acc, double* sums, uint64_t* samples, uint6
  * the fingerprint differs from this accumulator's, PRT_E_LIMIT above INT32_MAX samples.  The sums are taken to belong to
  * the scene's current geometry. */
 int prt_accum_import(PrtAccum* acc, const double* sums, uint64_t samples, uint64_t fingerprint);
+
+/*
+ * Adaptive sampling.  An adaptive accumulator gives each pixel samples until its own noise estimate meets a tolerance.
+ * Per pixel it keeps the raw fp64 RGB sum (as above), `moment` (fp64) and `count` (uint32, the pixel's samples n_p);
+ * it also keeps one global count n.  Every pixel still running has count == n, so a round renders samples [n, n + k)
+ * of every pixel it renders, and a pixel that stopped after n_p samples holds exactly prt_render(spp = n_p)'s value for
+ * that pixel (up to summation order, as above).
+ *
+ * Samples come in batches of `batch` consecutive samples; a batch is one work item of the path tracer, so its sum is a
+ * chunk partial.  With Y(rgb) = 0.2126 R + 0.7152 G + 0.0722 B and T_c = Y(batch c's RGB sum):
+ *     moment_p  = sum_c T_c^2 / batch                              (batches added in sample order)
+ *     C = n_p / batch,  S = Y(sum_p),  mean = S / n_p
+ *     var       = max(0, moment_p - S^2 / n_p) / (C - 1)            (batch means: unbiased per-sample variance)
+ *     se        = sqrt(var / n_p)
+ *     converged = se <= max(rel_tol * |mean|, abs_tol)              (false for NaN: a NaN pixel runs to max_spp)
+ * A pixel is ACTIVE iff it is owned by this rank, count == n, count < max_spp and not (count >= min_spp and
+ * converged).  A stopped pixel's state never changes again, so the rule never revives it.  The outcome of a pixel
+ * depends on its own samples only: the tile shares of nranks accumulators add up to the single-rank state.
+ *
+ * prt_accum_resolve / prt_accum_read divide each pixel by its own count (0 where the count is 0); prt_accum_samples is
+ * n (the largest count); prt_accum_reset zeroes sums, moments, counts and n.  prt_accum_render, prt_accum_export and
+ * prt_accum_import fail with PRT_E_INVALID on an adaptive accumulator (a plain checkpoint has no per-pixel counts).
+ * The adaptive fingerprint hashes the plain one's fields plus min_spp, max_spp, the effective batch, rel_tol and
+ * abs_tol under a layout tag of its own: plain and adaptive checkpoints never cross.
+ */
+typedef struct PrtAdaptiveParams {
+    int32_t min_spp;  /* no pixel stops before this: a multiple of batch, >= 2 * batch */
+    int32_t max_spp;  /* no pixel goes beyond this: a multiple of batch, >= min_spp */
+    int32_t batch;    /* samples per batch (= per work item); 0 = PRT_ADAPTIVE_DEFAULT_BATCH */
+    int32_t reserved; /* must be 0 */
+    double rel_tol;   /* >= 0, finite */
+    double abs_tol;   /* >= 0, finite */
+} PrtAdaptiveParams;
+#define PRT_ADAPTIVE_DEFAULT_BATCH 8 /* measured: tools/adaptive_timing.py, DESIGN.md §7 */
+
+/* An adaptive accumulator: zeroed state and n = 0.  Params as for prt_accum_create; PRT_E_INVALID for a bad
+ * PrtAdaptiveParams field. */
+int prt_accum_create_adaptive(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* params,
+                              const PrtAdaptiveParams* adaptive, PrtAccum** out);
+/* One round: (1) on the device, apply the rule above to every owned pixel and compact the active ones, in tile order,
+ * into a list; (2) read the list's length back (the one synchronisation of a round); (3) if it is not 0, render samples
+ * [n, n + min(n_samples, max_spp - n)) of the listed pixels in work items of `batch` samples; (4) add their sums,
+ * moments and counts.  *n_active = pixels rendered (0: the frame is done, nothing was launched).  Steps (3) and (4)
+ * are asynchronous on hip_stream.  n_samples must be a positive multiple of batch.  prt_get_counters afterwards reports
+ * the round's last launch, with samples = listed pixels x that launch's samples. */
+int prt_accum_render_adaptive(PrtAccum* acc, int32_t n_samples, uint64_t* n_active, void* hip_stream);
+/* Synchronous: the W*H per-pixel sample counts (row-major, j*W+i).  Works on plain accumulators too (every owned
+ * pixel has n samples there, the others 0). */
+int prt_accum_pixel_samples(PrtAccum* acc, uint32_t* counts);
+/* Synchronous checkpoint of an adaptive accumulator: W*H*3 sums, W*H moments, W*H counts, n and the fingerprint. */
+int prt_accum_export_adaptive(const PrtAccum* acc, double* sums, double* moments, uint32_t* counts, uint64_t* samples,
+                              uint64_t* fingerprint);
+/* Resume from prt_accum_export_adaptive.  PRT_E_INVALID for another fingerprint, a count above `samples` or not a
+ * multiple of batch, a nonzero count on a pixel this rank does not own, or a negative or non-finite moment;
+ * PRT_E_LIMIT above INT32_MAX samples. */
+int prt_accum_import_adaptive(PrtAccum* acc, const double* sums, const double* moments, const uint32_t* counts,
+                              uint64_t samples, uint64_t fingerprint);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,20 @@ class PrtRenderParams(C.Structure):
     ]
 
 
+class PrtAdaptiveParams(C.Structure):
+    _fields_ = [
+        ("min_spp", C.c_int32),
+        ("max_spp", C.c_int32),
+        ("batch", C.c_int32),
+        ("reserved", C.c_int32),
+        ("rel_tol", C.c_double),
+        ("abs_tol", C.c_double),
+    ]
+
+
+ADAPTIVE_DEFAULT_BATCH = 8  # prt.h PRT_ADAPTIVE_DEFAULT_BATCH
+
+
 class PrtRay(C.Structure):
     _fields_ = [("o", D3), ("tmin", C.c_double), ("d", D3), ("tmax", C.c_double)]
 
@@ -221,6 +235,11 @@ EXPORTS = [
     "prt_accum_read",
     "prt_accum_export",
     "prt_accum_import",
+    "prt_accum_create_adaptive",
+    "prt_accum_render_adaptive",
+    "prt_accum_pixel_samples",
+    "prt_accum_export_adaptive",
+    "prt_accum_import_adaptive",
 ]
 
 

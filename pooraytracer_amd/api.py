@@ -79,6 +79,11 @@ def load():
     L.prt_accum_read.argtypes = [vp, vp, vp]
     L.prt_accum_export.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.prt_accum_import.argtypes = [vp, vp, u64, u64]
+    L.prt_accum_create_adaptive.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
+    L.prt_accum_render_adaptive.argtypes = [vp, C.c_int32, C.POINTER(u64), vp]
+    L.prt_accum_pixel_samples.argtypes = [vp, vp]
+    L.prt_accum_export_adaptive.argtypes = [vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.prt_accum_import_adaptive.argtypes = [vp, vp, vp, vp, u64, u64]
     if L.prt_abi_version() != _abi.PRT_ABI_VERSION and os.environ.get("PRT_ABI_ANY") != "1":  # (PRT_ABI_ANY: A/B tools timing an older build)
         raise PrtError(-101, "ABI version mismatch between _abi.py and libprt_hip.so")
     try:
@@ -350,6 +355,84 @@ class Accumulator:
             raise ValueError(f"Accumulator.restore: samples must be an integer >= 0, got {samples!r}")
         sums = np.ascontiguousarray(sums, dtype=np.float64)
         _check(self._L.prt_accum_import(self._h, sums.ctypes.data, int(samples), int(fingerprint)), self._L)
+        return self
+
+
+class AdaptiveAccumulator(Accumulator):
+    """Adaptive sampling (prt_accum_create_adaptive, include/prt.h): each pixel gets samples, in rounds, until its own
+    batch-means noise estimate se <= max(rel_tol * |mean|, abs_tol), never fewer than min_spp and never more than max_spp.
+    A pixel that stopped after n_p samples holds Scene.render(spp=n_p)'s value there.  batch = samples per batch (0: the
+    library's default, _abi.ADAPTIVE_DEFAULT_BATCH); min_spp, max_spp and every round size are multiples of it.  Other
+    keywords as for Accumulator.  add(), state() and restore() are refused: use step(), export() and load()."""
+
+    def __init__(self, scene, camera=None, *, rel_tol, abs_tol, min_spp, max_spp, batch=0, **kw):
+        if "spp" in kw:
+            raise TypeError("AdaptiveAccumulator: spp is not a parameter (max_spp bounds every pixel)")
+        self.scene = scene
+        self._L = scene._L
+        self.camera = camera or scene.data.camera
+        self._shape = (self.camera.height, self.camera.width, 3)
+        c, p = _abi.make_camera(self.camera), _abi.make_params(**kw)
+        a = _abi.PrtAdaptiveParams(int(min_spp), int(max_spp), int(batch), 0, float(rel_tol), float(abs_tol))
+        self.batch = int(batch) or _abi.ADAPTIVE_DEFAULT_BATCH
+        self.min_spp, self.max_spp, self.rel_tol, self.abs_tol = int(min_spp), int(max_spp), float(rel_tol), float(abs_tol)
+        h = C.c_void_p()
+        _check(self._L.prt_accum_create_adaptive(scene._h, C.byref(c), C.byref(p), C.byref(a), C.byref(h)), self._L)
+        self._h = h
+
+    def step(self, n, stream=None):
+        """One round of n samples (a multiple of batch) for every active pixel; returns the number of pixels rendered
+        (0: every pixel has stopped).  Reads one word back from the device; the rendering itself is asynchronous."""
+        if int(n) != n or n < 1:
+            raise ValueError(f"AdaptiveAccumulator.step: n must be an integer >= 1, got {n!r}")
+        k = C.c_uint64(0)
+        _check(self._L.prt_accum_render_adaptive(self._h, int(n), C.byref(k), stream), self._L)
+        return k.value
+
+    def run(self, n_per_round, on_round=None):
+        """Rounds of n_per_round samples until no pixel is active; returns the number of rounds that rendered.
+        on_round(n_active, n_per_round) is called after every round that rendered."""
+        rounds = 0
+        while True:
+            k = self.step(n_per_round)
+            if k == 0:
+                return rounds
+            rounds += 1
+            if on_round is not None:
+                on_round(k, n_per_round)
+
+    def pixel_samples(self):
+        """Samples per pixel, (H, W) uint32."""
+        out = np.zeros(self._shape[:2], dtype=np.uint32)
+        _check(self._L.prt_accum_pixel_samples(self._h, out.ctypes.data), self._L)
+        return out
+
+    def export(self):
+        """Checkpoint: dict of sums (H, W, 3) float64, moments (H, W) float64, counts (H, W) uint32, samples, fingerprint."""
+        sums = np.zeros(self._shape, dtype=np.float64)
+        mom = np.zeros(self._shape[:2], dtype=np.float64)
+        cnt = np.zeros(self._shape[:2], dtype=np.uint32)
+        n, fp = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.prt_accum_export_adaptive(self._h, sums.ctypes.data, mom.ctypes.data, cnt.ctypes.data, C.byref(n),
+                                                 C.byref(fp)), self._L)
+        return {"sums": sums, "moments": mom, "counts": cnt, "samples": n.value, "fingerprint": fp.value}
+
+    def load(self, state):
+        """Resume from export() of an adaptive accumulator with the same camera, keywords, adaptive parameters and scene counts."""
+        sums = np.asarray(state["sums"])
+        mom, cnt = np.asarray(state["moments"]), np.asarray(state["counts"])
+        if sums.shape != self._shape or mom.shape != self._shape[:2] or cnt.shape != self._shape[:2]:
+            raise ValueError(f"AdaptiveAccumulator.load: shapes {sums.shape} {mom.shape} {cnt.shape}, want {self._shape} and {self._shape[:2]}")
+        if cnt.dtype != np.uint32 and (cnt.min(initial=0) < 0 or cnt.max(initial=0) > 0xFFFFFFFF):
+            raise ValueError("AdaptiveAccumulator.load: counts out of uint32 range")
+        samples = state["samples"]
+        if int(samples) != samples or samples < 0:
+            raise ValueError(f"AdaptiveAccumulator.load: samples must be an integer >= 0, got {samples!r}")
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        mom = np.ascontiguousarray(mom, dtype=np.float64)
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+        _check(self._L.prt_accum_import_adaptive(self._h, sums.ctypes.data, mom.ctypes.data, cnt.ctypes.data, int(samples),
+                                                 int(state["fingerprint"])), self._L)
         return self
 
 

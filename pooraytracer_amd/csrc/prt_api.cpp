@@ -36,7 +36,15 @@ void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, do
 void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d64, float* d32,
                      hipStream_t st);
 void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st);
-void launch_resolve(const double* d_sum, size_t n, uint64_t samples, double* d64, float* d32, uint8_t* d8, hipStream_t st);
+void launch_resolve(const double* d_sum, size_t n, uint64_t samples, const uint32_t* d_counts, double* d64, float* d32,
+                    uint8_t* d8, hipStream_t st);
+// adaptive sampling: the active pixels of a round (d_seg holds adapt_segments(owned items) words), and one launch's sums
+uint32_t adapt_segments(uint64_t owned_items);
+void launch_adapt_select(const DCamera& C, const DRenderParams& P, const DAdaptRule& R, const double* d_sum,
+                         const double* d_moment, const uint32_t* d_count, uint32_t* d_seg, int32_t* d_list, uint32_t* d_total,
+                         hipStream_t st);
+void launch_accumulate_list(const DRenderParams& P, const double* d_partial, const int32_t* d_list, uint32_t batch,
+                            uint32_t samples, double* d_sum, double* d_moment, uint32_t* d_count, hipStream_t st);
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
                           hipStream_t st);
 void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
@@ -1036,10 +1044,17 @@ int prt_texture_value(PrtScene* s, int32_t texture, size_t n, const double* uv, 
 // (Camera.cpp:83) and written by K5 into cleared framebuffers.  prt_accum_render: samples [first, first + spp), unscaled
 // (the launch runs with spp = 1, so an item's partial sum is the raw sum of its samples' RayColor), added by k_accumulate
 // into an accumulator's running sums; the chunks of the launch are sized for `spp` samples either way.
+// prt_accum_render_adaptive sets d_list: K3 renders the list_n listed pixels (j*W+i, device memory) in chunks of
+// exactly `batch` samples (spp / batch <= PRT_MAX_CHUNKS of them), and k_accumulate_list adds sums, moments and counts.
 struct RenderPass {
     int spp;
     int32_t first = 0;
     double* d_sum = nullptr;
+    const int32_t* d_list = nullptr;
+    uint32_t list_n = 0;
+    int batch = 0;
+    double* d_moment = nullptr;
+    uint32_t* d_count = nullptr;
 };
 
 static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const PrtRenderParams* p, const RenderPass& pass,
@@ -1086,7 +1101,7 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     if (const char* e = dev_env("PRT_TUNE_KEEP")) P.keep = std::atoi(e);
     if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::atoi(e);
     if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::atoi(e);
-    if (const char* e = dev_env("PRT_TUNE_SCRAMBLE")) P.scramble = std::atoi(e) ? 1 : 0; // experiment: incoherent pixel order (PRT_ITEMS_FROM_LIST stays internal to prt_render_samples)
+    if (const char* e = dev_env("PRT_TUNE_SCRAMBLE")) P.scramble = std::atoi(e) ? 1 : 0; // experiment: incoherent pixel order (PRT_ITEMS_FROM_LIST is set by adaptive rounds below and by prt_render_samples)
     for (int c = 0; c < 3; ++c) P.background[c] = p->background[c];
     P.seed_key = prt::seed_key(p->seed); // the seed is hashed on its own, once per launch (prt_device.h, Rng)
     int tile = p->tile_size > 0 ? p->tile_size : 32;
@@ -1104,6 +1119,10 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     P.stack_depth = s->stack_depth;
     P.owned_tiles = P.n_tiles > P.rank ? (P.n_tiles - P.rank + P.nranks - 1) / P.nranks : 0;
     P.items_per_chunk = (uint64_t)P.owned_tiles * tile * tile;
+    if (pass.d_list) { // an adaptive round: the listed pixels (all owned by this rank) instead of the owned tiles
+        P.scramble = PRT_ITEMS_FROM_LIST;
+        P.items_per_chunk = pass.list_n;
+    }
     const bool count = count_work != 0;
     const int bpc = f32 ? s->blocks_per_cu32[count ? 1 : 0] : s->blocks_per_cu[count ? 1 : 0];
     const uint64_t lanes = (uint64_t)s->n_cu * bpc * PRT_BLOCK;
@@ -1123,7 +1142,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     const int spp = pass.spp;
     int want = p->sample_chunks;
     if (const char* e = dev_env("PRT_TUNE_CHUNKS")) want = std::atoi(e);
-    if (want > 0) {
+    if (pass.d_list) {
+        for (int c = 0; c < spp / pass.batch; ++c) sizes.push_back(pass.batch);
+    } else if (want > 0) {
         want = std::min(want, std::min(spp, PRT_MAX_CHUNKS));
         for (int c = 0; c < want; ++c) sizes.push_back((int)(((int64_t)(c + 1) * spp) / want - ((int64_t)c * spp) / want));
     } else if (P.items_per_chunk == 0) {
@@ -1186,7 +1207,7 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     if (P.n_items) {
         const uint64_t want = (P.n_items + PRT_BLOCK - 1) / PRT_BLOCK;
         const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s->n_cu * bpc));
-        if ((rc = set_slot_pointers(s, q, st, grid, nullptr, nullptr))) return rc;
+        if ((rc = set_slot_pointers(s, q, st, grid, pass.d_list, nullptr))) return rc;
         if (const char* e = dev_env("PRT_TUNE_DUMP_RAYS")) { // "<max rays>,<file>" (counting launches only)
             const std::string v(e);
             const size_t comma = v.find(',');
@@ -1238,7 +1259,13 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
         }
         std::fprintf(stderr, "[prt] dumped %zu of %llu rays to %s\n", nd, h.ray_dump_n, dump_path.c_str());
     }
-    if (P.n_items) {
+    if (pass.d_list) {
+        // maxDepth < 0: no item ran, and every sample is 0; the counts still grow
+        if (!P.n_items) PRT_HIP(hipMemsetAsync(q.d_partial, 0, need * sizeof(double), st));
+        prt::launch_accumulate_list(P, q.d_partial, pass.d_list, (uint32_t)pass.batch, (uint32_t)spp, pass.d_sum, pass.d_moment,
+                                    pass.d_count, st);
+        PRT_HIP(hipGetLastError());
+    } else if (P.n_items) {
         if (pass.d_sum) prt::launch_accumulate(C, P, q.d_partial, pass.d_sum, st);
         else prt::launch_finalize(C, P, q.d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
         PRT_HIP(hipGetLastError());
@@ -1247,7 +1274,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     q.timed = true;
     q.counted = count;
     q.samples = 0;
-    if (P.n_items) { // pixels of this rank's tiles that lie inside the image, times spp
+    if (pass.d_list) {
+        q.samples = P.n_items ? (uint64_t)pass.list_n * (uint64_t)spp : 0;
+    } else if (P.n_items) { // pixels of this rank's tiles that lie inside the image, times spp
         uint64_t px = 0;
         for (int k = P.rank; k < P.n_tiles; k += P.nranks) {
             const int ty = k / P.tiles_x, kx = k - ty * P.tiles_x, tx = (kx + 3 * ty) % P.tiles_x; // prt_device.h, owned_to_pixel
@@ -1569,6 +1598,17 @@ struct PrtAccum {
     size_t n = 0; // W * H * 3
     double* d_sum = nullptr;
     hipEvent_t done = nullptr;
+    // adaptive accumulators (prt_accum_create_adaptive): `samples` is the global count n, and per pixel a second moment and
+    // a sample count; a round's active pixels are listed in d_list (d_seg: the select's per-segment counts, d_active: the
+    // list's length, read back through the pinned h_active)
+    bool adaptive = false;
+    PrtAdaptiveParams ad{}; // with the effective batch
+    double* d_moment = nullptr;
+    uint32_t* d_count = nullptr;
+    int32_t* d_list = nullptr;
+    uint32_t* d_seg = nullptr;
+    uint32_t* d_active = nullptr;
+    uint32_t* h_active = nullptr;
 };
 
 namespace {
@@ -1581,10 +1621,11 @@ struct Fnv {
         for (unsigned char c : b) h = (h ^ c) * 1099511628211ULL;
     }
 };
-// Everything that changes a sample's value or a pixel's owner, plus the scene's counts (not its contents).
-uint64_t accum_fingerprint(const PrtScene* s, const PrtCamera& c, const PrtRenderParams& p) {
+// Everything that changes a sample's value or a pixel's owner, plus the scene's counts (not its contents); for an adaptive
+// accumulator also everything that changes when a pixel stops, under a layout tag of its own.
+uint64_t accum_fingerprint(const PrtScene* s, const PrtCamera& c, const PrtRenderParams& p, const PrtAdaptiveParams* ad = nullptr) {
     Fnv f;
-    f.add((uint32_t)0x70727461u); // layout tag of this hash
+    f.add((uint32_t)(ad ? 0x70727462u : 0x70727461u)); // layout tag of this hash
     f.add(c.width); f.add(c.height); f.add(c.fovy);
     for (int k = 0; k < 3; ++k) { f.add(c.eye[k]); f.add(c.look_at[k]); f.add(c.up[k]); }
     f.add(p.max_depth); f.add(p.russian_roulette); f.add((int32_t)(p.sample_lights ? 1 : 0)); f.add(p.precision);
@@ -1594,7 +1635,44 @@ uint64_t accum_fingerprint(const PrtScene* s, const PrtCamera& c, const PrtRende
     tile = std::max(8, (tile + 7) / 8 * 8);
     f.add((int32_t)tile); f.add(p.rank); f.add(p.nranks); f.add((int32_t)(p.pixel_jitter ? 1 : 0));
     f.add((uint64_t)s->tris.size()); f.add((uint64_t)s->mesh_mat.size()); f.add((uint64_t)s->mats.size());
+    if (ad) {
+        f.add(ad->min_spp); f.add(ad->max_spp); f.add(ad->batch); f.add(ad->rel_tol); f.add(ad->abs_tol);
+    }
     return f.h;
+}
+// The tile layout render_impl gives the accumulator's launches (owned item oi -> pixel as in K3), for the adaptive select.
+void accum_layout(const PrtAccum* a, DCamera& C, DRenderParams& P) {
+    prt::setup_camera(a->cam, C);
+    std::memset(&P, 0, sizeof(P));
+    int tile = a->params.tile_size > 0 ? a->params.tile_size : 32;
+    tile = std::max(8, (tile + 7) / 8 * 8);
+    P.tile = tile;
+    P.tiles_x = (C.width + tile - 1) / tile;
+    P.tiles_y = (C.height + tile - 1) / tile;
+    P.n_tiles = P.tiles_x * P.tiles_y;
+    P.rank = a->params.rank;
+    P.nranks = a->params.nranks;
+    P.owned_tiles = P.n_tiles > P.rank ? (P.n_tiles - P.rank + P.nranks - 1) / P.nranks : 0;
+    P.items_per_chunk = (uint64_t)P.owned_tiles * tile * tile;
+}
+// Pixel j*W+i belongs to the accumulator's rank (tile_pixel in prt_device.h, inverted).
+std::vector<uint8_t> accum_owned(const PrtAccum* a) {
+    DCamera C;
+    DRenderParams P;
+    accum_layout(a, C, P);
+    std::vector<uint8_t> own((size_t)C.width * C.height, 0);
+    for (int py = 0; py < C.height; ++py)
+        for (int px = 0; px < C.width; ++px) {
+            const int tx = px / P.tile, ty = py / P.tile;
+            const int kx = ((tx - 3 * ty) % P.tiles_x + P.tiles_x) % P.tiles_x;
+            own[(size_t)py * C.width + px] = (ty * P.tiles_x + kx) % P.nranks == P.rank ? 1 : 0;
+        }
+    return own;
+}
+int not_adaptive(const PrtAccum* a, const char* who, const char* instead) {
+    if (a && a->adaptive)
+        return fail(PRT_E_INVALID, std::string(who) + ": an adaptive accumulator has per-pixel sample counts (use " + instead + ")");
+    return PRT_OK;
 }
 // The accumulator's scene is uploaded, to the device the sums live on.
 int accum_ready(PrtAccum* a, const char* who) {
@@ -1608,38 +1686,93 @@ int accum_ready(PrtAccum* a, const char* who) {
 
 extern "C" {
 
-int prt_accum_create(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, PrtAccum** out) {
-    if (!out) return fail(PRT_E_INVALID, "prt_accum_create: null argument");
+} // extern "C"
+
+namespace {
+// Zeroed state of an accumulator (ad: adaptive, its batch already resolved and checked).
+hipError_t accum_zero(PrtAccum* a) {
+    const size_t npx = a->n / 3;
+    hipError_t e = hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr);
+    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_moment, 0, npx * sizeof(double), nullptr);
+    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_count, 0, npx * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipEventRecord(a->done, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(a->done);
+    return e;
+}
+
+int accum_create(const char* who, PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, const PrtAdaptiveParams* ad, PrtAccum** out) {
+    const std::string w(who);
+    if (!out) return fail(PRT_E_INVALID, w + ": null argument");
     *out = nullptr;
-    int rc = require_uploaded(s, "prt_accum_create");
+    int rc = require_uploaded(s, who);
     if (rc) return rc;
-    if (!cam || !p) return fail(PRT_E_INVALID, "prt_accum_create: null argument");
-    if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, "prt_accum_create: bad image size");
-    if (p->reserved != 0) return fail(PRT_E_INVALID, "prt_accum_create: reserved must be 0");
-    if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, "prt_accum_create: unsupported precision");
-    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, "prt_accum_create: bad rank/nranks");
+    if (!cam || !p) return fail(PRT_E_INVALID, w + ": null argument");
+    if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, w + ": bad image size");
+    if (p->reserved != 0) return fail(PRT_E_INVALID, w + ": reserved must be 0");
+    if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
+    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, w + ": bad rank/nranks");
+    PrtAdaptiveParams A{};
+    if (ad) {
+        A = *ad;
+        if (A.reserved != 0) return fail(PRT_E_INVALID, w + ": adaptive reserved must be 0");
+        if (A.batch == 0) A.batch = PRT_ADAPTIVE_DEFAULT_BATCH;
+        if (A.batch < 1) return fail(PRT_E_INVALID, w + ": batch must be >= 1 (or 0 for the default)");
+        if (A.min_spp < 2 * (int64_t)A.batch || A.min_spp % A.batch)
+            return fail(PRT_E_INVALID, w + ": min_spp must be a multiple of batch and >= 2 * batch");
+        if (A.max_spp < A.min_spp || A.max_spp % A.batch) return fail(PRT_E_INVALID, w + ": max_spp must be a multiple of batch and >= min_spp");
+        if (!std::isfinite(A.rel_tol) || A.rel_tol < 0 || !std::isfinite(A.abs_tol) || A.abs_tol < 0)
+            return fail(PRT_E_INVALID, w + ": rel_tol and abs_tol must be finite and >= 0");
+    }
     if (p->precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
     PrtAccum* a = new (std::nothrow) PrtAccum();
-    if (!a) return fail(PRT_E_OOM, "prt_accum_create: out of host memory");
+    if (!a) return fail(PRT_E_OOM, w + ": out of host memory");
     a->scene = s;
     a->cam = *cam;
     a->params = *p;
     a->params.spp = 0; // the pass size is prt_accum_render's argument
     a->device = s->device;
     a->generation = s->generation;
-    a->fingerprint = accum_fingerprint(s, *cam, *p);
+    a->adaptive = ad != nullptr;
+    a->ad = A;
+    a->fingerprint = accum_fingerprint(s, *cam, *p, ad ? &A : nullptr);
     a->n = (size_t)cam->width * cam->height * 3;
+    const size_t npx = a->n / 3;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->d_sum), a->n * sizeof(double));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr);
-    if (e == hipSuccess) e = hipEventRecord(a->done, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(a->done);
+    if (a->adaptive) {
+        DCamera C;
+        DRenderParams P;
+        accum_layout(a, C, P);
+        const size_t items = std::max<size_t>(1, P.items_per_chunk), segs = std::max<uint32_t>(1, prt::adapt_segments(P.items_per_chunk));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_moment), npx * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_count), npx * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_list), items * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_seg), segs * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_active), sizeof(uint32_t));
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&a->h_active), sizeof(uint32_t), hipHostMallocDefault);
+    }
+    if (e == hipSuccess) e = accum_zero(a);
     if (e != hipSuccess) {
         prt_accum_destroy(a);
-        return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_accum_create: ") + hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, w + ": " + hipGetErrorString(e));
     }
     *out = a;
     return PRT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int prt_accum_create(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, PrtAccum** out) {
+    return accum_create("prt_accum_create", s, cam, p, nullptr, out);
+}
+
+int prt_accum_create_adaptive(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, const PrtAdaptiveParams* ad, PrtAccum** out) {
+    if (!ad) {
+        if (out) *out = nullptr;
+        return fail(PRT_E_INVALID, "prt_accum_create_adaptive: null argument");
+    }
+    return accum_create("prt_accum_create_adaptive", s, cam, p, ad, out);
 }
 
 void prt_accum_destroy(PrtAccum* a) {
@@ -1650,12 +1783,18 @@ void prt_accum_destroy(PrtAccum* a) {
         (void)hipEventDestroy(a->done);
     }
     if (a->d_sum) (void)hipFree(a->d_sum);
+    if (a->d_moment) (void)hipFree(a->d_moment);
+    if (a->d_count) (void)hipFree(a->d_count);
+    if (a->d_list) (void)hipFree(a->d_list);
+    if (a->d_seg) (void)hipFree(a->d_seg);
+    if (a->d_active) (void)hipFree(a->d_active);
+    if (a->h_active) (void)hipHostFree(a->h_active);
     delete a;
 }
 
 int prt_accum_render(PrtAccum* a, int32_t n_samples, void* stream) {
     int rc = accum_ready(a, "prt_accum_render");
-    if (rc) return rc;
+    if (rc || (rc = not_adaptive(a, "prt_accum_render", "prt_accum_render_adaptive"))) return rc;
     if (n_samples < 1) return fail(PRT_E_INVALID, "prt_accum_render: n_samples must be >= 1");
     if (a->samples + (uint64_t)n_samples > (uint64_t)INT32_MAX)
         return fail(PRT_E_LIMIT, "prt_accum_render: sample indices would pass INT32_MAX");
@@ -1683,9 +1822,7 @@ int prt_accum_reset(PrtAccum* a) {
     int rc = accum_ready(a, "prt_accum_reset");
     if (rc) return rc;
     PRT_HIP(hipEventSynchronize(a->done));
-    PRT_HIP(hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr));
-    PRT_HIP(hipEventRecord(a->done, nullptr));
-    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(accum_zero(a));
     a->samples = 0;
     a->generation = a->scene->generation;
     return PRT_OK;
@@ -1697,8 +1834,8 @@ int prt_accum_resolve(PrtAccum* a, void* d_rgb_f64, void* d_rgb_f32, void* d_rgb
     if (!d_rgb_f64 && !d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, "prt_accum_resolve: no output buffer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
-    prt::launch_resolve(a->d_sum, a->n, a->samples, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32),
-                        static_cast<uint8_t*>(d_rgb_u8), st);
+    prt::launch_resolve(a->d_sum, a->n, a->samples, a->adaptive ? a->d_count : nullptr, static_cast<double*>(d_rgb_f64),
+                        static_cast<float*>(d_rgb_f32), static_cast<uint8_t*>(d_rgb_u8), st);
     PRT_HIP(hipGetLastError());
     PRT_HIP(hipEventRecord(a->done, st));
     return PRT_OK;
@@ -1728,6 +1865,7 @@ int prt_accum_read(PrtAccum* a, double* rgb_f64, float* rgb_f32) {
 
 int prt_accum_export(const PrtAccum* a, double* sums, uint64_t* samples, uint64_t* fingerprint) {
     if (!a || !sums || !samples || !fingerprint) return fail(PRT_E_INVALID, "prt_accum_export: null argument");
+    if (int rc = not_adaptive(a, "prt_accum_export", "prt_accum_export_adaptive")) return rc;
     PRT_HIP(hipSetDevice(a->device));
     PRT_HIP(hipEventSynchronize(a->done));
     PRT_HIP(hipMemcpy(sums, a->d_sum, a->n * sizeof(double), hipMemcpyDeviceToHost));
@@ -1738,13 +1876,123 @@ int prt_accum_export(const PrtAccum* a, double* sums, uint64_t* samples, uint64_
 
 int prt_accum_import(PrtAccum* a, const double* sums, uint64_t samples, uint64_t fingerprint) {
     int rc = accum_ready(a, "prt_accum_import");
-    if (rc) return rc;
+    if (rc || (rc = not_adaptive(a, "prt_accum_import", "prt_accum_import_adaptive"))) return rc;
     if (!sums) return fail(PRT_E_INVALID, "prt_accum_import: null argument");
     if (fingerprint != a->fingerprint)
         return fail(PRT_E_INVALID, "prt_accum_import: fingerprint mismatch (other camera, render parameters or scene counts)");
     if (samples > (uint64_t)INT32_MAX) return fail(PRT_E_LIMIT, "prt_accum_import: more than INT32_MAX samples");
     PRT_HIP(hipEventSynchronize(a->done));
     PRT_HIP(hipMemcpy(a->d_sum, sums, a->n * sizeof(double), hipMemcpyHostToDevice));
+    a->samples = samples;
+    a->generation = a->scene->generation;
+    return PRT_OK;
+}
+
+int prt_accum_render_adaptive(PrtAccum* a, int32_t n_samples, uint64_t* n_active, void* stream) {
+    const char* who = "prt_accum_render_adaptive";
+    int rc = accum_ready(a, who);
+    if (rc) return rc;
+    if (!n_active) return fail(PRT_E_INVALID, "prt_accum_render_adaptive: null argument");
+    *n_active = 0;
+    if (!a->adaptive) return fail(PRT_E_INVALID, "prt_accum_render_adaptive: not an adaptive accumulator (prt_accum_create_adaptive)");
+    const PrtAdaptiveParams& A = a->ad;
+    if (n_samples < 1 || n_samples % A.batch) return fail(PRT_E_INVALID, "prt_accum_render_adaptive: n_samples must be a positive multiple of batch");
+    if (a->generation != a->scene->generation)
+        return fail(PRT_E_INVALID, "prt_accum_render_adaptive: the scene's vertices were updated since these sums were rendered (prt_accum_reset first)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    // (1) + (2): the active pixels, listed on the device; their number is the one value a round reads back
+    DCamera C;
+    DRenderParams P;
+    accum_layout(a, C, P);
+    DAdaptRule R;
+    R.n = (uint32_t)a->samples;
+    R.min_spp = (uint32_t)A.min_spp;
+    R.max_spp = (uint32_t)A.max_spp;
+    R.batch = (uint32_t)A.batch;
+    R.rel_tol = A.rel_tol;
+    R.abs_tol = A.abs_tol;
+    prt::launch_adapt_select(C, P, R, a->d_sum, a->d_moment, a->d_count, a->d_seg, a->d_list, a->d_active, st);
+    PRT_HIP(hipGetLastError());
+    PRT_HIP(hipMemcpyAsync(a->h_active, a->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PRT_HIP(hipStreamSynchronize(st));
+    const uint32_t listed = *a->h_active;
+    if (listed > P.items_per_chunk) return fail(PRT_E_HIP, "prt_accum_render_adaptive: the select listed more pixels than are owned");
+    if (listed == 0) {
+        PRT_HIP(hipEventRecord(a->done, st));
+        return PRT_OK;
+    }
+    // (3) + (4): samples [n, n + k) of the listed pixels, at most PRT_MAX_CHUNKS batches per launch
+    const int64_t k = std::min<int64_t>(n_samples, (int64_t)A.max_spp - (int64_t)a->samples);
+    const int64_t per_launch = (int64_t)PRT_MAX_CHUNKS * A.batch;
+    for (int64_t s0 = 0; s0 < k; s0 += per_launch) {
+        RenderPass pass;
+        pass.spp = (int)std::min<int64_t>(per_launch, k - s0);
+        pass.first = (int32_t)(a->samples + s0);
+        pass.d_sum = a->d_sum;
+        pass.d_list = a->d_list;
+        pass.list_n = listed;
+        pass.batch = A.batch;
+        pass.d_moment = a->d_moment;
+        pass.d_count = a->d_count;
+        if ((rc = render_impl(a->scene, who, &a->cam, &a->params, pass, nullptr, nullptr, 0, st))) return rc;
+    }
+    PRT_HIP(hipEventRecord(a->done, st));
+    a->samples += (uint64_t)k;
+    *n_active = listed;
+    return PRT_OK;
+}
+
+int prt_accum_pixel_samples(PrtAccum* a, uint32_t* counts) {
+    int rc = accum_ready(a, "prt_accum_pixel_samples");
+    if (rc) return rc;
+    if (!counts) return fail(PRT_E_INVALID, "prt_accum_pixel_samples: null argument");
+    PRT_HIP(hipEventSynchronize(a->done));
+    if (a->adaptive) {
+        PRT_HIP(hipMemcpy(counts, a->d_count, a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } else { // every owned pixel has every sample
+        const std::vector<uint8_t> own = accum_owned(a);
+        for (size_t i = 0; i < own.size(); ++i) counts[i] = own[i] ? (uint32_t)a->samples : 0u;
+    }
+    return PRT_OK;
+}
+
+int prt_accum_export_adaptive(const PrtAccum* a, double* sums, double* moments, uint32_t* counts, uint64_t* samples,
+                              uint64_t* fingerprint) {
+    if (!a || !sums || !moments || !counts || !samples || !fingerprint) return fail(PRT_E_INVALID, "prt_accum_export_adaptive: null argument");
+    if (!a->adaptive) return fail(PRT_E_INVALID, "prt_accum_export_adaptive: not an adaptive accumulator (prt_accum_export)");
+    PRT_HIP(hipSetDevice(a->device));
+    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipMemcpy(sums, a->d_sum, a->n * sizeof(double), hipMemcpyDeviceToHost));
+    PRT_HIP(hipMemcpy(moments, a->d_moment, a->n / 3 * sizeof(double), hipMemcpyDeviceToHost));
+    PRT_HIP(hipMemcpy(counts, a->d_count, a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *samples = a->samples;
+    *fingerprint = a->fingerprint;
+    return PRT_OK;
+}
+
+int prt_accum_import_adaptive(PrtAccum* a, const double* sums, const double* moments, const uint32_t* counts, uint64_t samples,
+                              uint64_t fingerprint) {
+    int rc = accum_ready(a, "prt_accum_import_adaptive");
+    if (rc) return rc;
+    if (!sums || !moments || !counts) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: null argument");
+    if (!a->adaptive) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: not an adaptive accumulator (prt_accum_import)");
+    if (fingerprint != a->fingerprint)
+        return fail(PRT_E_INVALID, "prt_accum_import_adaptive: fingerprint mismatch (other camera, render or adaptive parameters, or scene counts)");
+    if (samples > (uint64_t)INT32_MAX) return fail(PRT_E_LIMIT, "prt_accum_import_adaptive: more than INT32_MAX samples");
+    if (samples > (uint64_t)a->ad.max_spp || samples % (uint64_t)a->ad.batch)
+        return fail(PRT_E_INVALID, "prt_accum_import_adaptive: samples must be a multiple of batch and <= max_spp");
+    const std::vector<uint8_t> own = accum_owned(a);
+    for (size_t i = 0; i < own.size(); ++i) {
+        if (counts[i] > samples || counts[i] % (uint32_t)a->ad.batch)
+            return fail(PRT_E_INVALID, "prt_accum_import_adaptive: a count above samples or not a multiple of batch");
+        if (!own[i] && counts[i]) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: samples on a pixel this rank does not own");
+        if (!std::isfinite(moments[i]) || moments[i] < 0) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: a negative or non-finite moment");
+    }
+    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipMemcpy(a->d_sum, sums, a->n * sizeof(double), hipMemcpyHostToDevice));
+    PRT_HIP(hipMemcpy(a->d_moment, moments, a->n / 3 * sizeof(double), hipMemcpyHostToDevice));
+    PRT_HIP(hipMemcpy(a->d_count, counts, a->n / 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
     a->samples = samples;
     a->generation = a->scene->generation;
     return PRT_OK;

@@ -866,15 +866,137 @@ __global__ void k_tonemap(const float* __restrict__ in, size_t n, uint8_t* __res
 // Progressive rendering (prt_accum_resolve): the frame of `samples` accumulated samples, element-wise over the n
 // reals of the full frame: sum / samples in fp64, the fp32 frame its rounding, the 8-bit sRGB frame k_tonemap's bytes of
 // that fp32 value.  An accumulator without samples resolves to zeros.  Memory-bound: grid-stride over a capped grid.
-__global__ void k_resolve(const double* __restrict__ sum, size_t n, uint64_t samples, double* __restrict__ out64,
-                          float* __restrict__ out32, uint8_t* __restrict__ out8) {
+// Adaptive accumulators pass `counts` (one per pixel, n / 3 of them): each pixel is divided by its own count instead.
+__global__ void k_resolve(const double* __restrict__ sum, size_t n, uint64_t samples, const uint32_t* __restrict__ counts,
+                          double* __restrict__ out64, float* __restrict__ out32, uint8_t* __restrict__ out8) {
     const double ns = (double)samples;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double v = samples ? sum[i] / ns : 0.0;
+        const uint32_t c = counts ? counts[i / 3] : 0u;
+        const double v = counts ? (c ? sum[i] / (double)c : 0.0) : (samples ? sum[i] / ns : 0.0);
         const float f = (float)v;
         if (out64) out64[i] = v;
         if (out32) out32[i] = f;
         if (out8) out8[i] = srgb8_of(f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------- adaptive sampling
+// prt_accum_render_adaptive (include/prt.h).  Memory-bound over the owned pixels, like K5.  The rule and the moments are
+// evaluated without fused multiply-adds, so that a host-side restatement of them (tests/adaptive_model.py) computes the
+// same bits from the same sums.
+PRT_DEV double luma(double r, double g, double b) {
+#pragma clang fp contract(off)
+    return 0.2126 * r + 0.7152 * g + 0.0722 * b;
+}
+
+// The activity rule: count == n, count < max_spp and not (count >= min_spp and converged).  Batch means: C = count / batch
+// batches of equal size, var = max(0, moment - S^2 / count) / (C - 1) estimates the per-sample luminance variance, and
+// the pixel has converged when sqrt(var / count) <= max(rel_tol |mean|, abs_tol).  Every comparison is false for NaN,
+// so a NaN pixel never converges.
+PRT_DEV bool adapt_active(const DAdaptRule& R, const double* __restrict__ sum, const double* __restrict__ moment,
+                          const uint32_t* __restrict__ count, uint32_t pix) {
+#pragma clang fp contract(off)
+    const uint32_t c = count[pix];
+    if (c != R.n || c >= R.max_spp) return false;
+    if (c < R.min_spp) return true;
+    const double np = (double)c;
+    const double S = luma(sum[(size_t)pix * 3], sum[(size_t)pix * 3 + 1], sum[(size_t)pix * 3 + 2]);
+    const double d = moment[pix] - S * S / np;
+    const double var = (d < 0.0 ? 0.0 : d) / (double)(c / R.batch - 1u);
+    const double se = sqrt(var / np);
+    double thr = R.rel_tol * fabs(S / np);
+    if (thr < R.abs_tol) thr = R.abs_tol;
+    return !(se <= thr);
+}
+
+// Owned item oi of the tile order is an active pixel; its index j*W+i in `pix`.
+PRT_DEV bool adapt_item(const DCamera& C, const DRenderParams& P, const DAdaptRule& R, const double* __restrict__ sum,
+                        const double* __restrict__ moment, const uint32_t* __restrict__ count, uint64_t oi, uint32_t& pix) {
+    int px, py;
+    if (oi >= P.items_per_chunk || !owned_to_pixel(P, C, (uint32_t)oi, px, py)) return false;
+    pix = (uint32_t)(py * C.width + px);
+    return adapt_active(R, sum, moment, count, pix);
+}
+
+// The active pixels, compacted in owned-item order by three kernels (no atomics: the list is the same on every run).
+// Segment g = owned items [g * PRT_BLOCK, (g + 1) * PRT_BLOCK), one per thread of a block; blocks stride over segments.
+// (1) seg[g] = active items of segment g.
+__global__ void k_adapt_count(DCamera C, DRenderParams P, DAdaptRule R, const double* __restrict__ sum,
+                              const double* __restrict__ moment, const uint32_t* __restrict__ count, uint32_t* __restrict__ seg,
+                              uint32_t n_seg) {
+    for (uint32_t g = blockIdx.x; g < n_seg; g += gridDim.x) {
+        uint32_t pix;
+        const bool a = adapt_item(C, P, R, sum, moment, count, (uint64_t)g * PRT_BLOCK + threadIdx.x, pix);
+        const int k = __syncthreads_count(a);
+        if (threadIdx.x == 0) seg[g] = (uint32_t)k;
+    }
+}
+// (2) One block of PRT_ADAPT_SCAN threads: seg[] becomes its exclusive prefix sum, *total the number of active pixels.
+#define PRT_ADAPT_SCAN 1024
+__global__ void __launch_bounds__(PRT_ADAPT_SCAN) k_adapt_scan(uint32_t* __restrict__ seg, uint32_t n_seg, uint32_t* __restrict__ total) {
+    __shared__ uint32_t s[PRT_ADAPT_SCAN];
+    const uint32_t t = threadIdx.x, per = (n_seg + PRT_ADAPT_SCAN - 1) / PRT_ADAPT_SCAN;
+    const uint32_t b = min(n_seg, t * per), e = min(n_seg, b + per);
+    uint32_t mine = 0;
+    for (uint32_t g = b; g < e; ++g) mine += seg[g];
+    s[t] = mine;
+    __syncthreads();
+    for (uint32_t off = 1; off < PRT_ADAPT_SCAN; off *= 2) { // inclusive scan (Hillis-Steele)
+        const uint32_t v = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = s[t] - mine;
+    for (uint32_t g = b; g < e; ++g) {
+        const uint32_t v = seg[g];
+        seg[g] = run;
+        run += v;
+    }
+    if (t == PRT_ADAPT_SCAN - 1) *total = s[t];
+}
+// (3) list[seg[g] + rank of the item among the active ones of its segment] = pixel.
+__global__ void k_adapt_write(DCamera C, DRenderParams P, DAdaptRule R, const double* __restrict__ sum,
+                              const double* __restrict__ moment, const uint32_t* __restrict__ count,
+                              const uint32_t* __restrict__ seg, uint32_t n_seg, int32_t* __restrict__ list) {
+    __shared__ uint32_t s_wave[PRT_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t g = blockIdx.x; g < n_seg; g += gridDim.x) {
+        uint32_t pix = 0;
+        const bool a = adapt_item(C, P, R, sum, moment, count, (uint64_t)g * PRT_BLOCK + threadIdx.x, pix);
+        const unsigned long long m = __ballot(a);
+        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t at = seg[g] + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL));
+        for (uint32_t w = 0; w < wave; ++w) at += s_wave[w];
+        if (a) list[at] = (int32_t)pix;
+        __syncthreads(); // s_wave is reused by the next segment
+    }
+}
+
+// One adaptive launch: for list entry i, sum[pixel] += the item sum over the chunks (chunk_sum, as k_accumulate takes it),
+// moment[pixel] += sum over the chunks, in order, of Y(chunk partial)^2 / batch, count[pixel] += the launch's samples.
+// One thread per entry, and a pixel is listed once: one writer per pixel, no atomics.
+__global__ void k_accumulate_list(DRenderParams P, const double* __restrict__ partial, const int32_t* __restrict__ list,
+                                  uint32_t batch, uint32_t samples, double* __restrict__ sum, double* __restrict__ moment,
+                                  uint32_t* __restrict__ count) {
+#pragma clang fp contract(off)
+    const double b = (double)batch;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.items_per_chunk; i += (uint64_t)gridDim.x * blockDim.x) {
+        const size_t pix = (size_t)list[i];
+        double r, g, bl;
+        chunk_sum(P, partial, i, r, g, bl);
+        double m = 0.0;
+        for (int c = 0; c < P.chunks; ++c) {
+            const double* p = partial + ((uint64_t)c * P.items_per_chunk + i) * 3;
+            const double t = luma(p[0], p[1], p[2]);
+            m += t * t / b;
+        }
+        sum[pix * 3] += r;
+        sum[pix * 3 + 1] += g;
+        sum[pix * 3 + 2] += bl;
+        moment[pix] += m;
+        count[pix] += samples;
     }
 }
 
@@ -1032,10 +1154,31 @@ void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d
     if (grid == 0) return;
     hipLaunchKernelGGL(k_accumulate, dim3(grid), dim3(256), 0, st, C, P, d_partial, d_sum);
 }
-void launch_resolve(const double* d_sum, size_t n, uint64_t samples, double* d64, float* d32, uint8_t* d8, hipStream_t st) {
+void launch_resolve(const double* d_sum, size_t n, uint64_t samples, const uint32_t* d_counts, double* d64, float* d32,
+                    uint8_t* d8, hipStream_t st) {
     if (n == 0) return;
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, d_sum, n, samples, d64, d32, d8);
+    hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(256), 0, st, d_sum, n, samples, d_counts, d64, d32, d8);
+}
+uint32_t adapt_segments(uint64_t owned_items) { return (uint32_t)((owned_items + PRT_BLOCK - 1) / PRT_BLOCK); }
+void launch_adapt_select(const DCamera& C, const DRenderParams& P, const DAdaptRule& R, const double* d_sum,
+                         const double* d_moment, const uint32_t* d_count, uint32_t* d_seg, int32_t* d_list, uint32_t* d_total,
+                         hipStream_t st) {
+    const uint32_t n_seg = adapt_segments(P.items_per_chunk);
+    if (n_seg == 0) {
+        (void)hipMemsetAsync(d_total, 0, sizeof(uint32_t), st);
+        return;
+    }
+    const unsigned grid = std::min<uint32_t>(n_seg, 2048);
+    hipLaunchKernelGGL(k_adapt_count, dim3(grid), dim3(PRT_BLOCK), 0, st, C, P, R, d_sum, d_moment, d_count, d_seg, n_seg);
+    hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(PRT_ADAPT_SCAN), 0, st, d_seg, n_seg, d_total);
+    hipLaunchKernelGGL(k_adapt_write, dim3(grid), dim3(PRT_BLOCK), 0, st, C, P, R, d_sum, d_moment, d_count, d_seg, n_seg, d_list);
+}
+void launch_accumulate_list(const DRenderParams& P, const double* d_partial, const int32_t* d_list, uint32_t batch,
+                            uint32_t samples, double* d_sum, double* d_moment, uint32_t* d_count, hipStream_t st) {
+    if (P.items_per_chunk == 0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((P.items_per_chunk + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_accumulate_list, dim3(grid), dim3(256), 0, st, P, d_partial, d_list, batch, samples, d_sum, d_moment, d_count);
 }
 
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,

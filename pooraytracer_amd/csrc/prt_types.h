@@ -205,7 +205,7 @@ typedef DRenderParamsT<prt_real> DRenderParams;
 // blockIdx % PRT_ITEM_QUEUES and moves on to the next one when its queue runs dry.
 #define PRT_ITEM_QUEUES 16
 #define PRT_QUEUE_STRIDE 32 // in 8-byte words: one counter per 256 bytes (different memory channels)
-#define PRT_ITEMS_FROM_LIST 2 // DRenderParams::scramble: pixels come from DCounters::pixel_list (prt_render_samples)
+#define PRT_ITEMS_FROM_LIST 2 // DRenderParams::scramble: pixels come from DCounters::pixel_list (prt_render_samples, adaptive rounds)
 
 // device-side counters, zeroed before each call
 struct DCounters {
@@ -222,4 +222,11 @@ struct DCounters {
     unsigned long long ray_dump_cap, ray_dump_n;
     unsigned long long pad_[PRT_QUEUE_STRIDE - 15];
     unsigned long long queue[PRT_ITEM_QUEUES * PRT_QUEUE_STRIDE]; // queue[q * PRT_QUEUE_STRIDE] = next 64-item-block-local index of queue q
+};
+
+// Adaptive sampling (prt_accum_render_adaptive, include/prt.h): the activity rule of one round.  n = the accumulator's
+// global sample count; every count is a multiple of batch.
+struct DAdaptRule {
+    uint32_t n, min_spp, max_spp, batch;
+    double rel_tol, abs_tol;
 };

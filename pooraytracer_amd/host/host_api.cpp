@@ -452,6 +452,46 @@ void Camera::RenderProgressive(Hittable& world, Hittable& lights, const std::vec
     }
 }
 
+int Camera::RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int minSpp, int maxSpp, std::vector<uint32_t>* counts,
+                           double absTol, int batch, int roundSpp) {
+    if (devices.size() > 1) throw std::invalid_argument("Camera::RenderAdaptive: one device only (`devices` lists several)");
+    const std::vector<int> devs{devices.empty() ? device : devices[0]};
+    PrtCamera c;
+    PrtRenderParams p;
+    Hittable::DeviceCache& dc = PrepareScene(world, lights, devs, c, p);
+    PrtAdaptiveParams a;
+    std::memset(&a, 0, sizeof(a));
+    a.min_spp = minSpp;
+    a.max_spp = maxSpp;
+    a.batch = batch;
+    a.rel_tol = relTol;
+    a.abs_tol = absTol;
+    PrtAccum* acc = nullptr;
+    check(prt_accum_create_adaptive(dc.scene, &c, &p, &a, &acc), "prt_accum_create_adaptive");
+    std::unique_ptr<PrtAccum, void (*)(PrtAccum*)> guard(acc, prt_accum_destroy); // destroyed before the scene, on every way out
+    int rounds = 0;
+    for (int size = minSpp;; size = roundSpp > 0 ? roundSpp : minSpp) {
+        uint64_t active = 0;
+        check(prt_accum_render_adaptive(acc, size, &active, nullptr), "prt_accum_render_adaptive");
+        if (active == 0) break;
+        ++rounds;
+        PrtCounters cnt;
+        if (prt_get_counters(dc.scene, &cnt) == PRT_OK) { // the round's last launch
+            lastRays = cnt.rays_closest + cnt.rays_shadow;
+            lastKernelMs = cnt.kernel_ms;
+        }
+    }
+    std::vector<double> rgb((size_t)imageWidth * imageHeight * 3);
+    check(prt_accum_read(acc, rgb.data(), nullptr), "prt_accum_read");
+    colorAttachment.assign((size_t)imageWidth * imageHeight, color(0., 0., 0.));
+    for (size_t i = 0; i < colorAttachment.size(); ++i) colorAttachment[i] = color(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
+    std::vector<uint32_t> n((size_t)imageWidth * imageHeight);
+    check(prt_accum_pixel_samples(acc, n.data()), "prt_accum_pixel_samples");
+    samplesPerPixel = n.empty() ? 0 : (int)*std::max_element(n.begin(), n.end());
+    if (counts) *counts = std::move(n);
+    return rounds;
+}
+
 std::string Camera::GetParametersStr() const { // Camera.cpp:332-337
     std::stringstream ss;
     ss << "spp" << samplesPerPixel << "-depth" << maxDepth;
