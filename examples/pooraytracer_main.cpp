@@ -12,6 +12,9 @@
 // no pixel gets fewer than --min-spp (default 64, capped at max_spp), and every round after the first adds min_spp
 // samples.  The frame is written as <scene>_adaptive<REL_TOL>_spp<S>-depth<D>_<seconds>s.png + .hdr, S = the largest
 // per-pixel count; --counts=FILE receives the W*H per-pixel counts (uint32, row by row) and out.f64 the frame.
+// --denoise[=ITER] (anywhere on the line): every frame written (plain, each --ladder rung, --adaptive) is also denoised
+// (Camera::Denoise: the library's default parameters, ITER a-trous levels in 1..10 when given) and written next to it as
+// <name>_denoised.png + .hdr.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -32,9 +35,23 @@ int main(int argc_all, char** argv_all) {
     std::vector<int> ladder;
     std::vector<char*> args;
     std::string adaptive, minSppArg, countsPath;
+    bool denoise = false;
+    int denoiseIter = 0; // 0: the library's default
     for (int i = 0; i < argc_all; ++i) {
         const std::string a = argv_all[i];
-        if (i > 0 && a.rfind("--adaptive=", 0) == 0) {
+        if (i > 0 && (a == "--denoise" || a.rfind("--denoise=", 0) == 0)) {
+            denoise = true;
+            if (a != "--denoise") {
+                const std::string v = a.substr(10);
+                char* end = nullptr;
+                const long n = std::strtol(v.c_str(), &end, 10);
+                if (v.empty() || *end != '\0' || n < 1 || n > 10) {
+                    std::fprintf(stderr, "error: --denoise wants a number of a-trous levels in 1..10, got '%s'\n", v.c_str());
+                    return 2;
+                }
+                denoiseIter = (int)n;
+            }
+        } else if (i > 0 && a.rfind("--adaptive=", 0) == 0) {
             adaptive = a.substr(11);
         } else if (i > 0 && a.rfind("--min-spp=", 0) == 0) {
             minSppArg = a.substr(10);
@@ -74,7 +91,7 @@ int main(int argc_all, char** argv_all) {
         }
     }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...] [--adaptive=REL_TOL [--min-spp=M] [--counts=FILE]]\n", argv_all[0]);
+        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...] [--adaptive=REL_TOL [--min-spp=M] [--counts=FILE]] [--denoise[=ITER]]\n", argv_all[0]);
         return 2;
     }
     try {
@@ -100,6 +117,17 @@ int main(int argc_all, char** argv_all) {
         lights = HittableList(make_shared<BVHNode>(lights));
 
         const std::string outDir = argc > 5 ? argv[5] : ".";
+        // --denoise: the frame in colorAttachment, denoised, next to `png`
+        auto writeDenoised = [&](const std::string& png) {
+            if (!denoise) return;
+            PrtDenoiseParams dp;
+            prt_denoise_defaults(&dp);
+            if (denoiseIter > 0) dp.iterations = denoiseIter;
+            camera.Denoise(world, &dp);
+            const std::string out = png.substr(0, png.size() - 4) + "_denoised.png";
+            camera.WriteDenoisedAttachment(out);
+            std::printf("  denoised (%d levels) -> %s\n", dp.iterations, out.c_str());
+        };
         if (!adaptive.empty()) {
             const int batch = PRT_ADAPTIVE_DEFAULT_BATCH;
             const int maxSpp = camera.samplesPerPixel / batch * batch;
@@ -117,6 +145,7 @@ int main(int argc_all, char** argv_all) {
             std::snprintf(t, sizeof(t), "%.2fs", sec);
             const std::string png = outDir + "/" + fileName + "_adaptive" + adaptive + "_" + camera.GetParametersStr() + "_" + t + ".png";
             camera.WriteColorAttachment(png);
+            writeDenoised(png);
             double total = 0;
             for (const uint32_t n : counts) total += n;
             std::printf("%s: %dx%d adaptive rel_tol %s, spp %d..%d, %d rounds, mean %.1f samples per pixel, %.3f s (includes BVH build + upload) -> %s\n",
@@ -143,6 +172,7 @@ int main(int argc_all, char** argv_all) {
                 std::printf("%s: %dx%d %s, %.3f s since the start (the first rung includes BVH build + upload), %llu rays, kernel %.2f ms -> %s\n",
                             fileName.c_str(), camera.imageWidth, camera.imageHeight, camera.GetParametersStr().c_str(), sec,
                             camera.lastRays, camera.lastKernelMs, png.c_str());
+                writeDenoised(png);
             });
             if (argc > 6) {
                 std::ofstream o(argv[6], std::ios::binary);
@@ -159,6 +189,7 @@ int main(int argc_all, char** argv_all) {
         std::snprintf(t, sizeof(t), "%.2fs", sec);
         const std::string png = outDir + "/" + fileName + "_" + camera.GetParametersStr() + "_" + t + ".png";
         camera.WriteColorAttachment(png);
+        writeDenoised(png);
         if (argc > 6) {
             std::ofstream o(argv[6], std::ios::binary);
             o.write(reinterpret_cast<const char*>(camera.colorAttachment.data()),

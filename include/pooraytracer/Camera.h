@@ -12,6 +12,7 @@
 
 struct PrtCamera;
 struct PrtRenderParams;
+struct PrtDenoiseParams;
 
 namespace Pooraytracer {
 class Camera {
@@ -49,8 +50,16 @@ public:
     // of rounds that rendered.  Single device only, like RenderProgressive.
     int RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int minSpp, int maxSpp,
                        std::vector<uint32_t>* counts = nullptr, double absTol = 0.0, int batch = 0, int roundSpp = 0);
+    // Addition (not in the reference): the edge-aware a-trous denoiser (prt.h prt_denoise) on colorAttachment, guided by the
+    // first-hit features of this camera (prt_render_features: albedo, normal, depth).  Runs after Render, RenderProgressive
+    // or RenderAdaptive on the same world; params NULL = prt_denoise_defaults.  The result goes to denoisedAttachment;
+    // colorAttachment is left as it is.  Single device only, like RenderProgressive.
+    std::vector<color> denoisedAttachment;
+    void Denoise(Hittable& world, const PrtDenoiseParams* params = nullptr);
     // 8-bit sRGB PNG (+ Radiance .hdr), Camera.cpp:279-331
     void WriteColorAttachment(const std::string& outputPath, bool bWriteHDR = true) const;
+    // The same for denoisedAttachment.
+    void WriteDenoisedAttachment(const std::string& outputPath, bool bWriteHDR = true) const;
     std::string GetParametersStr() const;
     // <camera width height fovy><eye/><lookat/><up/></camera>, Camera.cpp:339-389
     void SetViewParametersByXmlFile(const std::string& xmlFilePath);
@@ -73,5 +82,6 @@ private:
     // camera's fields as the C ABI takes them
     Hittable::DeviceCache& PrepareScene(Hittable& world, Hittable& lights, const std::vector<int>& devs, PrtCamera& c,
                                         PrtRenderParams& p);
+    void FillParams(PrtCamera& c, PrtRenderParams& p) const;
 };
 } // namespace Pooraytracer

@@ -22,6 +22,8 @@
  *   prt_accum_*           progressive, resumable rendering: the same frame built up over several calls
  *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel);
  *                         the *_adaptive ones stop each pixel once its noise estimate meets a tolerance
+ *   prt_render_features   first-hit albedo / normal / depth / triangle per pixel (the inputs of a denoiser)
+ *   prt_denoise           edge-aware a-trous filter guided by those; prt_accum_*_denoised: an accumulator's frame, denoised
  *
  * Conventions: every function returns 0 on success or a negative PRT_E_* code and never throws;
  * prt_last_error() returns a thread-local message for the last failure.  All input buffers are
@@ -448,6 +450,68 @@ int prt_accum_export_adaptive(const PrtAccum* acc, double* sums, double* moments
  * PRT_E_LIMIT above INT32_MAX samples. */
 int prt_accum_import_adaptive(PrtAccum* acc, const double* sums, const double* moments, const uint32_t* counts,
                               uint64_t samples, uint64_t fingerprint);
+
+/*
+ * First-hit feature buffers (AOVs) and an edge-aware a-trous denoiser.
+ *
+ * Features.  prt_render_features traces the camera rays of the first feature_spp samples of every pixel of the frame (all
+ * of it, whatever rank / nranks / tile_size say) with the closest-hit traversal, always in fp64 (params->precision is
+ * ignored).  The rays are K3's: with pixel_jitter = 0 every sample is the pixel centre, so the one ray is traced once; with
+ * pixel_jitter = 1 sample s is offset by the SampleSquare() draws of the stream keyed (seed, j*W+i, s), as in a frame.  Per
+ * pixel, written as fp32 (each output pointer may be NULL = skip):
+ *   albedo [H][W][3]  at a hit: Lambertian, Debug: Kd (the texture if the material has one); Phong: Kd + Ks (the texture
+ *                     twice when the material has one, as PhoneReflectance stores it); Mirror, CookTorrance, DiffuseLight,
+ *                     Empty: (1,1,1).  At a miss: (1,1,1)
+ *   normal [H][W][3]  at a hit: the unit geometric normal K3 shades with, facing the incoming ray (SetFaceNormal); miss: 0
+ *   depth  [H][W]     at a hit: t * |d|, the world distance (camera directions are not normalised); miss: +inf
+ *   prim   [H][W]     triangle index (PrtSceneDesc order) of sample 0's hit, -1 on a miss
+ * With feature_spp > 1 albedo and normal are means over the samples (the normal mean is not renormalised) and depth is the
+ * mean over the samples that hit (+inf if none did).  Sums are fp64; each output is the float rounding of its mean.
+ *
+ * Filter (Dammertz et al., HPG 2010), spatial only, fp32, deterministic.  Level i = 0 .. iterations-1 is a 5x5 gather with
+ * step 2^i and weights h = [1,4,6,4,1]/16 per axis; each level's output colour is the next level's input, the features
+ * stay fixed.  For a centre pixel p and a tap q inside the image:
+ *     w = h(dx) h(dy) exp(-(|c_p-c_q|^2 / (sigma_color 2^-i)^2 + |n_p-n_q|^2 / sigma_normal^2
+ *                          + Dz + |a_p-a_q|^2 / sigma_albedo^2))
+ *     Dz = (z_p-z_q)^2 / (sigma_depth^2 z_p^2) if both hit (finite depth), 0 if both miss; w = 0 if exactly one misses
+ *     out_p = sum w c_q / sum w
+ * A tap with a non-finite colour gets weight 0; a non-finite centre outputs 0 at that level (as WriteColorAttachment maps
+ * NaN to 0).  A sigma that is <= 0 or +inf switches its term off (for sigma_depth: the hit / miss rule as well); NaN is
+ * refused.  demodulate = 1: the filter runs on c / max(a, 1e-3) per channel and multiplies the result back by the same
+ * max(a, 1e-3).  iterations = 0 copies the input.  The restatement in numpy is tests/denoise_model.py.
+ */
+typedef struct PrtDenoiseParams {
+    int32_t iterations;   /* levels, 0..10; 0 copies the input */
+    int32_t demodulate;   /* 0 or 1 */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+    int32_t feature_spp;  /* >= 1; used where features are traced (prt_accum_*_denoised) */
+    int32_t reserved;     /* must be 0 */
+} PrtDenoiseParams;
+/* The defaults, measured on cornell-box, veach-mis and bathroom2 (tools/denoise_timing.py). */
+void prt_denoise_defaults(PrtDenoiseParams* p);
+
+/* Synchronous: features of the frame into host buffers. */
+int prt_render_features(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* params, int32_t feature_spp,
+                        float* albedo, float* normal, float* depth, int32_t* prim);
+/* Same into device buffers, asynchronous on hip_stream. */
+int prt_render_features_device(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* params, int32_t feature_spp,
+                               void* d_albedo, void* d_normal, void* d_depth, void* d_prim, void* hip_stream);
+/* Synchronous: the filter on host buffers (rgb / albedo / normal [h][w][3], depth [h][w], out [h][w][3]; out may not alias
+ * an input).  The scene only supplies the device and the filter's scratch (64 bytes per pixel, kept between calls). */
+int prt_denoise(PrtScene* scene, int32_t w, int32_t h, const float* rgb, const float* albedo, const float* normal,
+                const float* depth, const PrtDenoiseParams* params, float* out);
+/* Same on device buffers, asynchronous on hip_stream.  Calls on one scene are ordered by the library (they share the scratch). */
+int prt_denoise_device(PrtScene* scene, int32_t w, int32_t h, const void* d_rgb, const void* d_albedo, const void* d_normal,
+                       const void* d_depth, const PrtDenoiseParams* params, void* d_out, void* hip_stream);
+/* The accumulator's frame, denoised: prt_accum_resolve's fp32 frame through prt_denoise_device, guided by
+ * prt_render_features of the accumulator's frozen camera and params (params->feature_spp samples).  Works on plain and
+ * adaptive accumulators.  The features are traced once and cached; the cache is dropped on prt_accum_reset and on a scene
+ * generation change (prt_scene_update_vertices), and retraced for another feature_spp.  d_rgb_f32 / d_rgb_u8 (W*H*3, either
+ * may be NULL, not both): the denoised frame and exactly the bytes prt_tonemap_srgb8 makes of it.  Asynchronous on
+ * hip_stream.  PRT_E_INVALID for nranks > 1: a tile share lacks its neighbours' pixels. */
+int prt_accum_resolve_denoised(PrtAccum* acc, const PrtDenoiseParams* params, void* d_rgb_f32, void* d_rgb_u8, void* hip_stream);
+/* Synchronous: the denoised frame into a W*H*3 host buffer. */
+int prt_accum_read_denoised(PrtAccum* acc, const PrtDenoiseParams* params, float* rgb_f32);
 
 #ifdef __cplusplus
 }

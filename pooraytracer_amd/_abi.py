@@ -145,6 +145,19 @@ class PrtAdaptiveParams(C.Structure):
 ADAPTIVE_DEFAULT_BATCH = 8  # prt.h PRT_ADAPTIVE_DEFAULT_BATCH
 
 
+class PrtDenoiseParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("demodulate", C.c_int32),
+        ("sigma_color", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("feature_spp", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class PrtRay(C.Structure):
     _fields_ = [("o", D3), ("tmin", C.c_double), ("d", D3), ("tmax", C.c_double)]
 
@@ -240,6 +253,13 @@ EXPORTS = [
     "prt_accum_pixel_samples",
     "prt_accum_export_adaptive",
     "prt_accum_import_adaptive",
+    "prt_denoise_defaults",
+    "prt_render_features",
+    "prt_render_features_device",
+    "prt_denoise",
+    "prt_denoise_device",
+    "prt_accum_resolve_denoised",
+    "prt_accum_read_denoised",
 ]
 
 

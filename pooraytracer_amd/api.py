@@ -84,6 +84,14 @@ def load():
     L.prt_accum_pixel_samples.argtypes = [vp, vp]
     L.prt_accum_export_adaptive.argtypes = [vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.prt_accum_import_adaptive.argtypes = [vp, vp, vp, vp, u64, u64]
+    L.prt_denoise_defaults.argtypes = [vp]
+    L.prt_denoise_defaults.restype = None
+    L.prt_render_features.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp]
+    L.prt_render_features_device.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.prt_denoise.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.prt_denoise_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.prt_accum_resolve_denoised.argtypes = [vp, vp, vp, vp, vp]
+    L.prt_accum_read_denoised.argtypes = [vp, vp, vp]
     if L.prt_abi_version() != _abi.PRT_ABI_VERSION and os.environ.get("PRT_ABI_ANY") != "1":  # (PRT_ABI_ANY: A/B tools timing an older build)
         raise PrtError(-101, "ABI version mismatch between _abi.py and libprt_hip.so")
     try:
@@ -127,6 +135,25 @@ def _check(rc, L=None):
 
 def _f64(a, k):
     return np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)
+
+
+def denoise_params(L=None, **params):
+    """A PrtDenoiseParams: prt_denoise_defaults, then the given fields (iterations, demodulate, sigma_color, sigma_normal,
+    sigma_depth, sigma_albedo, feature_spp)."""
+    p = _abi.PrtDenoiseParams()
+    (L or load()).prt_denoise_defaults(C.byref(p))
+    names = {f for f, _ in _abi.PrtDenoiseParams._fields_} - {"reserved"}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"denoise: unknown parameter {k!r}")
+        setattr(p, k, int(v) if k in ("iterations", "demodulate", "feature_spp") else float(v))
+    return p
+
+
+def denoise_defaults():
+    """prt_denoise_defaults as a dict."""
+    p = denoise_params()
+    return {f: getattr(p, f) for f, _ in _abi.PrtDenoiseParams._fields_ if f != "reserved"}
 
 
 def device_count():
@@ -258,6 +285,50 @@ class Scene:
         c, p = _abi.make_camera(cam), _abi.make_params(**kw)
         _check(self._L.prt_render_device(self._h, C.byref(c), C.byref(p), d_f64_ptr, d_f32_ptr, int(count_work), stream), self._L)
 
+    def features(self, camera=None, feature_spp=1, **kw):
+        """First-hit feature buffers (prt_render_features, include/prt.h): dict of albedo (H, W, 3) float32, normal (H, W, 3)
+        float32, depth (H, W) float32 (+inf on a miss) and prim (H, W) int32 (-1 on a miss).  kw as for render()."""
+        cam = camera or self.data.camera
+        c, p = _abi.make_camera(cam), _abi.make_params(**kw)
+        h, w = cam.height, cam.width
+        out = {"albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32),
+               "depth": np.zeros((h, w), np.float32), "prim": np.zeros((h, w), np.int32)}
+        _check(self._L.prt_render_features(self._h, C.byref(c), C.byref(p), int(feature_spp), out["albedo"].ctypes.data,
+                                          out["normal"].ctypes.data, out["depth"].ctypes.data, out["prim"].ctypes.data), self._L)
+        return out
+
+    def features_device(self, d_albedo, d_normal, d_depth, d_prim, camera=None, feature_spp=1, stream=None, **kw):
+        """prt_render_features_device: asynchronous, into device buffers (raw pointers; any may be None)."""
+        cam = camera or self.data.camera
+        c, p = _abi.make_camera(cam), _abi.make_params(**kw)
+        _check(self._L.prt_render_features_device(self._h, C.byref(c), C.byref(p), int(feature_spp), d_albedo, d_normal, d_depth,
+                                                 d_prim, stream), self._L)
+
+    def denoise(self, rgb, features, **params):
+        """The a-trous filter (prt_denoise) on host arrays: rgb (H, W, 3), features a dict with albedo (H, W, 3), normal
+        (H, W, 3) and depth (H, W) (what features() returns).  params: fields of PrtDenoiseParams, else the defaults.
+        Returns (H, W, 3) float32."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"denoise: rgb must have shape (H, W, 3), got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        a = np.ascontiguousarray(features["albedo"], dtype=np.float32)
+        n = np.ascontiguousarray(features["normal"], dtype=np.float32)
+        z = np.ascontiguousarray(features["depth"], dtype=np.float32)
+        if a.shape != rgb.shape or n.shape != rgb.shape or z.shape != rgb.shape[:2]:
+            raise ValueError(f"denoise: feature shapes {a.shape} {n.shape} {z.shape} do not match rgb {rgb.shape}")
+        p = denoise_params(self._L, **params)
+        out = np.empty_like(rgb)
+        _check(self._L.prt_denoise(self._h, w, h, rgb.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data, C.byref(p),
+                                  out.ctypes.data), self._L)
+        return out
+
+    def denoise_device(self, width, height, d_rgb, d_albedo, d_normal, d_depth, d_out, stream=None, **params):
+        """prt_denoise_device: asynchronous, on device buffers (raw pointers)."""
+        p = denoise_params(self._L, **params)
+        _check(self._L.prt_denoise_device(self._h, int(width), int(height), d_rgb, d_albedo, d_normal, d_depth, C.byref(p), d_out,
+                                         stream), self._L)
+
     def tonemap_srgb8(self, d_f32_ptr, width, height, d_u8_ptr, stream=None):
         _check(self._L.prt_tonemap_srgb8(self._h, d_f32_ptr, width, height, d_u8_ptr, stream), self._L)
 
@@ -338,6 +409,19 @@ class Accumulator:
     def reset(self):
         _check(self._L.prt_accum_reset(self._h), self._L)
         return self
+
+    def denoised(self, **params):
+        """The frame of the samples so far, denoised (prt_accum_read_denoised): (H, W, 3) float32.  params: fields of
+        PrtDenoiseParams, else the defaults.  The features are traced once with this accumulator's camera and keywords."""
+        p = denoise_params(self._L, **params)
+        out = np.zeros(self._shape, dtype=np.float32)
+        _check(self._L.prt_accum_read_denoised(self._h, C.byref(p), out.ctypes.data), self._L)
+        return out
+
+    def resolve_denoised(self, d_f32_ptr=None, d_u8_ptr=None, stream=None, **params):
+        """Asynchronous prt_accum_resolve_denoised into device buffers (raw pointers)."""
+        p = denoise_params(self._L, **params)
+        _check(self._L.prt_accum_resolve_denoised(self._h, C.byref(p), d_f32_ptr, d_u8_ptr, stream), self._L)
 
     def state(self):
         """Checkpoint: (sums (H, W, 3) float64, samples, fingerprint)."""

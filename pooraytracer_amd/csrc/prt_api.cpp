@@ -48,6 +48,11 @@ void launch_accumulate_list(const DRenderParams& P, const double* d_partial, con
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
                           hipStream_t st);
 void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
+void launch_features(const DScene& S, const DCamera& C, uint64_t seed_key, int jitter, int spp, float* albedo, float* normal,
+                     float* depth, int32_t* prim, hipStream_t st);
+size_t denoise_scratch_bytes(int w, int h);
+void launch_denoise(int w, int h, const float* rgb, const float* albedo, const float* normal, const float* depth,
+                    int iterations, int demod, const float sigma[4], void* scratch, float* out, hipStream_t st);
 void launch_add_f32(float* dst, const float* src, size_t n, hipStream_t st);
 void launch_material_eval(const DScene& S, int material, const double* wi, const double* wo, const double* uv, size_t n,
                           uint64_t seed, double* out, hipStream_t st);
@@ -175,6 +180,11 @@ struct PrtScene {
     PrtCounters last{};
     float* multi_fb = nullptr; // prt_render_multi: this device's full-size fp32 framebuffer (kept between frames)
     size_t multi_fb_cap = 0;
+    // prt_denoise_device: the filter's scratch (prt_denoise.hip), kept between calls; a call waits (on its stream) for the
+    // previous call's end (dn_done) before it reuses it
+    void* d_dn = nullptr;
+    size_t dn_cap = 0;
+    hipEvent_t dn_done = nullptr;
 
     int fail_upload_at = -1, n_uploads = 0; // test hook (PRT_TEST_FAIL_UPLOAD=k): the k-th table upload reports out-of-memory
     template <typename T>
@@ -198,6 +208,11 @@ struct PrtScene {
         if (d_sort) (void)hipFree(d_sort);
         d_sort = nullptr;
         sort_cap = 0;
+        if (d_dn) (void)hipFree(d_dn);
+        d_dn = nullptr;
+        dn_cap = 0;
+        if (dn_done) (void)hipEventDestroy(dn_done);
+        dn_done = nullptr;
         if (sort_done) (void)hipEventDestroy(sort_done);
         sort_done = nullptr;
         for (CallSlot& q : slots) {
@@ -1609,6 +1624,14 @@ struct PrtAccum {
     uint32_t* d_seg = nullptr;
     uint32_t* d_active = nullptr;
     uint32_t* h_active = nullptr;
+    // prt_accum_resolve_denoised: the cached features (albedo [n], normal [n], depth [n / 3] floats) of scene generation
+    // feat_gen traced with feat_spp samples, the resolved fp32 frame and the denoised one (when the caller wants only bytes)
+    float* d_feat = nullptr;
+    bool feat_valid = false;
+    uint64_t feat_gen = 0;
+    int32_t feat_spp = 0;
+    float* d_res32 = nullptr;
+    float* d_dn32 = nullptr;
 };
 
 namespace {
@@ -1789,6 +1812,9 @@ void prt_accum_destroy(PrtAccum* a) {
     if (a->d_seg) (void)hipFree(a->d_seg);
     if (a->d_active) (void)hipFree(a->d_active);
     if (a->h_active) (void)hipHostFree(a->h_active);
+    if (a->d_feat) (void)hipFree(a->d_feat);
+    if (a->d_res32) (void)hipFree(a->d_res32);
+    if (a->d_dn32) (void)hipFree(a->d_dn32);
     delete a;
 }
 
@@ -1825,6 +1851,7 @@ int prt_accum_reset(PrtAccum* a) {
     PRT_HIP(accum_zero(a));
     a->samples = 0;
     a->generation = a->scene->generation;
+    a->feat_valid = false; // the denoiser's features are retraced on the next use
     return PRT_OK;
 }
 
@@ -2006,6 +2033,219 @@ int prt_tonemap_srgb8(PrtScene* s, const void* d_rgb_f32, int width, int height,
                         reinterpret_cast<hipStream_t>(stream));
     PRT_HIP(hipGetLastError());
     return PRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------- features + denoiser
+void prt_denoise_defaults(PrtDenoiseParams* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    // measured: tools/denoise_timing.py, DESIGN.md §7 (the best point of its 16-spp sweep over cornell-box, veach-mis and bathroom2)
+    p->iterations = 4;
+    p->demodulate = 1;
+    p->sigma_color = 0.5f;
+    p->sigma_normal = 0.2f;
+    p->sigma_depth = 0.1f;
+    p->sigma_albedo = 0.1f;
+    p->feature_spp = 1;
+    p->reserved = 0;
+}
+
+} // extern "C"
+
+namespace {
+int check_denoise_params(const PrtDenoiseParams* p, const std::string& w) {
+    if (!p) return fail(PRT_E_INVALID, w + ": null denoise params");
+    if (p->reserved != 0) return fail(PRT_E_INVALID, w + ": reserved must be 0");
+    if (p->iterations < 0 || p->iterations > 10) return fail(PRT_E_INVALID, w + ": iterations must be in 0..10");
+    if (p->demodulate != 0 && p->demodulate != 1) return fail(PRT_E_INVALID, w + ": demodulate must be 0 or 1");
+    if (std::isnan(p->sigma_color) || std::isnan(p->sigma_normal) || std::isnan(p->sigma_depth) || std::isnan(p->sigma_albedo))
+        return fail(PRT_E_INVALID, w + ": a sigma is NaN");
+    if (p->feature_spp < 1) return fail(PRT_E_INVALID, w + ": feature_spp must be >= 1");
+    return PRT_OK;
+}
+
+// k_features on the scene's fp64 tables (the tree K1 traverses).
+int features_impl(PrtScene* s, const std::string& w, const PrtCamera* cam, const PrtRenderParams* p, int32_t feature_spp, float* albedo,
+                  float* normal, float* depth, int32_t* prim, hipStream_t st) {
+    if (!cam || !p) return fail(PRT_E_INVALID, w + ": null argument");
+    if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, w + ": bad image size");
+    if ((uint64_t)cam->width * (uint64_t)cam->height >= (1ull << 31)) return fail(PRT_E_LIMIT, w + ": more than 2^31 pixels");
+    if (feature_spp < 1) return fail(PRT_E_INVALID, w + ": feature_spp must be >= 1");
+    if (!albedo && !normal && !depth && !prim) return fail(PRT_E_INVALID, w + ": no output buffer");
+    DCamera C;
+    prt::setup_camera(*cam, C);
+    prt::launch_features(s->d, C, prt::seed_key(p->seed), p->pixel_jitter ? 1 : 0, feature_spp, albedo, normal, depth, prim, st);
+    PRT_HIP(hipGetLastError());
+    return PRT_OK;
+}
+
+// The filter on device buffers through the scene's scratch.
+int denoise_impl(PrtScene* s, const std::string& w, int32_t W, int32_t H, const void* rgb, const void* albedo, const void* normal,
+                 const void* depth, const PrtDenoiseParams* p, void* out, hipStream_t st) {
+    int rc = check_denoise_params(p, w);
+    if (rc) return rc;
+    if (W < 1 || H < 1) return fail(PRT_E_INVALID, w + ": bad image size");
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 31)) return fail(PRT_E_LIMIT, w + ": more than 2^31 pixels");
+    if (!rgb || !albedo || !normal || !depth || !out) return fail(PRT_E_INVALID, w + ": null buffer");
+    const size_t npx = (size_t)W * H;
+    if (p->iterations == 0) {
+        PRT_HIP(hipMemcpyAsync(out, rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return PRT_OK;
+    }
+    const size_t need = prt::denoise_scratch_bytes(W, H);
+    if (!s->dn_done) PRT_HIP(hipEventCreateWithFlags(&s->dn_done, hipEventDisableTiming));
+    else PRT_HIP(hipStreamWaitEvent(st, s->dn_done, 0)); // the scratch is the previous call's until that call has ended
+    if (s->dn_cap < need) {
+        PRT_HIP(hipEventSynchronize(s->dn_done));
+        if (s->d_dn) (void)hipFree(s->d_dn);
+        s->d_dn = nullptr;
+        s->dn_cap = 0;
+        if (hipMalloc(&s->d_dn, need) != hipSuccess) return fail(PRT_E_OOM, w + ": hipMalloc of the filter scratch failed");
+        s->dn_cap = need;
+    }
+    const float sigma[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
+    prt::launch_denoise(W, H, static_cast<const float*>(rgb), static_cast<const float*>(albedo), static_cast<const float*>(normal),
+                        static_cast<const float*>(depth), p->iterations, p->demodulate, sigma, s->d_dn, static_cast<float*>(out), st);
+    PRT_HIP(hipGetLastError());
+    PRT_HIP(hipEventRecord(s->dn_done, st));
+    return PRT_OK;
+}
+
+// Device buffers of a host-side call, freed on every way out.
+struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+    void* get(size_t bytes, hipError_t& e) {
+        void* q = nullptr;
+        if (e == hipSuccess) e = hipMalloc(&q, bytes);
+        if (q) p.push_back(q);
+        return q;
+    }
+};
+int hip_fail(const std::string& w, hipError_t e) {
+    return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, w + ": " + hipGetErrorString(e));
+}
+} // namespace
+
+extern "C" {
+
+int prt_render_features_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, int32_t feature_spp, void* d_albedo,
+                               void* d_normal, void* d_depth, void* d_prim, void* stream) {
+    int rc = require_uploaded(s, "prt_render_features_device");
+    if (rc) return rc;
+    return features_impl(s, "prt_render_features_device", cam, p, feature_spp, static_cast<float*>(d_albedo), static_cast<float*>(d_normal),
+                         static_cast<float*>(d_depth), static_cast<int32_t*>(d_prim), reinterpret_cast<hipStream_t>(stream));
+}
+
+int prt_render_features(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, int32_t feature_spp, float* albedo, float* normal,
+                        float* depth, int32_t* prim) {
+    const std::string w = "prt_render_features";
+    int rc = require_uploaded(s, w.c_str());
+    if (rc) return rc;
+    if (!cam || cam->width < 1 || cam->height < 1) return features_impl(s, w, cam, p, feature_spp, albedo, normal, depth, prim, nullptr);
+    const size_t npx = (size_t)cam->width * cam->height;
+    DevBufs b;
+    hipError_t e = hipSuccess;
+    void* da = albedo ? b.get(npx * 3 * sizeof(float), e) : nullptr;
+    void* dn = normal ? b.get(npx * 3 * sizeof(float), e) : nullptr;
+    void* dz = depth ? b.get(npx * sizeof(float), e) : nullptr;
+    void* dp = prim ? b.get(npx * sizeof(int32_t), e) : nullptr;
+    if (e != hipSuccess) return hip_fail(w, e);
+    if ((rc = features_impl(s, w, cam, p, feature_spp, static_cast<float*>(da), static_cast<float*>(dn), static_cast<float*>(dz),
+                            static_cast<int32_t*>(dp), nullptr)))
+        return rc;
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess && albedo) e = hipMemcpy(albedo, da, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && normal) e = hipMemcpy(normal, dn, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && depth) e = hipMemcpy(depth, dz, npx * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && prim) e = hipMemcpy(prim, dp, npx * sizeof(int32_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? PRT_OK : hip_fail(w, e);
+}
+
+int prt_denoise_device(PrtScene* s, int32_t w, int32_t h, const void* d_rgb, const void* d_albedo, const void* d_normal,
+                       const void* d_depth, const PrtDenoiseParams* p, void* d_out, void* stream) {
+    int rc = require_uploaded(s, "prt_denoise_device");
+    if (rc) return rc;
+    return denoise_impl(s, "prt_denoise_device", w, h, d_rgb, d_albedo, d_normal, d_depth, p, d_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int prt_denoise(PrtScene* s, int32_t w, int32_t h, const float* rgb, const float* albedo, const float* normal, const float* depth,
+                const PrtDenoiseParams* p, float* out) {
+    const std::string who = "prt_denoise";
+    int rc = require_uploaded(s, who.c_str());
+    if (rc) return rc;
+    if ((rc = check_denoise_params(p, who))) return rc;
+    if (w < 1 || h < 1) return fail(PRT_E_INVALID, who + ": bad image size");
+    if ((uint64_t)w * (uint64_t)h >= (1ull << 31)) return fail(PRT_E_LIMIT, who + ": more than 2^31 pixels");
+    if (!rgb || !albedo || !normal || !depth || !out) return fail(PRT_E_INVALID, who + ": null buffer");
+    const size_t npx = (size_t)w * h, b3 = npx * 3 * sizeof(float), b1 = npx * sizeof(float);
+    DevBufs b;
+    hipError_t e = hipSuccess;
+    void* dc = b.get(b3, e);
+    void* da = b.get(b3, e);
+    void* dn = b.get(b3, e);
+    void* dz = b.get(b1, e);
+    void* dout = b.get(b3, e);
+    if (e == hipSuccess) e = hipMemcpy(dc, rgb, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(da, albedo, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dn, normal, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dz, depth, b1, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(who, e);
+    if ((rc = denoise_impl(s, who, w, h, dc, da, dn, dz, p, dout, nullptr))) return rc;
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, b3, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? PRT_OK : hip_fail(who, e);
+}
+
+int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
+    const std::string w = "prt_accum_resolve_denoised";
+    int rc = accum_ready(a, w.c_str());
+    if (rc || (rc = check_denoise_params(p, w))) return rc;
+    if (a->params.nranks > 1) return fail(PRT_E_INVALID, w + ": nranks > 1 (a tile share lacks its neighbours' pixels)");
+    if (!d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, w + ": no output buffer");
+    const size_t npx = a->n / 3;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    if (!a->d_feat) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_feat), npx * 7 * sizeof(float)));
+    if (!a->d_res32) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_res32), a->n * sizeof(float)));
+    if (!d_rgb_f32 && !a->d_dn32) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_dn32), a->n * sizeof(float)));
+    float* alb = a->d_feat;
+    float* nrm = alb + a->n;
+    float* dep = nrm + a->n;
+    if (!a->feat_valid || a->feat_gen != a->scene->generation || a->feat_spp != p->feature_spp) {
+        a->feat_valid = false;
+        if ((rc = features_impl(a->scene, w, &a->cam, &a->params, p->feature_spp, alb, nrm, dep, nullptr, st))) return rc;
+        a->feat_valid = true;
+        a->feat_gen = a->scene->generation;
+        a->feat_spp = p->feature_spp;
+    }
+    prt::launch_resolve(a->d_sum, a->n, a->samples, a->adaptive ? a->d_count : nullptr, nullptr, a->d_res32, nullptr, st);
+    PRT_HIP(hipGetLastError());
+    float* out = d_rgb_f32 ? static_cast<float*>(d_rgb_f32) : a->d_dn32;
+    if ((rc = denoise_impl(a->scene, w, a->cam.width, a->cam.height, a->d_res32, alb, nrm, dep, p, out, st))) return rc;
+    if (d_rgb_u8) {
+        prt::launch_tonemap(out, a->n, static_cast<uint8_t*>(d_rgb_u8), st);
+        PRT_HIP(hipGetLastError());
+    }
+    PRT_HIP(hipEventRecord(a->done, st));
+    return PRT_OK;
+}
+
+int prt_accum_read_denoised(PrtAccum* a, const PrtDenoiseParams* p, float* rgb_f32) {
+    const std::string w = "prt_accum_read_denoised";
+    int rc = accum_ready(a, w.c_str());
+    if (rc) return rc;
+    if (!rgb_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
+    DevBufs b;
+    hipError_t e = hipSuccess;
+    void* d = b.get(a->n * sizeof(float), e);
+    if (e != hipSuccess) return hip_fail(w, e);
+    if ((rc = prt_accum_resolve_denoised(a, p, d, nullptr, nullptr))) return rc;
+    e = hipEventSynchronize(a->done);
+    if (e == hipSuccess) e = hipMemcpy(rgb_f32, d, a->n * sizeof(float), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? PRT_OK : hip_fail(w, e);
 }
 
 } // extern "C"

@@ -1000,6 +1000,82 @@ __global__ void k_accumulate_list(DRenderParams P, const double* __restrict__ pa
     }
 }
 
+// ------------------------------------------------------------------------------------------- feature buffers
+// prt_render_features (include/prt.h): the first-hit features a denoiser is guided by.  One thread per pixel; sample s of the
+// pixel is K3's camera ray of sample s (the pixel centre, or with jitter the SampleSquare offset drawn as the first two numbers
+// of the stream keyed (seed, j*W+i, s)), traced with the closest-hit traversal K1 and K3 use.  Without jitter every sample is
+// the same ray: it is traced once and its features are the means.  Sums are fp64, the outputs their fp32 rounding.
+template <bool PAD>
+__global__ __launch_bounds__(PRT_BLOCK) void k_features(DScene S, DCamera C, uint64_t seed_key, int jitter, int spp,
+                                                        float* __restrict__ albedo, float* __restrict__ normal,
+                                                        float* __restrict__ depth, int32_t* __restrict__ prim) {
+    __shared__ uint32_t s_stack[PRT_BLOCK / 64][PRT_STACK_DEPTH][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t* stk = &s_stack[wave][0][lane];
+    const uint32_t W = (uint32_t)C.width, npx = W * (uint32_t)C.height;
+    const uint32_t pix = blockIdx.x * PRT_BLOCK + threadIdx.x;
+    const bool valid = pix < npx;
+    const int py = valid ? (int)(pix / W) : 0, px = valid ? (int)(pix - (uint32_t)py * W) : 0;
+    const d3 center = mk3(C.center[0], C.center[1], C.center[2]);
+    const d3 p00 = mk3(C.pixel00[0], C.pixel00[1], C.pixel00[2]), du = mk3(C.du[0], C.du[1], C.du[2]), dv = mk3(C.dv[0], C.dv[1], C.dv[2]);
+    d3 a_sum = mk3(0, 0, 0), n_sum = mk3(0, 0, 0);
+    double z_sum = 0.0;
+    int n_hit = 0;
+    int32_t prim0 = -1;
+    WorkCount wc{0, 0, 0, 0, 0};
+    Trav<PAD> tr;
+    const int traced = jitter ? spp : 1; // wave-uniform
+    for (int s = 0; s < traced; ++s) {
+        real fx = (real)px, fy = (real)py;
+        if (jitter) {
+            Rng rng;
+            rng.seed_keyed(seed_key, (uint64_t)pix, (uint64_t)s);
+            fy = fy + (rng.next() - RL(0.5)); // offset.y first, as K3 draws it
+            fx = fx + (rng.next() - RL(0.5));
+        }
+        const d3 ps = p00 + fx * du + fy * dv;
+        tr.init(S, center, ps - center, RL(0.0001), PRT_INF);
+        tr.hit.alpha = tr.hit.beta = RL(0.0);
+        if (!valid) tr.active = false;
+        while (__ballot(tr.active) != 0ULL) tr.template round<false>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, RL(0.0001), false);
+        if (!valid) continue;
+        if (s == 0) prim0 = tr.hit.tri >= 0 ? S.shade[tr.hit.tri].prim : -1;
+        if (tr.hit.tri < 0) {
+            a_sum = a_sum + mk3(1, 1, 1);
+            continue;
+        }
+        const DTriShade* sh = S.shade + tr.hit.tri;
+        const DMaterial& m = S.materials[sh->material];
+        const d3 gn = ld3(tri_at<PAD>(S, (uint32_t)tr.hit.tri)->n);
+        const d3 fn = dot(tr.d, gn) < RL(0.) ? gn : -gn; // SetFaceNormal, as make_ctx
+        const real w0 = RL(1.) - tr.hit.alpha - tr.hit.beta;
+        const d2 uv{w0 * sh->uv0[0] + tr.hit.alpha * sh->uv1[0] + tr.hit.beta * sh->uv2[0],
+                    w0 * sh->uv0[1] + tr.hit.alpha * sh->uv1[1] + tr.hit.beta * sh->uv2[1]};
+        constexpr int F = PRT_FEAT_ALL | PRT_FEAT_EXTRA;
+        d3 a = mk3(1, 1, 1);
+        if (m.type == PRT_MAT_LAMBERTIAN || m.type == PRT_MAT_DEBUG) a = mat_kd<F>(S, m, uv);
+        else if (m.type == PRT_MAT_PHONG) a = mat_kd<F>(S, m, uv) + mat_ks<F>(S, m, uv);
+        a_sum = a_sum + a;
+        n_sum = n_sum + fn;
+        z_sum += (double)tr.hit.t * sqrt((double)dot(tr.d, tr.d)); // world distance: d is not normalised
+        n_hit++;
+    }
+    if (!valid) return;
+    const real nt = (real)traced; // means over the traced samples (the untraced ones repeat the one ray)
+    if (albedo) {
+        albedo[(size_t)pix * 3] = (float)(a_sum.x / nt);
+        albedo[(size_t)pix * 3 + 1] = (float)(a_sum.y / nt);
+        albedo[(size_t)pix * 3 + 2] = (float)(a_sum.z / nt);
+    }
+    if (normal) {
+        normal[(size_t)pix * 3] = (float)(n_sum.x / nt);
+        normal[(size_t)pix * 3 + 1] = (float)(n_sum.y / nt);
+        normal[(size_t)pix * 3 + 2] = (float)(n_sum.z / nt);
+    }
+    if (depth) depth[pix] = n_hit ? (float)(z_sum / (double)n_hit) : __builtin_huge_valf();
+    if (prim) prim[pix] = prim0;
+}
+
 // dst += src (fp32 framebuffers of tile shares that live on ONE device: disjoint tiles, so every element is x + 0)
 __global__ void k_add_f32(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1202,6 +1278,15 @@ void launch_material_scatter(const DScene& S, int material, const double* rd, co
 void launch_texture_value(const DScene& S, int texture, const double* uv, size_t n, double* out, hipStream_t st) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_texture_value, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, texture, uv, n, out);
+}
+
+void launch_features(const DScene& S, const DCamera& C, uint64_t seed_key, int jitter, int spp, float* albedo, float* normal,
+                     float* depth, int32_t* prim, hipStream_t st) {
+    const size_t npx = (size_t)C.width * C.height;
+    if (npx == 0) return;
+    const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
+    hipLaunchKernelGGL(pad ? k_features<true> : k_features<false>, dim3((unsigned)((npx + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
+                       st, S, C, seed_key, jitter, spp, albedo, normal, depth, prim);
 }
 
 void launch_add_f32(float* dst, const float* src, size_t n, hipStream_t st) {

@@ -365,6 +365,11 @@ Hittable::DeviceCache& Camera::PrepareScene(Hittable& world, Hittable& lights, c
     }
     dc.Ensure(world, devs[0], sceneFlags);
     dc.EnsureReplicas(devs, sceneFlags);
+    FillParams(c, p);
+    return dc;
+}
+
+void Camera::FillParams(PrtCamera& c, PrtRenderParams& p) const {
     c.width = imageWidth; c.height = imageHeight; c.fovy = fovy;
     c.eye[0] = eye.x; c.eye[1] = eye.y; c.eye[2] = eye.z;
     c.look_at[0] = lookAt.x; c.look_at[1] = lookAt.y; c.look_at[2] = lookAt.z;
@@ -381,7 +386,6 @@ Hittable::DeviceCache& Camera::PrepareScene(Hittable& world, Hittable& lights, c
     p.rank = 0;
     p.nranks = 1;
     p.pixel_jitter = bPixelJitter ? 1 : 0;
-    return dc;
 }
 
 void Camera::Render(Hittable& world, Hittable& lights) {
@@ -642,12 +646,13 @@ double linear_to_srgb(double c) { // Camera.cpp:214-221
 }
 } // namespace
 
-void Camera::WriteColorAttachment(const std::string& outputPath, bool bWriteHDR) const { // Camera.cpp:279-331
+namespace {
+void write_attachment(const std::vector<color>& att, int imageWidth, int imageHeight, const std::string& outputPath, bool bWriteHDR) {
     std::vector<uint8_t> raw((size_t)imageWidth * imageHeight * 3);
     std::vector<float> hdr(bWriteHDR ? raw.size() : 0);
     const Interval intensity(0.0000, 0.9999);
-    for (size_t i = 0; i < (size_t)imageWidth * imageHeight && i < colorAttachment.size(); ++i) {
-        double c[3] = {colorAttachment[i].x, colorAttachment[i].y, colorAttachment[i].z};
+    for (size_t i = 0; i < (size_t)imageWidth * imageHeight && i < att.size(); ++i) {
+        double c[3] = {att[i].x, att[i].y, att[i].z};
         for (int k = 0; k < 3; ++k) {
             if (c[k] != c[k]) c[k] = 0.0;
             raw[i * 3 + k] = (uint8_t)(intensity.Clamp(linear_to_srgb(c[k])) * 255);
@@ -659,6 +664,39 @@ void Camera::WriteColorAttachment(const std::string& outputPath, bool bWriteHDR)
         const std::string h = outputPath.substr(0, outputPath.find_last_of('.')) + ".hdr";
         if (!write_hdr(h, imageWidth, imageHeight, hdr)) std::fprintf(stderr, "[pooraytracer] cannot write %s\n", h.c_str());
     }
+}
+} // namespace
+
+void Camera::WriteColorAttachment(const std::string& outputPath, bool bWriteHDR) const { // Camera.cpp:279-331
+    write_attachment(colorAttachment, imageWidth, imageHeight, outputPath, bWriteHDR);
+}
+
+void Camera::WriteDenoisedAttachment(const std::string& outputPath, bool bWriteHDR) const {
+    write_attachment(denoisedAttachment, imageWidth, imageHeight, outputPath, bWriteHDR);
+}
+
+void Camera::Denoise(Hittable& world, const PrtDenoiseParams* params) {
+    if (devices.size() > 1) throw std::invalid_argument("Camera::Denoise: one device only (`devices` lists several)");
+    Hittable::DeviceCache& dc = world.Device();
+    if (!dc.scene) throw std::logic_error("Camera::Denoise: render this world first (Render, RenderProgressive or RenderAdaptive)");
+    const size_t npx = (size_t)imageWidth * imageHeight;
+    if (colorAttachment.size() != npx) throw std::logic_error("Camera::Denoise: colorAttachment does not hold a frame of this size");
+    PrtDenoiseParams dp;
+    if (params) dp = *params;
+    else prt_denoise_defaults(&dp);
+    PrtCamera c;
+    PrtRenderParams p;
+    FillParams(c, p);
+    std::vector<float> albedo(npx * 3), normal(npx * 3), depth(npx), rgb(npx * 3), out(npx * 3);
+    check(prt_render_features(dc.scene, &c, &p, dp.feature_spp, albedo.data(), normal.data(), depth.data(), nullptr), "prt_render_features");
+    for (size_t i = 0; i < npx; ++i) {
+        rgb[i * 3] = (float)colorAttachment[i].x;
+        rgb[i * 3 + 1] = (float)colorAttachment[i].y;
+        rgb[i * 3 + 2] = (float)colorAttachment[i].z;
+    }
+    check(prt_denoise(dc.scene, imageWidth, imageHeight, rgb.data(), albedo.data(), normal.data(), depth.data(), &dp, out.data()), "prt_denoise");
+    denoisedAttachment.assign(npx, color(0., 0., 0.));
+    for (size_t i = 0; i < npx; ++i) denoisedAttachment[i] = color(out[i * 3], out[i * 3 + 1], out[i * 3 + 2]);
 }
 
 namespace {
