@@ -479,6 +479,10 @@ int prt_accum_import_adaptive(PrtAccum* acc, const double* sums, const double* m
  * NaN to 0).  A sigma that is <= 0 or +inf switches its term off (for sigma_depth: the hit / miss rule as well); NaN is
  * refused.  demodulate = 1: the filter runs on c / max(a, 1e-3) per channel and multiplies the result back by the same
  * max(a, 1e-3).  iterations = 0 copies the input.  The restatement in numpy is tests/denoise_model.py.
+ * Precision: the fp32 result follows the fp64 rule within about 1e-6 relative while the exponents stay small.  Where the
+ * colour term's exponent is in the tens (demodulated colours of albedo near 1e-3 reach 1e3-1e4 beside colours near 1;
+ * inputs spanning many decades), exp() multiplies each level's fp32 rounding by about that exponent, and the gap grows
+ * with the levels: about 1e-4 relative after 10 levels on such pixels (dark pixels next to those taps), not a bug.
  */
 typedef struct PrtDenoiseParams {
     int32_t iterations;   /* levels, 0..10; 0 copies the input */

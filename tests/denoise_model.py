@@ -114,17 +114,22 @@ def camera_setup(cam):
     return eye, ul + 0.5 * (du + dv), du, dv
 
 
-def jittered_rays(cam, seed, sample, rng_stream):
-    """Directions of sample `sample` of every pixel with pixel_jitter on: (H, W, 3).  rng_stream(seed, pixel, sample, n) is
-    the library's keyed stream (oracle.rng_stream); offset.y is the first number, offset.x the second."""
+def jittered_rays(cam, seed, sample, rng_stream, pixels=None):
+    """Directions of sample `sample` of every pixel with pixel_jitter on: (H, W, 3); or, with pixels = (N, 2) (x, y)
+    pairs, of those pixels only: (N, 3).  rng_stream(seed, pixel, sample, n) is the library's keyed stream
+    (oracle.rng_stream); offset.y is the first number, offset.x the second."""
     center, p00, du, dv = camera_setup(cam)
-    d = np.zeros((cam.height, cam.width, 3))
-    for y in range(cam.height):
-        for x in range(cam.width):
-            r = rng_stream(seed, y * cam.width + x, sample, 2)
-            fy, fx = y + (r[0] - 0.5), x + (r[1] - 0.5)
-            d[y, x] = p00 + fx * du + fy * dv - center
-    return d
+    if pixels is None:
+        pixels = np.stack(np.meshgrid(np.arange(cam.width), np.arange(cam.height)), -1).reshape(-1, 2)
+        shape = (cam.height, cam.width, 3)
+    else:
+        shape = (len(pixels), 3)
+    d = np.zeros((len(pixels), 3))
+    for k, (x, y) in enumerate(np.asarray(pixels, np.int64)):
+        r = rng_stream(seed, y * cam.width + x, sample, 2)
+        fy, fx = y + (r[0] - 0.5), x + (r[1] - 0.5)
+        d[k] = p00 + fx * du + fy * dv - center
+    return d.reshape(shape)
 
 
 def hit_features(data, rays_d, hits, texture_value=None):

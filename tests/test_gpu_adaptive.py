@@ -42,15 +42,22 @@ def adaptive_run(sc, rel_tol, rounds=32, **kw):
 
 @pytest.mark.parametrize("name", ["tiny", "mixed"])
 def test_adaptive_matches_the_model_on_oracle_radiance(gpu, name):
+    model_parity(gpu, name, batch=AD["batch"], rounds=32)
+
+
+def model_parity(gpu, name, batch, rounds):
+    """An adaptive run with rounds of `rounds` samples in batches of `batch` against adaptive_model.run on the oracle's
+    per-sample radiance: the same counts (a decision within 1e-9 of the threshold excepted), sums and moments."""
+    ad = dict(AD, batch=batch)
     data = SCENES[name]()
     cam = data.camera
     sc = api.Scene(data).upload(gpu)
-    with adaptive_run(sc, REL[name])[0] as acc:
+    with adaptive_run(sc, REL[name], rounds=rounds, batch=batch)[0] as acc:
         got = acc.export()
         assert np.array_equal(got["counts"], acc.pixel_samples())
     px = np.stack(np.meshgrid(np.arange(cam.width), np.arange(cam.height)), -1).reshape(-1, 2)
     rad = oracle.Oracle(data).render_samples(px, sample_begin=0, sample_count=AD["max_spp"], **KW)
-    ref = M.run(rad, rel_tol=REL[name], rounds=32, **AD)
+    ref = M.run(rad, rel_tol=REL[name], rounds=rounds, **ad)
     cnt = got["counts"].reshape(-1)
     stopped = (cnt < AD["max_spp"]).mean()
     assert 0.1 <= stopped <= 0.9, stopped
@@ -59,8 +66,8 @@ def test_adaptive_matches_the_model_on_oracle_radiance(gpu, name):
         # only a decision within 1e-9 of the threshold may go the other way: at the smaller count, the model's se / threshold
         for i in diff:
             m = min(int(cnt[i]), int(ref["counts"][i]))
-            sub = M.run(rad[i:i + 1, :m], rel_tol=REL[name], rounds=32, **dict(AD, max_spp=m))
-            r = M.ratio(sub, REL[name], 0.0, AD["batch"])[0]
+            sub = M.run(rad[i:i + 1, :m], rel_tol=REL[name], rounds=rounds, **dict(ad, max_spp=m))
+            r = M.ratio(sub, REL[name], 0.0, batch)[0]
             print(f"{name}: pixel {i} count {cnt[i]} vs model {ref['counts'][i]}, model se/threshold at {m} = {r!r}")
             assert abs(r - 1.0) <= 1e-9, (i, r)
     same = np.setdiff1d(np.arange(cnt.size), diff)
@@ -68,7 +75,9 @@ def test_adaptive_matches_the_model_on_oracle_radiance(gpu, name):
     gap = np.abs(got["moments"].reshape(-1)[same] - ref["moments"][same]) / np.maximum(1e-300, np.abs(ref["moments"][same]))
     assert gap.max() <= 1e-9, float(gap.max())
     assert got["samples"] == ref["samples"]
-    print(f"{name}: {stopped:.0%} stopped before max_spp, {diff.size} decisions at the threshold, n_active {ref['n_active']}")
+    print(f"{name} batch {batch} rounds {rounds}: {stopped:.0%} stopped before max_spp, {diff.size} decisions at the threshold, "
+          f"n_active {ref['n_active']}")
+    return ref
 
 
 @pytest.mark.parametrize("jitter", [False, True])

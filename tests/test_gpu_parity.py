@@ -17,6 +17,7 @@ import pytest
 
 import oracle
 from pooraytracer_amd import _abi, api, scenes
+from tests import frame_model
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -214,11 +215,10 @@ def test_f32_output_and_tonemap(gpu):
     u8 = torch.zeros(t.shape, dtype=torch.uint8, device="cuda")
     sc.tonemap_srgb8(t.data_ptr(), 64, 64, u8.data_ptr())
     torch.cuda.synchronize()
-    x = np.nan_to_num(t.cpu().numpy().astype(np.float64), nan=0.0)
-    srgb = np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(np.maximum(x, 0), 1 / 2.4) - 0.055)
-    ref = (np.clip(srgb, 0, 0.9999) * 255).astype(np.uint8)
-    diff = np.abs(u8.cpu().numpy().astype(int) - ref.astype(int))
-    assert diff.max() <= 1 and (diff > 0).mean() < 1e-3
+    # the bytes of the fp64 model exactly; only where sv * 255 lies within 1e-9 of an integer may the device's pow round over
+    ref, near = frame_model.srgb8(t.cpu().numpy())
+    off = u8.cpu().numpy() != ref
+    assert not (off & ~near).any(), np.argwhere(off & ~near)[:8].tolist()
 
 
 def test_full_size_properties(gpu):
