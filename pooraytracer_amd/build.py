@@ -4,6 +4,8 @@ Every source is compiled to its own object (in parallel, only when it or a heade
   libprt_hip.so      the product: reads NO developer environment variable (PRT_DEV_HOOKS 0);
   libprt_hip_dev.so  the same objects except prt_api.o, which is compiled with -DPRT_DEV_HOOKS=1: the PRT_TUNE_* / PRT_TEST_*
                      / PRT_VALIDATE_BVH hooks exist only there (failure-injection tests, sweep tools: api.dev_hooks()).
+                     PRT_TEST_DUMP_BVH=<file> writes each scene's traversal tree (header, nodes, leaf order) when it is
+                     built: host trees at create and on a host rebuild, device trees at upload (tests/bvh_model.py reads it).
 """
 import concurrent.futures
 import hashlib

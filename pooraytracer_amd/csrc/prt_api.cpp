@@ -228,6 +228,48 @@ struct PrtScene {
     }
 };
 
+// Test hook PRT_TEST_DUMP_BVH=<file> (dev-hooks build only): the traversal tree of a scene, as the kernels get it, for the
+// fp64 tree model of the tests (tests/bvh_model.py).  Little-endian: a 72-byte header
+//   u32 magic 'PBVH', u32 version 1, u64 n_tris, u64 n_nodes, u32 built_on_device, u32 depth, i32 stack_need, u32 node_bytes,
+//   f32 grid_origin[3], f32 grid_step[3], f32 coord_scale, u32 0
+// then the DNode array, then the leaf order (u32 per triangle: leaf position -> triangle index in description order).
+struct BvhDumpHeader {
+    uint32_t magic, version;
+    uint64_t n_tris, n_nodes;
+    uint32_t built_on_device, depth;
+    int32_t stack_need;
+    uint32_t node_bytes;
+    float grid_origin[3], grid_step[3], coord_scale;
+    uint32_t zero;
+};
+static_assert(sizeof(BvhDumpHeader) == 72, "dump header layout");
+
+static int dump_bvh(const char* path, const PrtScene* s, const DNode* nodes, size_t n_nodes, const uint32_t* order,
+                    int stack_need) {
+    BvhDumpHeader h;
+    std::memset(&h, 0, sizeof(h));
+    h.magic = 0x48564250u; // "PBVH"
+    h.version = 1;
+    h.n_tris = s->tris.size();
+    h.n_nodes = n_nodes;
+    h.built_on_device = s->bvh_info.built_on_device;
+    h.depth = s->bvh_info.depth;
+    h.stack_need = stack_need;
+    h.node_bytes = sizeof(DNode);
+    for (int a = 0; a < 3; ++a) {
+        h.grid_origin[a] = s->bvh.grid_origin[a];
+        h.grid_step[a] = s->bvh.grid_step[a];
+    }
+    h.coord_scale = s->bvh.coord_scale;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(PRT_E_INVALID, std::string("PRT_TEST_DUMP_BVH: cannot open ") + path);
+    bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1;
+    ok = ok && std::fwrite(nodes, sizeof(DNode), n_nodes, f) == n_nodes;
+    ok = ok && std::fwrite(order, sizeof(uint32_t), s->tris.size(), f) == s->tris.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? PRT_OK : fail(PRT_E_INVALID, std::string("PRT_TEST_DUMP_BVH: cannot write ") + path);
+}
+
 template <typename T, typename U>
 static void conv_arr(T* o, const U* a, int n) {
     for (int i = 0; i < n; ++i) o[i] = (T)a[i];
@@ -346,6 +388,14 @@ int prt_scene_create(const PrtSceneDesc* desc, PrtScene** out) {
     s->last.bvh_depth = s->bvh.depth;
     s->bvh_info.n_nodes = s->bvh.nodes.size();
     s->bvh_info.depth = s->bvh.depth;
+    if (const char* p = dev_env("PRT_TEST_DUMP_BVH"))
+        if (!s->device_bvh) {
+            const int rc = dump_bvh(p, s, s->bvh.nodes.data(), s->bvh.nodes.size(), s->bvh.order.data(), s->bvh.stack_need);
+            if (rc != PRT_OK) {
+                delete s;
+                return rc;
+            }
+        }
     *out = s;
     return PRT_OK;
 }
@@ -490,6 +540,9 @@ static int upload_impl(PrtScene* s, int device) {
         *out = static_cast<const DTri*>(p);
         return PRT_OK;
     };
+    const char* dump_path = s->device_bvh ? dev_env("PRT_TEST_DUMP_BVH") : nullptr; // (host trees are dumped where they are built)
+    std::vector<DNode> dump_nodes;
+    std::vector<uint32_t> dump_order;
     if (s->device_bvh) {
         std::vector<prt::PrimBox> pb;
         float box_origin[3];
@@ -505,6 +558,16 @@ static int upload_impl(PrtScene* s, int device) {
             if (!prt::validate_nodes(hn.data(), hn.size(), n, &err)) {
                 (void)hipFree(db.d_order);
                 return fail(PRT_E_LIMIT, "prt_scene_upload: device-built BVH is malformed: " + err);
+            }
+        }
+        if (dump_path) { // PRT_TEST_DUMP_BVH: nodes and leaf order come back here, the file is written once the stack need is known
+            dump_nodes.resize(db.n_nodes);
+            dump_order.resize(n);
+            hipError_t e = hipMemcpy(dump_nodes.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(dump_order.data(), db.d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                (void)hipFree(db.d_order);
+                return fail(PRT_E_HIP, std::string("prt_scene_upload: PRT_TEST_DUMP_BVH: ") + hipGetErrorString(e));
             }
         }
         // records go up in description order and are permuted into BVH leaf order in HBM
@@ -652,6 +715,7 @@ static int upload_impl(PrtScene* s, int device) {
             PRT_HIP(hipMemcpy(hn.data(), d.nodes, (size_t)d.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
             need = prt::tree_stack_need(hn.data(), hn.size());
         }
+        if (dump_path && (rc = dump_bvh(dump_path, s, dump_nodes.data(), dump_nodes.size(), dump_order.data(), need))) return rc;
         s->stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH);
         s->d_k3 = d;
         s->d_nodes_shallow = nullptr;
@@ -712,6 +776,10 @@ int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double*
             s->bvh_info.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             s->last.bvh_nodes = s->bvh_info.n_nodes = s->bvh.nodes.size();
             s->last.bvh_depth = s->bvh_info.depth = s->bvh.depth;
+            if (const char* p = dev_env("PRT_TEST_DUMP_BVH")) {
+                const int rc = dump_bvh(p, s, s->bvh.nodes.data(), s->bvh.nodes.size(), s->bvh.order.data(), s->bvh.stack_need);
+                if (rc != PRT_OK) return rc;
+            }
         }
     } catch (const std::bad_alloc&) {
         return fail(PRT_E_OOM, "prt_scene_update_vertices: out of host memory");

@@ -121,7 +121,7 @@ def test_render_multi_rccl_branch_with_one_rank_and_injected_failures(gpu, dev_l
     sc.close()
 
 
-def test_shipped_library_reads_no_environment_hooks(gpu, monkeypatch):
+def test_shipped_library_reads_no_environment_hooks(gpu, monkeypatch, tmp_path):
     """the PRT_TUNE_* / PRT_TEST_* hooks are compiled into libprt_hip_dev.so only.  With the variables set,
     the shipped library uploads (no injected failure), keeps its LDS tables and its packed records, and renders the same
     frame as without them."""
@@ -132,8 +132,11 @@ def test_shipped_library_reads_no_environment_hooks(gpu, monkeypatch):
     for k, v in (("PRT_TEST_FAIL_UPLOAD", "0"), ("PRT_TUNE_TRI_STRIDE", "128"), ("PRT_TUNE_NO_LDS", "1"), ("PRT_TUNE_KEEP", "63"),
                  ("PRT_TUNE_CACHED_MIN", "0"), ("PRT_TUNE_SCRAMBLE", "2"), ("PRT_TEST_FAIL_NCCL", "init"), ("PRT_TEST_FORCE_RCCL", "1")):
         monkeypatch.setenv(k, v)
+    dump = tmp_path / "tree.bin"
+    monkeypatch.setenv("PRT_TEST_DUMP_BVH", str(dump))
     sc = api.Scene(data).upload(gpu)
     assert sc.bvh_info()["tri_stride"] == 96
+    assert not dump.exists()
     assert np.array_equal(sc.render(spp=3, max_depth=5, seed=2), want)
     assert np.array_equal(api.render_multi([sc], spp=3, max_depth=5, seed=2), want.astype(np.float32))
 
