@@ -18,22 +18,29 @@ fixed); every rank renders its tiles into a zero-initialised full-size fp32 fram
 reduce(sum) to rank 0 assembles the image (disjoint tiles => x + 0 + ... + 0: the reduce itself is exact; a share's
 own chunking of the samples makes its fp64 sums differ from the 1-GPU launch's by ~1e-15, invisible in fp32 except
 for about one value in 10^9).  The reduce is inside the timed region; consecutive frames alternate between two HIP streams /
-framebuffers so the next frame fills the GPU while the previous one drains and is being reduced.  After
-the timed region rank 0 renders the frame alone and compares (`assembled_matches_single_rank`, `assembled_exact`), and
-BASELINE config 5 (bathroom2 spp=500 depth=50) is timed the same way (`config5`).
+framebuffers so the next frame fills the GPU while the previous one drains and is being reduced.
 
-Rank 0 prints TWO JSON lines: first the detailed object (every workload's full entry; also written to bench_detail.json),
-then — as the LAST line, the one the driver parses — a compact object of < 4 KB with the contract's keys, `roofline`
-(bound / achieved / peak / unit / frac / traffic as the bench contract defines them), `cpu_baseline`, `parity_check`,
-`checks_ok` and a one-entry-per-workload `workloads_summary`.  Objects of the detailed line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line on rank 0: the contract's
+keys (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data,
+config), nothing else measured and nothing written besides the dump.
+
+`--full` adds, after the timed steps, everything that takes launches or runs of its own.  N>1: rank 0 renders the frame
+alone and compares (`assembled_matches_single_rank`, `assembled_exact`), and BASELINE config 5 (bathroom2 spp=500
+depth=50) is timed the same way (`config5`).  Rank 0 then prints TWO JSON lines: first the detailed object (every
+workload's full entry; also written to bench_detail.json), then — as the LAST line, the one the driver parses — a compact
+object of < 4 KB with the contract's keys, `roofline` (bound / achieved / peak / unit / frac / traffic as the bench
+contract defines them), `cpu_baseline`, `parity_check`, `checks_ok` and a one-entry-per-workload `workloads_summary`.
+Objects of the detailed line:
   roofline      dominant kernel: what bounds it according to the PMC counters of the same build
                 (profiles/pmc_summary.json, separate rocprofv3 --pmc passes), priced with the launch
-                duration measured live with HIP events on the launch stream.
+                duration measured live with HIP events on the launch stream and the per-ray work of a counting launch.
   cpu_baseline  the CPU oracle (port of the reference algorithm, oracle/pt_oracle.cpp) timed on this
                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
   parity_check  the rows the CPU baseline rendered, compared with an fp64 GPU frame of the same
                 configuration (1e-9 per channel); a mismatch makes the bench fail.
   workloads     (N=1) the other single-GPU workloads, each with its own roofline / parity entry.
+  f32 / k4_sorted  (ray workloads) the same batch through the fp32 fast mode and in a locality order, checked against the
+                fp64 hits.
 
 `--dump-outputs DIR` writes what the headline workload's last timed step computed to DIR/<name>.npy (see dump_outputs):
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -441,6 +448,7 @@ def time_render(ctx, name, steps, warmup, spp_override=0, with_cpu=True, cpu_tar
                "config": f"{name} (synthetic stand-in, {data.n_tris} tris, {info['width']}-wide BVH {info['n_nodes']} nodes) "
                          f"{cam.width}x{cam.height} spp={spp} depth={depth} rr=0.8 bSampleLights seed={seed}",
                "tile_size": render_kw["tile_size"], "pipelined": bool(pipelined), "dtype": "f32" if precision else "f64"}
+    if rank == 0 and ctx.args.full:  # checks and figures that take launches of their own
         if nranks > 1:
             # outside the timed region: the reduced framebuffer must equal a single-rank render bit for bit
             assembled = fb.clone()
@@ -539,18 +547,22 @@ def time_rays(ctx, name, steps, warmup, dump_dir=None):
         sel = d_h.index_select(0, torch.from_numpy(idx).cuda()).cpu().numpy()
         sel = sel.view(np.dtype([("t", "<f8"), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"), ("front", "<i4")])).reshape(-1)
         dump_outputs(dump_dir, {"ray_index": idx.astype(np.float64), **{"hit_" + f: sel[f].astype(np.float64) for f in sel.dtype.names}})
+    out = {"workload": name, "value": round(n * steps / elapsed / 1e6, 2), "unit": "Mrays/s", "steps": steps, "warmup": warmup,
+           "ms_per_step": round(elapsed / steps * 1e3, 3), "rays_per_launch": n,
+           "config": f"{name}: {n} seeded {'camera rays in pixel order' if coherent else 'random rays'} vs {data.n_tris} triangles ({info['width']}-wide BVH, {info['n_nodes']} nodes, "
+                     f"depth {info['depth']}, {'GPU' if info['built_on_device'] else 'host'} build, create+upload {build_s:.1f} s)"}
+    if not ctx.args.full:
+        sc.close()
+        return out
+    # --full: checks and figures that take launches of their own
     sc.trace_closest_device(d_r.data_ptr(), n, d_h.data_ptr(), count_work=True)
     torch.cuda.synchronize()
     cc = sc.counters()
     cc["rays_closest"], cc["rays_shadow"] = n, 0
     bpr, npr, tpr, fpr = bytes_per_ray(cc, info)
     hits = d_h.cpu().numpy().view(np.dtype([("t", "<f8"), ("a", "<f8"), ("b", "<f8"), ("prim", "<i4"), ("front", "<i4")])).reshape(-1)
-    out = {"workload": name, "value": round(n * steps / elapsed / 1e6, 2), "unit": "Mrays/s", "steps": steps, "warmup": warmup,
-           "ms_per_step": round(elapsed / steps * 1e3, 3), "rays_per_launch": n,
-           "config": f"{name}: {n} seeded {'camera rays in pixel order' if coherent else 'random rays'} vs {data.n_tris} triangles ({info['width']}-wide BVH, {info['n_nodes']} nodes, "
-                     f"depth {info['depth']}, {'GPU' if info['built_on_device'] else 'host'} build, create+upload {build_s:.1f} s)",
-           "hit_fraction": round(float((hits["prim"] >= 0).mean()), 4),
-           "roofline": roofline(name, "k_trace_closest", bpr, npr, tpr, fpr, n, 0.0, sum(ms) / len(ms), "HIP events around each launch")}
+    out["hit_fraction"] = round(float((hits["prim"] >= 0).mean()), 4)
+    out["roofline"] = roofline(name, "k_trace_closest", bpr, npr, tpr, fpr, n, 0.0, sum(ms) / len(ms), "HIP events around each launch")
     # the same batch through the fp32 fast mode (tolerance tier 2: |dt| / max(1, t) <= 1e-5 against the fp64 kernel's hits)
     d_h32 = torch.zeros_like(d_h)
     sc.trace_closest_device(d_r.data_ptr(), n, d_h32.data_ptr(), precision=1)
@@ -735,6 +747,12 @@ def emit(full):
     print(line, flush=True)
 
 
+def emit_plain(out):
+    """A plain run (no --full): the result line alone, nothing written to disk."""
+    line = json.dumps(out)
+    assert len(line) <= COMPACT_LIMIT, len(line)
+    print(line, flush=True)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -745,8 +763,11 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="override spp (0 = the workload's)")
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64",
                     help="f64 = the reference's arithmetic (default, the headline); f32 = the fp32 fast mode of the same workload (tolerance tier 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline workload only (no `workloads` / `config5` entries)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline, the CPU baseline, the parity / assembly checks and the other "
+                         "workloads (the detailed line + bench_detail.json); a plain run prints only the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline (nor the parity check it feeds)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: headline workload only (no `workloads` / `config5` entries)")
     ap.add_argument("--no-pipeline", action="store_true", help="one stream, one framebuffer: frames strictly back to back")
     ap.add_argument("--pipeline", action="store_true", help="alternate two streams / framebuffers also at N=1 (default: only for N>1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -815,18 +836,22 @@ def main():
         out = {"metric": "Mrays/s (closest-hit, %s rays)" % ("coherent camera" if args.workload.endswith("-coherent") else "incoherent"), "value": w["value"], "unit": "Mrays/s", "n_gpus": 1,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": w["ms_per_step"], "higher_is_better": True,
                "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": w["config"], "hit_fraction": w["hit_fraction"], "rays_per_launch": w["rays_per_launch"]},
-               "roofline": w["roofline"]}
-        for k in ("cpu_baseline", "parity_check", "f32", "k4_sorted"):
-            if k in w:
-                out[k] = w[k]
-        ok = out.get("parity_check", {}).get("ok", True) and out.get("k4_sorted", {}).get("hits_equal_unsorted", True)
-        out["checks_ok"] = bool(ok)
-        emit(out)
+               "config": {"workload": w["config"], "rays_per_launch": w["rays_per_launch"]}}
+        if not args.full:
+            emit_plain(out)
+        else:
+            out["config"]["hit_fraction"] = w["hit_fraction"]
+            out["roofline"] = w["roofline"]
+            for k in ("cpu_baseline", "parity_check", "f32", "k4_sorted"):
+                if k in w:
+                    out[k] = w[k]
+            ok = out.get("parity_check", {}).get("ok", True) and out.get("k4_sorted", {}).get("hits_equal_unsorted", True)
+            out["checks_ok"] = bool(ok)
+            emit(out)
     else:
         w = time_render(ctx, args.workload, args.steps, args.warmup, spp_override=args.spp, dump_dir=args.dump_outputs)
         extras, config5 = [], None
-        if not args.no_extra and args.workload in ("cornell-box", "cornell-box-f32") and args.spp == 0:
+        if args.full and not args.no_extra and args.workload in ("cornell-box", "cornell-box-f32") and args.spp == 0:
             if nranks > 1:
                 # BASELINE config 5: bathroom2 spp 500 depth 50, tiles over the ranks + RCCL reduce
                 config5 = time_render(ctx, "bathroom2-spp500" + ("-f32" if args.precision == "f32" else ""), max(1, min(args.steps, 3)), 1, with_cpu=False)
@@ -837,7 +862,6 @@ def main():
                     else:
                         extras.append(time_render(ctx, name, 2 if name in ("veach-mis", "bathroom2-spp500") else 3, 1, cpu_target_s=3.0))
         if rank == 0:
-            rf = w["roofline"]
             out = {
                 "metric": "Mrays/s (primary+secondary) at fixed spp; s/frame in ms_per_step",
                 "value": w["value"],
@@ -859,23 +883,26 @@ def main():
                     "mpaths_per_s": w["mpaths_per_s"],
                     "rays_per_frame": w["rays_per_frame"],
                     "s_per_frame": round(w["ms_per_step"] / 1e3, 4),
+                    "ray_definition": RAY_DEFINITION,
                 },
-                "roofline": rf,
             }
-            for k in ("cpu_baseline", "parity_check", "assembled_matches_single_rank", "assembled_exact", "assembled_differing_values"):
-                if k in w:
-                    out[k] = w[k]
-            out["config"]["ray_definition"] = RAY_DEFINITION
-            if config5 is not None:
-                out["config5"] = config5
-            checks = [w] + extras + ([config5] if config5 else [])
-            ok = all(x.get("parity_check", {}).get("ok", True) and x.get("assembled_matches_single_rank", True) and
-                     x.get("f32", {}).get("parity_check", {}).get("ok", True) and x.get("k4_sorted", {}).get("hits_equal_unsorted", True) for x in checks)
-            out["checks_ok"] = bool(ok)
-            out["workloads_summary"] = [summary_entry(x) for x in checks]
-            if extras:
-                out["workloads"] = extras
-            emit(out)
+            if not args.full:
+                emit_plain(out)
+            else:
+                out["roofline"] = w["roofline"]
+                for k in ("cpu_baseline", "parity_check", "assembled_matches_single_rank", "assembled_exact", "assembled_differing_values"):
+                    if k in w:
+                        out[k] = w[k]
+                if config5 is not None:
+                    out["config5"] = config5
+                checks = [w] + extras + ([config5] if config5 else [])
+                ok = all(x.get("parity_check", {}).get("ok", True) and x.get("assembled_matches_single_rank", True) and
+                         x.get("f32", {}).get("parity_check", {}).get("ok", True) and x.get("k4_sorted", {}).get("hits_equal_unsorted", True) for x in checks)
+                out["checks_ok"] = bool(ok)
+                out["workloads_summary"] = [summary_entry(x) for x in checks]
+                if extras:
+                    out["workloads"] = extras
+                emit(out)
     if in_group:
         flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device="cpu" if rehearsal else "cuda")
         dist.broadcast(flag, src=0)

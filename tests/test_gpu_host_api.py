@@ -270,16 +270,36 @@ def _bench(args, env_extra, timeout=600):
     if raw:
         # the LAST stdout line is the one the driver parses: compact, with the contract's objects
         assert r.stdout.rstrip().splitlines()[-1] == raw[-1] and len(raw[-1]) < 4096, len(raw[-1])
-        assert {"metric", "value", "unit", "n_gpus", "ms_per_step", "config", "roofline", "checks_ok"} <= set(lines[-1])
-        assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(lines[-1]["roofline"])
+        assert {"metric", "value", "unit", "n_gpus", "ms_per_step", "config"} <= set(lines[-1])
+        if "--full" in args:
+            assert {"roofline", "checks_ok"} <= set(lines[-1])
+            assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(lines[-1]["roofline"])
     return r, lines
+
+
+def test_bench_plain_run_prints_only_the_result_line(gpu, tmp_path):
+    """Without --full the bench times its steps, writes --dump-outputs and prints one result line: no roofline, CPU
+    baseline, parity check or other workload, and no bench_detail.json."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    detail = os.path.join(root, "bench_detail.json")
+    before = os.path.getmtime(detail) if os.path.exists(detail) else None
+    r, lines = _bench(["--steps", "2", "--warmup", "1", "--spp", "4", "--dump-outputs", str(tmp_path / "dump")], {})
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1
+    out = lines[0]
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["unit"] == "Mrays/s"
+    assert not {"roofline", "cpu_baseline", "parity_check", "checks_ok", "workloads", "workloads_summary"} & set(out)
+    fb = np.load(tmp_path / "dump" / "framebuffer.npy")
+    assert fb.shape == (1024, 1024, 3) and fb.dtype == np.float32 and np.isfinite(fb).all() and fb.max() > 0
+    assert (os.path.getmtime(detail) if os.path.exists(detail) else None) == before
 
 
 def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     """`python bench.py --gpus 2` starts its two ranks itself; with PRT_BENCH_REHEARSAL=1 both share this box's one GPU
     and the reduce runs over gloo (RCCL refuses two ranks on one device) — the whole N>1 path except RCCL: tile split,
     two-stream pipelining off, reduce, max-over-ranks timing, the assembled-image check, one JSON line from rank 0."""
-    r, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--spp", "6", "--no-cpu-baseline"], {"PRT_BENCH_REHEARSAL": "1"})
+    r, lines = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--spp", "6", "--no-cpu-baseline"], {"PRT_BENCH_REHEARSAL": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 2  # the detailed object, then the compact line
     out = lines[-1]
@@ -294,7 +314,7 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible(gpu):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible")
-    r, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {}, timeout=900)
+    r, lines = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = lines[-1]
     assert out["n_gpus"] == 2 and out["assembled_matches_single_rank"] is True
@@ -304,9 +324,9 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible(gpu):
 def test_bench_parity_check_fails_the_run_when_pixels_differ(gpu, monkeypatch):
     """bench.py compares the rows its CPU baseline rendered with a GPU frame of the same configuration and must exit
     non-zero on a mismatch: PRT_BENCH_FAULT=1 makes it compare against a deliberately different seed."""
-    r, lines = _bench(["--steps", "1", "--warmup", "0", "--spp", "4", "--no-extra"], {"PRT_BENCH_FAULT": "1"})
+    r, lines = _bench(["--full", "--steps", "1", "--warmup", "0", "--spp", "4", "--no-extra"], {"PRT_BENCH_FAULT": "1"})
     assert r.returncode != 0 and lines and lines[-1]["parity_check"]["ok"] is False and lines[-1]["checks_ok"] is False
-    r, lines = _bench(["--steps", "1", "--warmup", "0", "--spp", "4", "--no-extra"], {})
+    r, lines = _bench(["--full", "--steps", "1", "--warmup", "0", "--spp", "4", "--no-extra"], {})
     pc = lines[-1]["parity_check"]
     cb = lines[-1]["cpu_baseline"]
     # the CPU baseline runs on the fastest worker count of a scan up to the whole affinity mask, and says which
