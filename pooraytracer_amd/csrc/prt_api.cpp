@@ -13,9 +13,11 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "prt_host.h"
@@ -97,17 +99,109 @@ const char* dev_env(const char* name) { return std::getenv(name); }
 #else
 inline const char* dev_env(const char*) { return nullptr; } // (not constexpr: call sites pass the result on to atoi)
 #endif
+
+int hip_fail(const std::string& who, hipError_t e) {
+    return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, who + ": " + hipGetErrorString(e));
+}
+
+// Owners of device memory and events: freed (destroyed) when they go, on whatever device is current then.
+struct HipFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+template <typename T = void>
+using DevBuf = std::unique_ptr<T, HipFree>;
+struct HipHostFree {
+    void operator()(void* p) const { (void)hipHostFree(p); }
+};
+struct EventDestroy {
+    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+using Event = std::unique_ptr<std::remove_pointer<hipEvent_t>::type, EventDestroy>;
+
+template <typename T>
+hipError_t dev_alloc(DevBuf<T>& out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    out.reset(e == hipSuccess ? static_cast<T*>(p) : nullptr);
+    return e;
+}
+hipError_t make_event(Event& out, unsigned flags) {
+    hipEvent_t e = nullptr;
+    const hipError_t r = hipEventCreateWithFlags(&e, flags);
+    out.reset(r == hipSuccess ? e : nullptr);
+    return r;
+}
+
+// A device buffer kept between calls and grown on demand.  A buffer whose users call used() gets a "last user done"
+// event: a later call's stream waits for it first, so the buffer is the previous call's until that call has ended.
+struct Scratch {
+    DevBuf<> p;
+    size_t cap = 0;
+    Event done;
+    // Waits (on st) for the last user, then makes room for `bytes` (hipFree of the old buffer waits for the device).
+    hipError_t reserve(size_t bytes, hipStream_t st) {
+        hipError_t e = done ? hipStreamWaitEvent(st, done.get(), 0) : hipSuccess;
+        if (e != hipSuccess || cap >= bytes) return e;
+        if (done && (e = hipEventSynchronize(done.get())) != hipSuccess) return e;
+        p.reset();
+        cap = 0;
+        if ((e = dev_alloc(p, bytes)) == hipSuccess) cap = bytes;
+        return e;
+    }
+    hipError_t used(hipStream_t st) {
+        const hipError_t e = done ? hipSuccess : make_event(done, hipEventDisableTiming);
+        return e == hipSuccess ? hipEventRecord(done.get(), st) : e;
+    }
+    template <typename T>
+    T* get() const { return static_cast<T*>(p.get()); }
+};
+
+// Device copies of one call's host buffers, freed on every way out.  After the first failure every step is skipped and
+// `e` keeps that failure.
+struct Staging {
+    std::vector<DevBuf<>> bufs;
+    hipError_t e = hipSuccess;
+    void* out(size_t bytes) {
+        DevBuf<> b;
+        if (e == hipSuccess) e = dev_alloc(b, std::max<size_t>(bytes, 16));
+        bufs.push_back(std::move(b));
+        return bufs.back().get();
+    }
+    void* in(const void* src, size_t bytes) { // nullptr in -> nullptr out
+        if (!src) return nullptr;
+        void* d = out(bytes);
+        if (e == hipSuccess) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+        return d;
+    }
+    void sync(hipEvent_t ev = nullptr) { // the device, or the event's work
+        if (e == hipSuccess) e = ev ? hipEventSynchronize(ev) : hipDeviceSynchronize();
+    }
+    void down(void* dst, const void* src, size_t bytes) {
+        if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    }
+    int status(const std::string& who) const { return e == hipSuccess ? PRT_OK : hip_fail(who, e); }
+};
+
+// What the render kernels of one precision get: the scene tables, resident blocks per CU of the plain and the counting
+// instantiation, the light-tree nodes / light triangles / materials staged in LDS (all 0 = the kernels without LDS
+// tables), and the traversal stack entries per lane.
+template <typename R>
+struct KernelConfig {
+    DSceneT<R> d{};
+    int blocks_per_cu[2] = {0, 0};
+    int light_lds = 0, ltri_lds = 0, mat_lds = 0;
+    int stack_depth = PRT_STACK_DEPTH;
+};
 } // namespace
 
 extern "C" int prt_dev_hooks(void) { return PRT_DEV_HOOKS; }
 
-#define PRT_HIP(call)                                                                                   \
+#define PRT_HIP_AS(who, call)                                                                           \
     do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP,                              \
-                        std::string(#call) + ": " + hipGetErrorString(e_));                             \
+        const hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) return hip_fail(who, e_);                                                 \
     } while (0)
+#define PRT_HIP(call) PRT_HIP_AS(#call, call)
 
 struct PrtScene {
     // host side
@@ -130,42 +224,55 @@ struct PrtScene {
     // device side
     int device = -1;
     int n_cu = 0;
-    int blocks_per_cu[2] = {0, 0};
     int blocks_wanted = 0; // what the production kernel's register allocation allows (occupancy without LDS tables)
-    int ltri_lds = 0;
-    int light_lds = 0, mat_lds = 0; // light-tree nodes / materials staged in LDS by K3 (both 0 = the kernels without LDS tables)
     int feat = 0; // material features of the scene (1 textures, 2 Phong, 4 CookTorrance) -> K3 permutation
-    DScene d{};
+    KernelConfig<double> k64;
     // fp32 fast mode: float copies of the tables, made on the first PRT_PRECISION_F32 call (ensure_f32)
-    DSceneT<float> d32{};
+    KernelConfig<float> k32;
     bool f32_ready = false;
-    int blocks_per_cu32[2] = {0, 0};
-    int ltri_lds32 = 0, light_lds32 = 0, mat_lds32 = 0; // table sizes of the fp32 kernels (their own LDS budget)
-    int stack_depth32 = PRT_STACK_DEPTH;                // LDS stack entries per lane of the fp32 render kernels
     int stack_need = PRT_STACK_DEPTH;                   // stack entries a traversal of the resident tree can need at most
-    int stack_depth = PRT_STACK_DEPTH;                  // ... and what the fp64 render kernels get: that, rounded up to a multiple of 4
     const DNode* d_nodes_shallow = nullptr;             // the same binary tree collapsed for PRT_STACK_SHALLOW entries (host build, deep trees), or null
     uint32_t n_nodes_shallow = 0;
-    DScene d_k3{};                                      // the scene as K3 sees it: `d`, on the shallow tree when that buys LDS the kernel needs
-    std::vector<void*> allocs;
+    std::vector<DevBuf<>> allocs;
     // Per-call device state, double-buffered: consecutive calls alternate slots, so a caller that
     // alternates two streams (and two framebuffers) can have frame k+1 filling the GPU while the last
     // long paths of frame k drain — the two launches never share counters, partial sums or events.
     struct CallSlot {
-        DCounters* d_ctr = nullptr;
-        double* d_partial = nullptr;
-        size_t partial_cap = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        hipEvent_t done = nullptr; // recorded behind the last kernel of the call that used this slot
+        DevBuf<DCounters> d_ctr;
+        Scratch partial; // K3's item sums (doubles)
+        Event ev0, ev1;
+        Event done; // recorded behind the last kernel of the call that used this slot
         bool timed = false;
         bool counted = false;
         uint64_t samples = 0; // camera samples of the call (render: owned pixels inside the image x spp; the kernel does not count them)
+        // A call's start: counters cleared, then ev0 (the start of the timed part) ...
+        hipError_t start(hipStream_t st) {
+            const hipError_t e = hipMemsetAsync(d_ctr.get(), 0, sizeof(DCounters), st);
+            return e == hipSuccess ? hipEventRecord(ev0.get(), st) : e;
+        }
+        // ... ev1 (its end) ...
+        hipError_t stop(hipStream_t st) { return hipEventRecord(ev1.get(), st); }
+        // ... and done, behind the call's last kernel.
+        hipError_t finish(hipStream_t st, bool count, uint64_t n) {
+            const hipError_t e = hipEventRecord(done.get(), st);
+            if (e == hipSuccess) {
+                timed = true;
+                counted = count;
+                samples = n;
+            }
+            return e;
+        }
+        // After the counters have been cleared: the pointers K3 reads from them (DCounters::pixel_list / trace).
+        hipError_t set_pointers(hipStream_t st, const void* pixel_list, void* trace) {
+            if (!pixel_list && !trace) return hipSuccess; // zeroed already
+            const void* ptrs[2] = {pixel_list, trace};
+            return hipMemcpyAsync(reinterpret_cast<char*>(d_ctr.get()) + offsetof(DCounters, pixel_list), ptrs, sizeof(ptrs),
+                                  hipMemcpyHostToDevice, st);
+        }
     };
     // prt_trace_closest_sorted_device: K4's keys, values and the permutation — one scratch area per scene, kept between
-    // calls; a call on another stream first waits for the previous sorted call's end (sort_done)
-    void* d_sort = nullptr;
-    size_t sort_cap = 0;
-    hipEvent_t sort_done = nullptr;
+    // calls; a call on another stream first waits for the previous sorted call's end
+    Scratch sort;
     CallSlot slots[2];
     int cur = 0; // slot of the most recent call (prt_get_counters reads it)
     // Next slot for an asynchronous call on `st`.  A slot may still be in use by a call issued two calls ago on
@@ -174,55 +281,48 @@ struct PrtScene {
     CallSlot* next_slot(hipStream_t st, hipError_t* err) {
         cur ^= 1;
         CallSlot& q = slots[cur];
-        *err = q.timed ? hipStreamWaitEvent(st, q.done, 0) : hipSuccess;
+        *err = q.timed ? hipStreamWaitEvent(st, q.done.get(), 0) : hipSuccess;
         return &q;
     }
     PrtCounters last{};
-    float* multi_fb = nullptr; // prt_render_multi: this device's full-size fp32 framebuffer (kept between frames)
-    size_t multi_fb_cap = 0;
+    Scratch multi_fb; // prt_render_multi: this device's full-size fp32 framebuffer (kept between frames)
     // prt_denoise_device: the filter's scratch (prt_denoise.hip), kept between calls; a call waits (on its stream) for the
-    // previous call's end (dn_done) before it reuses it
-    void* d_dn = nullptr;
-    size_t dn_cap = 0;
-    hipEvent_t dn_done = nullptr;
+    // previous call's end before it reuses it
+    Scratch dn;
 
     int fail_upload_at = -1, n_uploads = 0; // test hook (PRT_TEST_FAIL_UPLOAD=k): the k-th table upload reports out-of-memory
+    // One table to the device (at least 256 bytes); `inject`: it counts as an upload for PRT_TEST_FAIL_UPLOAD.
+    int put(const void* src, size_t bytes, DevBuf<>& out, bool inject = true) {
+        if (inject && n_uploads++ == fail_upload_at) return fail(PRT_E_OOM, "prt_scene_upload: injected allocation failure (PRT_TEST_FAIL_UPLOAD)");
+        PRT_HIP_AS("hipMalloc", dev_alloc(out, std::max<size_t>(bytes, 256)));
+        if (bytes) PRT_HIP(hipMemcpy(out.get(), src, bytes, hipMemcpyHostToDevice));
+        return PRT_OK;
+    }
     template <typename T>
-    int up(const std::vector<T>& v, const T** out) {
-        if (n_uploads++ == fail_upload_at) return fail(PRT_E_OOM, "prt_scene_upload: injected allocation failure (PRT_TEST_FAIL_UPLOAD)");
-        void* p = nullptr;
-        size_t bytes = std::max<size_t>(v.size() * sizeof(T), 256);
-        PRT_HIP(hipMalloc(&p, bytes));
-        allocs.push_back(p);
-        if (!v.empty()) PRT_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        *out = reinterpret_cast<const T*>(p);
+    int up(const std::vector<T>& v, const T** out, bool inject = true) {
+        DevBuf<> p;
+        if (int rc = put(v.data(), v.size() * sizeof(T), p, inject)) return rc;
+        *out = static_cast<const T*>(p.get());
+        allocs.push_back(std::move(p));
+        return PRT_OK;
+    }
+    // A device array that lives as long as the upload (at least 256 bytes).
+    int alloc(size_t bytes, void** out) {
+        DevBuf<> p;
+        PRT_HIP_AS("hipMalloc", dev_alloc(p, std::max<size_t>(bytes, 256)));
+        *out = p.get();
+        allocs.push_back(std::move(p));
         return PRT_OK;
     }
     void release() {
         if (device >= 0) (void)hipSetDevice(device);
-        for (void* p : allocs) (void)hipFree(p);
         allocs.clear();
-        if (multi_fb) (void)hipFree(multi_fb);
-        multi_fb = nullptr;
-        multi_fb_cap = 0;
-        if (d_sort) (void)hipFree(d_sort);
-        d_sort = nullptr;
-        sort_cap = 0;
-        if (d_dn) (void)hipFree(d_dn);
-        d_dn = nullptr;
-        dn_cap = 0;
-        if (dn_done) (void)hipEventDestroy(dn_done);
-        dn_done = nullptr;
-        if (sort_done) (void)hipEventDestroy(sort_done);
-        sort_done = nullptr;
-        for (CallSlot& q : slots) {
-            if (q.d_ctr) (void)hipFree(q.d_ctr);
-            if (q.d_partial) (void)hipFree(q.d_partial);
-            if (q.ev0) (void)hipEventDestroy(q.ev0);
-            if (q.ev1) (void)hipEventDestroy(q.ev1);
-            if (q.done) (void)hipEventDestroy(q.done);
-            q = CallSlot();
-        }
+        multi_fb = Scratch();
+        sort = Scratch();
+        dn = Scratch();
+        for (CallSlot& q : slots) q = CallSlot();
+        k64 = KernelConfig<double>();
+        k32 = KernelConfig<float>();
         device = -1;
         f32_ready = false;
     }
@@ -273,6 +373,144 @@ static int dump_bvh(const char* path, const PrtScene* s, const DNode* nodes, siz
 template <typename T, typename U>
 static void conv_arr(T* o, const U* a, int n) {
     for (int i = 0; i < n; ++i) o[i] = (T)a[i];
+}
+
+// How much of the material table, the light triangles and the light tree a render kernel stages in LDS, given the
+// bytes a block may spend on them (record sizes differ between the fp64 and the fp32 kernels).
+static void size_tables(const PrtScene* s, int budget, size_t mat_bytes, size_t ltri_bytes, size_t lnode_bytes, int* mat, int* ltri, int* light) {
+    *mat = *ltri = *light = 0;
+    const bool off = dev_env("PRT_TUNE_NO_LDS") && std::atoi(dev_env("PRT_TUNE_NO_LDS"));
+    if (off || s->mats.empty() || s->mats.size() * mat_bytes > 8192 || (int)(s->mats.size() * mat_bytes) > budget) return;
+    *mat = (int)s->mats.size();
+    budget -= *mat * (int)mat_bytes;
+    if (!s->lights.tris.empty() && s->lights.tris.size() <= 32 && (int)(s->lights.tris.size() * ltri_bytes) <= budget) {
+        *ltri = (int)s->lights.tris.size();
+        budget -= *ltri * (int)ltri_bytes;
+    }
+    *light = (int)std::min<size_t>(s->lights.nodes.size(), (size_t)(std::max(budget, 0) / (int)lnode_bytes));
+    if (const char* e = dev_env("PRT_TUNE_LIGHT_LDS")) *light = std::min(*light, std::max(0, std::atoi(e)));
+    if (const char* e = dev_env("PRT_TUNE_LTRI_LDS")) if (!std::atoi(e)) *ltri = 0;
+}
+
+// LDS tables and resident blocks per CU of the render kernels of one precision, for stacks of k.stack_depth entries.
+// drop_tables: render without the tables when they would cost the production kernel a resident block (the budget is an
+// estimate; the occupancy query is the truth).  Returns the blocks per CU without the tables (with drop_tables; else
+// blocks_per_cu[0]).
+template <typename R>
+static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables) {
+    constexpr bool f64 = std::is_same<R, double>::value;
+    const auto lds_budget = f64 ? prt::render_lds_budget : prt32::render_lds_budget;
+    const auto table_bytes = f64 ? prt::render_table_bytes : prt32::render_table_bytes;
+    const auto blocks_per_cu = f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu;
+    size_tables(s, lds_budget(s->feat, k.stack_depth), sizeof(DMaterialT<R>), sizeof(DLightTriT<R>), sizeof(DLightNodeT<R>),
+                &k.mat_lds, &k.ltri_lds, &k.light_lds);
+    const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
+    const bool extra = !s->lights.tab.empty() || k.d.tex_compact != 0;
+    auto blocks = [&](bool count, size_t tables) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra); };
+    const size_t tables = table_bytes(k.light_lds, k.mat_lds, k.ltri_lds);
+    k.blocks_per_cu[0] = blocks(false, tables);
+    const int wanted = drop_tables && tables != 0 ? blocks(false, 0) : k.blocks_per_cu[0];
+    if (k.blocks_per_cu[0] < wanted) { // a block per CU is worth far more than the tables
+        k.mat_lds = k.ltri_lds = k.light_lds = 0;
+        k.blocks_per_cu[0] = wanted;
+    }
+    k.blocks_per_cu[1] = blocks(true, table_bytes(k.light_lds, k.mat_lds, k.ltri_lds));
+    if (dev_env("PRT_TUNE_VERBOSE")) {
+        if (f64)
+            std::fprintf(stderr, "[prt] fp64 render kernels: %d blocks per CU, LDS tables: %d materials, %d light triangles, %d light nodes\n",
+                         k.blocks_per_cu[0], k.mat_lds, k.ltri_lds, k.light_lds);
+        else
+            std::fprintf(stderr, "[prt] fp32 render kernels: %d blocks per CU, stacks %d, LDS tables: %d materials, %d light triangles, %d light nodes\n",
+                         k.blocks_per_cu[0], k.stack_depth, k.mat_lds, k.ltri_lds, k.light_lds);
+    }
+    return wanted;
+}
+
+// The host's tile layout of a frame (the device has its own copy: tile_pixel in prt_device.h).  tile_size 0 means 32, and
+// the tile is rounded up to a multiple of 8 (at least 8); tiles are dealt round-robin over the ranks in row-major order,
+// and tile row ty is rotated by 3 * ty.
+struct TileLayout {
+    int width, height, tile, tiles_x, tiles_y, n_tiles, rank, nranks, owned_tiles;
+    uint64_t items_per_chunk; // owned_tiles * tile * tile
+    TileLayout(const PrtCamera& c, const PrtRenderParams& p) : width(c.width), height(c.height), rank(p.rank), nranks(p.nranks) {
+        tile = p.tile_size > 0 ? p.tile_size : 32;
+        tile = std::max(8, (tile + 7) / 8 * 8);
+        tiles_x = (width + tile - 1) / tile;
+        tiles_y = (height + tile - 1) / tile;
+        n_tiles = tiles_x * tiles_y;
+        owned_tiles = n_tiles > rank ? (n_tiles - rank + nranks - 1) / nranks : 0;
+        items_per_chunk = (uint64_t)owned_tiles * tile * tile;
+    }
+    // Pixel (x, y) lies in one of this rank's tiles.
+    bool owns(int x, int y) const {
+        const int tx = x / tile, ty = y / tile;
+        const int kx = ((tx - 3 * ty) % tiles_x + tiles_x) % tiles_x;
+        return (ty * tiles_x + kx) % nranks == rank;
+    }
+    // The pixels of this rank's tiles that lie inside the image.
+    uint64_t owned_pixels() const {
+        uint64_t px = 0;
+        for (int k = rank; k < n_tiles; k += nranks) {
+            const int ty = k / tiles_x, tx = (k - ty * tiles_x + 3 * ty) % tiles_x;
+            px += (uint64_t)std::max(0, std::min(tile, width - tx * tile)) * (uint64_t)std::max(0, std::min(tile, height - ty * tile));
+        }
+        return px;
+    }
+    void set(DRenderParams& P) const {
+        P.tile = tile; P.tiles_x = tiles_x; P.tiles_y = tiles_y; P.n_tiles = n_tiles;
+        P.rank = rank; P.nranks = nranks; P.owned_tiles = owned_tiles; P.items_per_chunk = items_per_chunk;
+    }
+};
+
+// What every K3 launch of the scene shares (render_impl, prt_render_samples); the callers set the samples, tiles, items
+// and chunks of their launch.
+static DRenderParams base_params(const PrtScene* s, const PrtRenderParams* p) {
+    DRenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.max_depth = p->max_depth;
+    P.sample_lights = p->sample_lights ? 1 : 0;
+    P.rr = p->russian_roulette;
+    P.inv_rr = 1.0 / p->russian_roulette;
+    // wave scheduling thresholds: measured optima at the BASELINE spp with 4-wide nodes (flat within 2 %): lean 28 / 48 / 20,
+    // others 20 / 40 / 12; the Phong permutations at three waves: leaf batch 32 (round 4, two sweeps and a four-fold A/B on
+    // veach-mis: -0.75 %)
+    P.keep = s->feat == 0 ? 28 : 20;
+    P.leaf_batch = s->feat == 0 ? 48 : (s->feat & 2) ? 32 : 40; // (2 = Phong, as in s->feat above)
+    P.inner_min = s->feat == 0 ? 20 : 12;
+    for (int c = 0; c < 3; ++c) P.background[c] = p->background[c];
+    P.seed_key = prt::seed_key(p->seed); // the seed is hashed on its own, once per launch (prt_device.h, Rng)
+    P.jitter = p->pixel_jitter ? 1 : 0;
+    P.light_lds = s->k64.light_lds;
+    P.mat_lds = s->k64.mat_lds;
+    P.ltri_lds = s->k64.ltri_lds;
+    P.stack_depth = PRT_STACK_DEPTH;
+    return P;
+}
+
+// The same launch for the fp32 kernels: reals rounded from the fp64 values, the fp32 kernels' own LDS tables and stacks.
+static DRenderParamsT<float> to_f32(const DRenderParams& P, const KernelConfig<float>& k) {
+    static_assert(sizeof(DRenderParamsT<float>) == 400, "DRenderParamsT changed: convert its new fields here");
+    DRenderParamsT<float> o;
+    std::memset(&o, 0, sizeof(o));
+    o.spp = P.spp; o.max_depth = P.max_depth; o.sample_lights = P.sample_lights; o.chunks = P.chunks;
+    o.rr = (float)P.rr; o.inv_rr = (float)P.inv_rr;
+    conv_arr(o.background, P.background, 3);
+    o.seed_key = P.seed_key;
+    o.tile = P.tile; o.tiles_x = P.tiles_x; o.tiles_y = P.tiles_y; o.n_tiles = P.n_tiles;
+    o.rank = P.rank; o.nranks = P.nranks; o.owned_tiles = P.owned_tiles; o.jitter = P.jitter;
+    o.keep = P.keep; o.leaf_batch = P.leaf_batch; o.inner_min = P.inner_min; o.scramble = P.scramble; o.cached_min = P.cached_min;
+    o.light_lds = k.light_lds; o.mat_lds = k.mat_lds; o.ltri_lds = k.ltri_lds;
+    o.stack_depth = k.stack_depth;
+    o.items_per_chunk = P.items_per_chunk; o.n_items = P.n_items;
+    std::memcpy(o.chunk_begin, P.chunk_begin, sizeof(P.chunk_begin));
+    return o;
+}
+static DCameraT<float> to_f32(const DCamera& C) {
+    DCameraT<float> o;
+    conv_arr(o.center, C.center, 3); conv_arr(o.pixel00, C.pixel00, 3);
+    conv_arr(o.du, C.du, 3); conv_arr(o.dv, C.dv, 3);
+    o.width = C.width; o.height = C.height;
+    return o;
 }
 
 extern "C" {
@@ -412,16 +650,16 @@ int prt_scene_bvh_info(const PrtScene* s, PrtBvhInfo* out) {
     out->node_bytes = (uint32_t)sizeof(DNode);
     out->width = PRT_BVH_WIDTH;
     out->tri_bytes = (uint32_t)sizeof(DTri);
-    out->tri_stride = s->device >= 0 ? s->d.tri_stride : 0u;
+    out->tri_stride = s->device >= 0 ? s->k64.d.tri_stride : 0u;
     out->texture_bytes = s->device >= 0 ? (uint64_t)s->n_texel_reals * sizeof(double) : 0u;
     out->texture_footprint_bytes = s->device >= 0 ? (uint64_t)s->tex_footprint_bytes : 0u;
     out->texture_layouts = s->device >= 0 ? s->tex_layouts : 0u;
     const bool up = s->device >= 0;
-    out->render_blocks_per_cu = up ? (uint32_t)s->blocks_per_cu[0] : 0u;
+    out->render_blocks_per_cu = up ? (uint32_t)s->k64.blocks_per_cu[0] : 0u;
     out->render_blocks_wanted = up ? (uint32_t)s->blocks_wanted : 0u;
-    out->lds_materials = up ? (uint32_t)s->mat_lds : 0u;
-    out->lds_light_nodes = up ? (uint32_t)s->light_lds : 0u;
-    out->lds_light_tris = up ? (uint32_t)s->ltri_lds : 0u;
+    out->lds_materials = up ? (uint32_t)s->k64.mat_lds : 0u;
+    out->lds_light_nodes = up ? (uint32_t)s->k64.light_lds : 0u;
+    out->lds_light_tris = up ? (uint32_t)s->k64.ltri_lds : 0u;
     out->stack_need = up ? (uint32_t)s->stack_need : 0u;
     out->reserved_ = 0;
     return PRT_OK;
@@ -441,23 +679,6 @@ int prt_scene_light_order(const PrtScene* s, int32_t* prims, uint64_t cap) {
 }
 
 static int upload_impl(PrtScene* s, int device);
-
-// How much of the material table, the light triangles and the light tree a render kernel stages in LDS, given the
-// bytes a block may spend on them (record sizes differ between the fp64 and the fp32 kernels).
-static void size_tables(const PrtScene* s, int budget, size_t mat_bytes, size_t ltri_bytes, size_t lnode_bytes, int* mat, int* ltri, int* light) {
-    *mat = *ltri = *light = 0;
-    const bool off = dev_env("PRT_TUNE_NO_LDS") && std::atoi(dev_env("PRT_TUNE_NO_LDS"));
-    if (off || s->mats.empty() || s->mats.size() * mat_bytes > 8192 || (int)(s->mats.size() * mat_bytes) > budget) return;
-    *mat = (int)s->mats.size();
-    budget -= *mat * (int)mat_bytes;
-    if (!s->lights.tris.empty() && s->lights.tris.size() <= 32 && (int)(s->lights.tris.size() * ltri_bytes) <= budget) {
-        *ltri = (int)s->lights.tris.size();
-        budget -= *ltri * (int)ltri_bytes;
-    }
-    *light = (int)std::min<size_t>(s->lights.nodes.size(), (size_t)(std::max(budget, 0) / (int)lnode_bytes));
-    if (const char* e = dev_env("PRT_TUNE_LIGHT_LDS")) *light = std::min(*light, std::max(0, std::atoi(e)));
-    if (const char* e = dev_env("PRT_TUNE_LTRI_LDS")) if (!std::atoi(e)) *ltri = 0;
-}
 
 // Either the whole scene is resident afterwards, or nothing is: a failure anywhere (allocation, copy, device build)
 // releases what was uploaded so far and leaves the scene in the not-uploaded state (device = -1), so that no later
@@ -512,8 +733,7 @@ static int upload_impl(PrtScene* s, int device) {
         b.material = T.material;
         b.prim = T.prim;
     }
-    DScene& d = s->d;
-    std::memset(&d, 0, sizeof(d));
+    DScene& d = s->k64.d;
     int rc;
     // packed records for scenes the caches hold, one record per 128-byte line for scenes that stream from HBM
     uint32_t stride = (uint64_t)n * sizeof(DTri) > PRT_TRI_PADDED_ABOVE ? 128u : (uint32_t)sizeof(DTri);
@@ -523,8 +743,7 @@ static int upload_impl(PrtScene* s, int device) {
     auto up_tris = [&](const DTri** out) -> int { // host records (packed) -> device records `stride` bytes apart
         if (stride == sizeof(DTri)) return s->up(dt, out);
         void* p = nullptr;
-        PRT_HIP(hipMalloc(&p, std::max<size_t>(n * (size_t)stride, 256)));
-        s->allocs.push_back(p);
+        if (int rc = s->alloc(n * (size_t)stride, &p)) return rc;
         if (n) {
             // the padded array is laid out on the host and goes up in one copy (a 2-D copy of millions of 96-byte rows
             // from pageable memory is served row by row)
@@ -550,54 +769,33 @@ static int upload_impl(PrtScene* s, int device) {
         prt::DeviceBVH db;
         std::string err;
         if (!prt::build_bvh_device(pb.data(), box_origin, n, db, &err)) return fail(PRT_E_HIP, "prt_scene_upload: " + err);
-        s->allocs.push_back(db.d_nodes);
+        s->allocs.emplace_back(db.d_nodes);
+        const DevBuf<> order(db.d_order); // the leaf order is needed only for the gather below
         d.nodes = db.d_nodes;
         if (dev_env("PRT_VALIDATE_BVH")) { // tests: check the device-built tree on the host before any ray visits it
             std::vector<DNode> hn(db.n_nodes);
             PRT_HIP(hipMemcpy(hn.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
-            if (!prt::validate_nodes(hn.data(), hn.size(), n, &err)) {
-                (void)hipFree(db.d_order);
+            if (!prt::validate_nodes(hn.data(), hn.size(), n, &err))
                 return fail(PRT_E_LIMIT, "prt_scene_upload: device-built BVH is malformed: " + err);
-            }
         }
         if (dump_path) { // PRT_TEST_DUMP_BVH: nodes and leaf order come back here, the file is written once the stack need is known
             dump_nodes.resize(db.n_nodes);
             dump_order.resize(n);
-            hipError_t e = hipMemcpy(dump_nodes.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(dump_order.data(), db.d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) {
-                (void)hipFree(db.d_order);
-                return fail(PRT_E_HIP, std::string("prt_scene_upload: PRT_TEST_DUMP_BVH: ") + hipGetErrorString(e));
-            }
+            PRT_HIP_AS("prt_scene_upload: PRT_TEST_DUMP_BVH",
+                       hipMemcpy(dump_nodes.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
+            PRT_HIP_AS("prt_scene_upload: PRT_TEST_DUMP_BVH", hipMemcpy(dump_order.data(), db.d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         }
-        // records go up in description order and are permuted into BVH leaf order in HBM
-        const DTri* t_in = nullptr;
-        const DTriShade* s_in = nullptr;
+        // records go up in description order (staging copies, freed at the end of this block) and are permuted into BVH
+        // leaf order in HBM
+        DevBuf<> t_in, s_in;
         void *t_out = nullptr, *s_out = nullptr;
-        const size_t mark = s->allocs.size();
-        rc = s->up(dt, &t_in);
-        if (!rc) rc = s->up(ds, &s_in);
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            e = hipMalloc(&t_out, n * (size_t)stride);
-            if (e == hipSuccess) { s->allocs.push_back(t_out); e = hipMalloc(&s_out, n * sizeof(DTriShade)); }
-            if (e == hipSuccess) {
-                s->allocs.push_back(s_out);
-                prt::launch_gather_tris(t_in, s_in, db.d_order, (uint32_t)n, t_out, stride,
-                                        static_cast<DTriShade*>(s_out), nullptr);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipDeviceSynchronize();
-            }
-        }
-        (void)hipFree(db.d_order);
-        // drop the two staging copies (they sit at allocs[mark], allocs[mark+1] when their upload succeeded)
-        for (const void* p : {static_cast<const void*>(t_in), static_cast<const void*>(s_in)})
-            if (p) {
-                (void)hipFree(const_cast<void*>(p));
-                s->allocs.erase(std::find(s->allocs.begin() + mark, s->allocs.end(), const_cast<void*>(p)));
-            }
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_scene_upload: ") + hipGetErrorString(e));
+        if ((rc = s->put(dt.data(), n * sizeof(DTri), t_in)) || (rc = s->put(ds.data(), n * sizeof(DTriShade), s_in)) ||
+            (rc = s->alloc(n * (size_t)stride, &t_out)) || (rc = s->alloc(n * sizeof(DTriShade), &s_out)))
+            return rc;
+        prt::launch_gather_tris(static_cast<const DTri*>(t_in.get()), static_cast<const DTriShade*>(s_in.get()), db.d_order,
+                                (uint32_t)n, t_out, stride, static_cast<DTriShade*>(s_out), nullptr);
+        PRT_HIP_AS("prt_scene_upload", hipGetLastError());
+        PRT_HIP_AS("prt_scene_upload", hipDeviceSynchronize());
         d.tris = static_cast<const DTri*>(t_out);
         d.shade = static_cast<const DTriShade*>(s_out);
         s->bvh.depth = db.depth;
@@ -687,11 +885,11 @@ static int upload_impl(PrtScene* s, int device) {
         d.slab_scale = std::nextafter((float)e, std::numeric_limits<float>::infinity());
     }
     for (PrtScene::CallSlot& q : s->slots) {
-        PRT_HIP(hipMalloc(reinterpret_cast<void**>(&q.d_ctr), sizeof(DCounters)));
-        PRT_HIP(hipMemset(q.d_ctr, 0, sizeof(DCounters)));
-        PRT_HIP(hipEventCreate(&q.ev0));
-        PRT_HIP(hipEventCreate(&q.ev1));
-        PRT_HIP(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        PRT_HIP_AS("hipMalloc", dev_alloc(q.d_ctr, sizeof(DCounters)));
+        PRT_HIP(hipMemset(q.d_ctr.get(), 0, sizeof(DCounters)));
+        PRT_HIP(make_event(q.ev0, hipEventDefault));
+        PRT_HIP(make_event(q.ev1, hipEventDefault));
+        PRT_HIP(make_event(q.done, hipEventDisableTiming));
     }
     s->feat = 0;
     for (const DMaterial& m : s->mats) {
@@ -717,34 +915,17 @@ static int upload_impl(PrtScene* s, int device) {
         }
         if (dump_path && (rc = dump_bvh(dump_path, s, dump_nodes.data(), dump_nodes.size(), dump_order.data(), need))) return rc;
         s->stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH);
-        s->d_k3 = d;
         s->d_nodes_shallow = nullptr;
         s->n_nodes_shallow = 0;
         // The fp64 render kernels keep STATIC stacks of PRT_STACK_DEPTH entries per lane (they are register-limited to three
         // blocks per CU; a run-time depth cost them 1.2 %), so a shallower collapse of the tree frees them no LDS: they
         // always traverse the full tree, and their table budget is what those static stacks leave.  (The fp32 kernels size
-        // their stacks per launch and do take the 32-entry collapse of a deep host-built tree: upload_f32_tables.)
-        s->stack_depth = PRT_STACK_DEPTH;
+        // their stacks per launch and do take the 32-entry collapse of a deep host-built tree: ensure_f32.)
         if (dev_env("PRT_TUNE_VERBOSE")) std::fprintf(stderr, "[prt] tree needs %d stack entries\n", s->stack_need);
     }
-    size_tables(s, prt::render_lds_budget(s->feat, s->stack_depth), sizeof(DMaterial), sizeof(DLightTri), sizeof(DLightNode),
-                &s->mat_lds, &s->ltri_lds, &s->light_lds);
     static_assert(sizeof(DLightNode) == 16 && sizeof(DLightTri) % 16 == 0, "LDS staging copies 16-byte pieces");
-    const size_t tables = prt::render_table_bytes(s->light_lds, s->mat_lds, s->ltri_lds);
-    const bool pad = d.tri_stride == PRT_TRI_PAD_STRIDE(double) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(double);
-    s->blocks_per_cu[0] = prt::render_blocks_per_cu(false, s->feat, tables, s->stack_depth, pad, !s->lights.tab.empty() || s->d.tex_compact != 0);
-    s->blocks_wanted = tables != 0 ? prt::render_blocks_per_cu(false, s->feat, 0, s->stack_depth, pad, !s->lights.tab.empty() || s->d.tex_compact != 0) : s->blocks_per_cu[0];
-    if (s->blocks_per_cu[0] < s->blocks_wanted) {
-        // the tables would cost the production kernel a resident block (the budget is an estimate; the occupancy query is
-        // the truth): a block per CU is worth far more than the tables — render without them
-        s->mat_lds = s->ltri_lds = s->light_lds = 0;
-        s->blocks_per_cu[0] = s->blocks_wanted;
-    }
-    const size_t tables_used = prt::render_table_bytes(s->light_lds, s->mat_lds, s->ltri_lds);
-    s->blocks_per_cu[1] = prt::render_blocks_per_cu(true, s->feat, tables_used, s->stack_depth, pad, !s->lights.tab.empty() || s->d.tex_compact != 0);
-    if (dev_env("PRT_TUNE_VERBOSE"))
-        std::fprintf(stderr, "[prt] fp64 render kernels: %d blocks per CU, LDS tables: %d materials, %d light triangles, %d light nodes\n",
-                     s->blocks_per_cu[0], s->mat_lds, s->ltri_lds, s->light_lds);
+    // the fp64 kernels render without their LDS tables when the tables would cost a resident block (the fp32 ones do not)
+    s->blocks_wanted = size_kernels(s, s->k64, true);
     return PRT_OK;
 }
 
@@ -799,26 +980,23 @@ static int ensure_f32(PrtScene* s) {
     const int rc = ensure_f32_impl(s);
     if (rc != PRT_OK) {
         const std::string keep = g_err;
-        for (size_t i = mark; i < s->allocs.size(); ++i) (void)hipFree(s->allocs[i]);
         s->allocs.resize(mark);
-        std::memset(&s->d32, 0, sizeof(s->d32));
+        s->k32 = KernelConfig<float>();
         g_err = keep;
     }
     return rc;
 }
 static int ensure_f32_impl(PrtScene* s) {
-    const DScene& d = s->d;
-    DSceneT<float>& f = s->d32;
-    std::memset(&f, 0, sizeof(f));
+    const DScene& d = s->k64.d;
+    KernelConfig<float>& k = s->k32;
+    DSceneT<float>& f = k.d;
     const size_t n = d.n_tris;
     const uint32_t stride = d.tri_stride == sizeof(DTriT<double>) ? (uint32_t)sizeof(DTriT<float>) : PRT_TRI_PAD_STRIDE(float);
     void *t = nullptr, *sh = nullptr, *tx = nullptr;
-    PRT_HIP(hipMalloc(&t, std::max<size_t>(n * (size_t)stride, 256)));
-    s->allocs.push_back(t);
-    PRT_HIP(hipMalloc(&sh, std::max<size_t>(n * sizeof(DTriShadeT<float>), 256)));
-    s->allocs.push_back(sh);
-    PRT_HIP(hipMalloc(&tx, std::max<size_t>(s->n_texel_reals * sizeof(float), 256)));
-    s->allocs.push_back(tx);
+    int rc;
+    if ((rc = s->alloc(n * (size_t)stride, &t)) || (rc = s->alloc(n * sizeof(DTriShadeT<float>), &sh)) ||
+        (rc = s->alloc(s->n_texel_reals * sizeof(float), &tx)))
+        return rc;
     prt32::launch_convert_tris(d.tris, d.tri_stride, (uint32_t)n, t, stride, nullptr);
     prt32::launch_convert_shade(d.shade, (uint32_t)n, static_cast<DTriShadeT<float>*>(sh), nullptr);
     prt32::launch_convert_reals(d.texels_lin, s->n_texel_reals, static_cast<float*>(tx), nullptr);
@@ -851,14 +1029,9 @@ static int ensure_f32_impl(PrtScene* s) {
         conv_arr(o.v0, a.v0, 3); conv_arr(o.v1, a.v1, 3); conv_arr(o.v2, a.v2, 3); conv_arr(o.n, a.n, 3);
         o.area = (float)a.area; o.material = a.material; o.prim = a.prim; o.pdf = (float)a.pdf;
     }
-    int rc;
-    const int keep_fail = s->fail_upload_at;
-    s->fail_upload_at = -1;
-    if ((rc = s->up(mats, &f.materials)) || (rc = s->up(ln, &f.light_nodes)) || (rc = s->up(lt, &f.light_tris))) {
-        s->fail_upload_at = keep_fail;
+    // (these uploads do not count for PRT_TEST_FAIL_UPLOAD, which injects failures into prt_scene_upload)
+    if ((rc = s->up(mats, &f.materials, false)) || (rc = s->up(ln, &f.light_nodes, false)) || (rc = s->up(lt, &f.light_tris, false)))
         return rc;
-    }
-    s->fail_upload_at = keep_fail;
     PRT_HIP(hipDeviceSynchronize());
     f.nodes = d.nodes;
     f.tris = static_cast<const DTriT<float>*>(t);
@@ -886,11 +1059,7 @@ static int ensure_f32_impl(PrtScene* s) {
         if (need > PRT_STACK_SHALLOW && !s->d_nodes_shallow && !s->bvh_info.built_on_device && !s->bvh.nodes_shallow.empty()) {
             // the same binary tree collapsed for 32 entries (same leaf order: the records above fit both): the fp32 kernels
             // have the registers for a fourth block per CU, which 32-entry stacks leave the LDS for
-            const int keep = s->fail_upload_at;
-            s->fail_upload_at = -1;
-            rc = s->up(s->bvh.nodes_shallow, &s->d_nodes_shallow);
-            s->fail_upload_at = keep;
-            if (rc) return rc;
+            if ((rc = s->up(s->bvh.nodes_shallow, &s->d_nodes_shallow, false))) return rc;
             s->n_nodes_shallow = (uint32_t)s->bvh.nodes_shallow.size();
         }
         if (s->d_nodes_shallow) {
@@ -898,28 +1067,12 @@ static int ensure_f32_impl(PrtScene* s) {
             f.n_nodes = s->n_nodes_shallow;
             need = std::min(need, PRT_STACK_SHALLOW);
         }
-        s->stack_depth32 = need <= PRT_STACK_SHALLOW ? PRT_STACK_SHALLOW : PRT_STACK_DEPTH;
-        if (const char* e = dev_env("PRT_TUNE_STACK32")) s->stack_depth32 = std::max(need, std::min(PRT_STACK_DEPTH, std::atoi(e))); // developer: smaller stacks when the tree allows
-        if (dev_env("PRT_TUNE_VERBOSE")) std::fprintf(stderr, "[prt] fp32 tables: tree needs %d stack entries, using %d\n", need, s->stack_depth32);
+        k.stack_depth = need <= PRT_STACK_SHALLOW ? PRT_STACK_SHALLOW : PRT_STACK_DEPTH;
+        if (const char* e = dev_env("PRT_TUNE_STACK32")) k.stack_depth = std::max(need, std::min(PRT_STACK_DEPTH, std::atoi(e))); // developer: smaller stacks when the tree allows
+        if (dev_env("PRT_TUNE_VERBOSE")) std::fprintf(stderr, "[prt] fp32 tables: tree needs %d stack entries, using %d\n", need, k.stack_depth);
     }
-    size_tables(s, prt32::render_lds_budget(s->feat, s->stack_depth32), sizeof(DMaterialT<float>), sizeof(DLightTriT<float>),
-                sizeof(DLightNodeT<float>), &s->mat_lds32, &s->ltri_lds32, &s->light_lds32);
-    const size_t tables = prt32::render_table_bytes(s->light_lds32, s->mat_lds32, s->ltri_lds32);
-    const bool pad = stride == PRT_TRI_PAD_STRIDE(float) && sizeof(DTriT<float>) != PRT_TRI_PAD_STRIDE(float);
-    s->blocks_per_cu32[0] = prt32::render_blocks_per_cu(false, s->feat, tables, s->stack_depth32, pad, !s->lights.tab.empty() || s->d.tex_compact != 0);
-    s->blocks_per_cu32[1] = prt32::render_blocks_per_cu(true, s->feat, tables, s->stack_depth32, pad, !s->lights.tab.empty() || s->d.tex_compact != 0);
-    if (dev_env("PRT_TUNE_VERBOSE"))
-        std::fprintf(stderr, "[prt] fp32 render kernels: %d blocks per CU, stacks %d, LDS tables: %d materials, %d light triangles, %d light nodes\n",
-                     s->blocks_per_cu32[0], s->stack_depth32, s->mat_lds32, s->ltri_lds32, s->light_lds32);
+    size_kernels(s, k, false); // the fp32 kernels keep their LDS tables whatever they cost in occupancy
     s->f32_ready = true;
-    return PRT_OK;
-}
-
-// After the counters of a call slot have been zeroed: the pointers K3 reads from them (DCounters::pixel_list / trace).
-static int set_slot_pointers(PrtScene*, PrtScene::CallSlot& q, hipStream_t st, unsigned, const void* pixel_list, void* trace) {
-    if (!pixel_list && !trace) return PRT_OK; // zeroed already
-    const void* ptrs[2] = {pixel_list, trace};
-    PRT_HIP(hipMemcpyAsync(reinterpret_cast<char*>(q.d_ctr) + offsetof(DCounters, pixel_list), ptrs, sizeof(ptrs), hipMemcpyHostToDevice, st));
     return PRT_OK;
 }
 
@@ -954,42 +1107,31 @@ static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void*
     hipError_t we;
     PrtScene::CallSlot& q = *s->next_slot(st, &we);
     PRT_HIP(we);
-    PRT_HIP(hipMemsetAsync(q.d_ctr, 0, sizeof(DCounters), st));
-    const uint32_t* d_perm = nullptr;
-    if (sorted && n > 1) {
+    const bool sort = sorted && n > 1;
+    if (sort) {
         std::string err;
         const size_t need = prt::ray_sort_scratch_bytes(n, &err);
         if (!need) return fail(PRT_E_HIP, err);
-        if (!s->sort_done) PRT_HIP(hipEventCreateWithFlags(&s->sort_done, hipEventDisableTiming));
-        else PRT_HIP(hipStreamWaitEvent(st, s->sort_done, 0)); // the scratch is the previous sorted call's until that call has ended
-        if (s->sort_cap < need) {
-            PRT_HIP(hipEventSynchronize(s->sort_done)); // (never recorded: returns at once)
-            if (s->d_sort) (void)hipFree(s->d_sort);    // hipFree waits for the device
-            s->d_sort = nullptr;
-            s->sort_cap = 0;
-            if (hipMalloc(&s->d_sort, need) != hipSuccess) return fail(PRT_E_OOM, "prt_trace_closest_sorted_device: hipMalloc of the sort scratch failed");
-            s->sort_cap = need;
-        }
+        PRT_HIP_AS("prt_trace_closest_sorted_device", s->sort.reserve(need, st));
     }
-    PRT_HIP(hipEventRecord(q.ev0, st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
-    if (sorted && n > 1) {
+    PRT_HIP(q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
+    const uint32_t* d_perm = nullptr;
+    if (sort) {
         std::string err;
-        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->d.grid_origin, s->d.grid_step, s->d_sort, s->sort_cap, st, &err);
+        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->k64.d.grid_origin, s->k64.d.grid_step, s->sort.get<void>(),
+                               s->sort.cap, st, &err);
         if (!d_perm) return fail(PRT_E_HIP, err);
     }
     if (precision == PRT_PRECISION_F32)
-        prt32::launch_trace(s->d32, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr, count_work != 0,
-                            s->n_cu, st, d_perm);
+        prt32::launch_trace(s->k32.d, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr.get(),
+                            count_work != 0, s->n_cu, st, d_perm);
     else
-        prt::launch_trace(s->d, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr, count_work != 0,
-                          s->n_cu, st, d_perm);
+        prt::launch_trace(s->k64.d, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr.get(),
+                          count_work != 0, s->n_cu, st, d_perm);
     PRT_HIP(hipGetLastError());
-    PRT_HIP(hipEventRecord(q.ev1, st));
-    PRT_HIP(hipEventRecord(q.done, st));
-    if (d_perm) PRT_HIP(hipEventRecord(s->sort_done, st));
-    q.timed = true;
-    q.counted = count_work != 0;
-    q.samples = 0;
+    PRT_HIP(q.stop(st));
+    PRT_HIP(q.finish(st, count_work != 0, 0));
+    if (d_perm) PRT_HIP(s->sort.used(st));
     return PRT_OK;
 }
 
@@ -998,25 +1140,13 @@ int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, i
     if (rc) return rc;
     if (n == 0) return PRT_OK;
     if (!rays || !hits) return fail(PRT_E_INVALID, "prt_trace_closest: null buffer");
-    void *dr = nullptr, *dh = nullptr;
-    PRT_HIP(hipMalloc(&dr, n * sizeof(PrtRay)));
-    hipError_t e = hipMalloc(&dh, n * sizeof(PrtHit));
-    if (e != hipSuccess) {
-        (void)hipFree(dr);
-        return fail(PRT_E_OOM, "prt_trace_closest: hipMalloc failed");
-    }
-    rc = PRT_OK;
-    do {
-        if (hipMemcpy(dr, rays, n * sizeof(PrtRay), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(PRT_E_HIP, "prt_trace_closest: H2D copy failed"); break; }
-        rc = prt_trace_closest_device(s, dr, n, dh, count_work, nullptr);
-        if (rc) break;
-        e = hipDeviceSynchronize();
-        if (e != hipSuccess) { rc = fail(PRT_E_HIP, std::string("prt_trace_closest: ") + hipGetErrorString(e)); break; }
-        if (hipMemcpy(hits, dh, n * sizeof(PrtHit), hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(PRT_E_HIP, "prt_trace_closest: D2H copy failed"); break; }
-    } while (0);
-    (void)hipFree(dr);
-    (void)hipFree(dh);
-    return rc;
+    Staging b;
+    void* dr = b.in(rays, n * sizeof(PrtRay));
+    void* dh = b.out(n * sizeof(PrtHit));
+    if ((rc = b.status("prt_trace_closest")) || (rc = prt_trace_closest_device(s, dr, n, dh, count_work, nullptr))) return rc;
+    b.sync();
+    b.down(hits, dh, n * sizeof(PrtHit));
+    return b.status("prt_trace_closest");
 }
 
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {
@@ -1024,49 +1154,16 @@ int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t see
     if (rc) return rc;
     if (n == 0) return PRT_OK;
     if (!origins || !out) return fail(PRT_E_INVALID, "prt_sample_lights: null buffer");
-    if (s->d.n_lights == 0) return fail(PRT_E_INVALID, "prt_sample_lights: scene has no emissive mesh");
-    void *dorg = nullptr, *dout = nullptr;
-    PRT_HIP(hipMalloc(&dorg, n * 3 * sizeof(double)));
-    if (hipMalloc(&dout, n * sizeof(PrtLightSample)) != hipSuccess) {
-        (void)hipFree(dorg);
-        return fail(PRT_E_OOM, "prt_sample_lights: hipMalloc failed");
-    }
-    rc = PRT_OK;
-    do {
-        if (hipMemcpy(dorg, origins, n * 3 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(PRT_E_HIP, "prt_sample_lights: H2D copy failed"); break; }
-        prt::launch_sample_lights(s->d, static_cast<const double*>(dorg), n, seed, static_cast<PrtLightSample*>(dout), nullptr);
-        hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) { rc = fail(PRT_E_HIP, std::string("prt_sample_lights: ") + hipGetErrorString(e)); break; }
-        if (hipMemcpy(out, dout, n * sizeof(PrtLightSample), hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(PRT_E_HIP, "prt_sample_lights: D2H copy failed"); break; }
-    } while (0);
-    (void)hipFree(dorg);
-    (void)hipFree(dout);
-    return rc;
+    if (s->k64.d.n_lights == 0) return fail(PRT_E_INVALID, "prt_sample_lights: scene has no emissive mesh");
+    Staging b;
+    const double* dorg = static_cast<const double*>(b.in(origins, n * 3 * sizeof(double)));
+    PrtLightSample* dout = static_cast<PrtLightSample*>(b.out(n * sizeof(PrtLightSample)));
+    if ((rc = b.status("prt_sample_lights"))) return rc;
+    prt::launch_sample_lights(s->k64.d, dorg, n, seed, dout, nullptr);
+    b.sync();
+    b.down(out, dout, n * sizeof(PrtLightSample));
+    return b.status("prt_sample_lights");
 }
-
-namespace {
-// Device staging for the small host-buffer test hooks: copies inputs up, frees everything on destruction.
-struct HookBufs {
-    std::vector<void*> p;
-    ~HookBufs() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    void* up(const void* src, size_t bytes) { // nullptr in -> nullptr out
-        if (!src) return nullptr;
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        p.push_back(d);
-        if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    }
-    void* out(size_t bytes) {
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        p.push_back(d);
-        return d;
-    }
-};
-} // namespace
 
 int prt_material_eval(PrtScene* s, int32_t material, size_t n, const double* wi, const double* wo, const double* uv,
                       uint64_t seed, double* f) {
@@ -1075,15 +1172,15 @@ int prt_material_eval(PrtScene* s, int32_t material, size_t n, const double* wi,
     if (material < 0 || (size_t)material >= s->mats.size()) return fail(PRT_E_INVALID, "prt_material_eval: material index out of range");
     if (n == 0) return PRT_OK;
     if (!wi || !wo || !f) return fail(PRT_E_INVALID, "prt_material_eval: null buffer");
-    HookBufs b;
-    const double *dwi = static_cast<const double*>(b.up(wi, n * 24)), *dwo = static_cast<const double*>(b.up(wo, n * 24));
-    const double* duv = static_cast<const double*>(b.up(uv, n * 16));
+    Staging b;
+    const double *dwi = static_cast<const double*>(b.in(wi, n * 24)), *dwo = static_cast<const double*>(b.in(wo, n * 24));
+    const double* duv = static_cast<const double*>(b.in(uv, n * 16));
     double* df = static_cast<double*>(b.out(n * 24));
-    if (!dwi || !dwo || !df || (uv && !duv)) return fail(PRT_E_OOM, "prt_material_eval: device staging failed");
-    prt::launch_material_eval(s->d, material, dwi, dwo, duv, n, seed, df, nullptr);
-    PRT_HIP(hipDeviceSynchronize());
-    PRT_HIP(hipMemcpy(f, df, n * 24, hipMemcpyDeviceToHost));
-    return PRT_OK;
+    if ((rc = b.status("prt_material_eval"))) return rc;
+    prt::launch_material_eval(s->k64.d, material, dwi, dwo, duv, n, seed, df, nullptr);
+    b.sync();
+    b.down(f, df, n * 24);
+    return b.status("prt_material_eval");
 }
 
 int prt_material_scatter(PrtScene* s, int32_t material, size_t n, const double* rd, const double* normal, const double* tangent,
@@ -1093,18 +1190,18 @@ int prt_material_scatter(PrtScene* s, int32_t material, size_t n, const double* 
     if (material < 0 || (size_t)material >= s->mats.size()) return fail(PRT_E_INVALID, "prt_material_scatter: material index out of range");
     if (n == 0) return PRT_OK;
     if (!rd || !normal || !tangent || !wi_world || !attenuation || !ok) return fail(PRT_E_INVALID, "prt_material_scatter: null buffer");
-    HookBufs b;
-    const double* drd = static_cast<const double*>(b.up(rd, n * 24));
-    const double* duv = static_cast<const double*>(b.up(uv, n * 16));
+    Staging b;
+    const double* drd = static_cast<const double*>(b.in(rd, n * 24));
+    const double* duv = static_cast<const double*>(b.in(uv, n * 16));
     double *dwi = static_cast<double*>(b.out(n * 24)), *datt = static_cast<double*>(b.out(n * 24));
     int32_t* dok = static_cast<int32_t*>(b.out(n * 4));
-    if (!drd || !dwi || !datt || !dok || (uv && !duv)) return fail(PRT_E_OOM, "prt_material_scatter: device staging failed");
-    prt::launch_material_scatter(s->d, material, drd, normal, tangent, duv, n, seed, dwi, datt, dok, nullptr);
-    PRT_HIP(hipDeviceSynchronize());
-    PRT_HIP(hipMemcpy(wi_world, dwi, n * 24, hipMemcpyDeviceToHost));
-    PRT_HIP(hipMemcpy(attenuation, datt, n * 24, hipMemcpyDeviceToHost));
-    PRT_HIP(hipMemcpy(ok, dok, n * 4, hipMemcpyDeviceToHost));
-    return PRT_OK;
+    if ((rc = b.status("prt_material_scatter"))) return rc;
+    prt::launch_material_scatter(s->k64.d, material, drd, normal, tangent, duv, n, seed, dwi, datt, dok, nullptr);
+    b.sync();
+    b.down(wi_world, dwi, n * 24);
+    b.down(attenuation, datt, n * 24);
+    b.down(ok, dok, n * 4);
+    return b.status("prt_material_scatter");
 }
 
 int prt_texture_value(PrtScene* s, int32_t texture, size_t n, const double* uv, double* rgb) {
@@ -1113,14 +1210,14 @@ int prt_texture_value(PrtScene* s, int32_t texture, size_t n, const double* uv, 
     if (texture < 0 || (size_t)texture >= s->texs.size()) return fail(PRT_E_INVALID, "prt_texture_value: texture index out of range");
     if (n == 0) return PRT_OK;
     if (!uv || !rgb) return fail(PRT_E_INVALID, "prt_texture_value: null buffer");
-    HookBufs b;
-    const double* duv = static_cast<const double*>(b.up(uv, n * 16));
+    Staging b;
+    const double* duv = static_cast<const double*>(b.in(uv, n * 16));
     double* d = static_cast<double*>(b.out(n * 24));
-    if (!duv || !d) return fail(PRT_E_OOM, "prt_texture_value: device staging failed");
-    prt::launch_texture_value(s->d, texture, duv, n, d, nullptr);
-    PRT_HIP(hipDeviceSynchronize());
-    PRT_HIP(hipMemcpy(rgb, d, n * 24, hipMemcpyDeviceToHost));
-    return PRT_OK;
+    if ((rc = b.status("prt_texture_value"))) return rc;
+    prt::launch_texture_value(s->k64.d, texture, duv, n, d, nullptr);
+    b.sync();
+    b.down(rgb, d, n * 24);
+    return b.status("prt_texture_value");
 }
 
 // What one K3 launch renders and where its item sums go.  prt_render_device: samples [0, spp) of a frame, scaled by 1/spp
@@ -1166,48 +1263,23 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
 
     DCamera C;
     prt::setup_camera(*cam, C);
-    DRenderParams P;
-    std::memset(&P, 0, sizeof(P));
+    DRenderParams P = base_params(s, p);
     P.spp = pass.d_sum ? 1 : pass.spp;
-    P.max_depth = p->max_depth;
-    P.sample_lights = p->sample_lights ? 1 : 0;
-    P.rr = p->russian_roulette;
-    P.inv_rr = 1.0 / p->russian_roulette;
-    // wave scheduling thresholds (developer overrides through the environment for sweeps)
-    // measured optima at the BASELINE spp with 4-wide nodes (flat within 2 %): lean 28 / 48 / 20, others 20 / 40 / 12; the Phong
-    // permutations at three waves: leaf batch 32 (round 4, two sweeps and a four-fold A/B on veach-mis: -0.75 %)
-    P.keep = s->feat == 0 ? 28 : 20;
-    P.leaf_batch = s->feat == 0 ? 48 : (s->feat & 2) ? 32 : 40; // (2 = Phong, as in s->feat above)
-    P.inner_min = s->feat == 0 ? 20 : 12;
     P.cached_min = 24; // measured: veach-mis -1 %, the others flat
+    // (developer overrides of the wave scheduling thresholds through the environment, for sweeps)
     if (const char* e = dev_env("PRT_TUNE_CACHED_MIN")) P.cached_min = std::max(1, std::atoi(e)); // (0 would keep a wave passing for ever)
     if (const char* e = dev_env("PRT_TUNE_KEEP")) P.keep = std::atoi(e);
     if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::atoi(e);
     if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::atoi(e);
     if (const char* e = dev_env("PRT_TUNE_SCRAMBLE")) P.scramble = std::atoi(e) ? 1 : 0; // experiment: incoherent pixel order (PRT_ITEMS_FROM_LIST is set by adaptive rounds below and by prt_render_samples)
-    for (int c = 0; c < 3; ++c) P.background[c] = p->background[c];
-    P.seed_key = prt::seed_key(p->seed); // the seed is hashed on its own, once per launch (prt_device.h, Rng)
-    int tile = p->tile_size > 0 ? p->tile_size : 32;
-    tile = std::max(8, (tile + 7) / 8 * 8);
-    P.tile = tile;
-    P.tiles_x = (C.width + tile - 1) / tile;
-    P.tiles_y = (C.height + tile - 1) / tile;
-    P.n_tiles = P.tiles_x * P.tiles_y;
-    P.rank = p->rank;
-    P.nranks = p->nranks;
-    P.jitter = p->pixel_jitter ? 1 : 0;
-    P.light_lds = s->light_lds;
-    P.mat_lds = s->mat_lds;
-    P.ltri_lds = s->ltri_lds;
-    P.stack_depth = s->stack_depth;
-    P.owned_tiles = P.n_tiles > P.rank ? (P.n_tiles - P.rank + P.nranks - 1) / P.nranks : 0;
-    P.items_per_chunk = (uint64_t)P.owned_tiles * tile * tile;
+    const TileLayout L(*cam, *p);
+    L.set(P);
     if (pass.d_list) { // an adaptive round: the listed pixels (all owned by this rank) instead of the owned tiles
         P.scramble = PRT_ITEMS_FROM_LIST;
         P.items_per_chunk = pass.list_n;
     }
     const bool count = count_work != 0;
-    const int bpc = f32 ? s->blocks_per_cu32[count ? 1 : 0] : s->blocks_per_cu[count ? 1 : 0];
+    const int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : 0];
     const uint64_t lanes = (uint64_t)s->n_cu * bpc * PRT_BLOCK;
     // Work item = (pixel, chunk of samples), dealt chunk-major from PRT_ITEM_QUEUES counters (prt_types.h).
     //  * explicit sample_chunks: that many equal chunks;
@@ -1270,72 +1342,46 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     hipError_t we;
     PrtScene::CallSlot& q = *s->next_slot(st, &we);
     PRT_HIP(we);
-    if (need > q.partial_cap) {
-        if (q.d_partial) (void)hipFree(q.d_partial); // hipFree waits for the device: nothing in flight reads it
-        q.d_partial = nullptr;
-        q.partial_cap = 0;
-        PRT_HIP(hipMalloc(reinterpret_cast<void**>(&q.d_partial), need * sizeof(double)));
-        q.partial_cap = need;
-    }
+    PRT_HIP(q.partial.reserve(need * sizeof(double), st));
+    double* d_partial = q.partial.get<double>();
     const size_t npx = (size_t)C.width * C.height * 3;
-    void* dump_buf = nullptr;
+    DevBuf<> dump_buf;
     unsigned long long dump_cap = 0;
     std::string dump_path;
-    PRT_HIP(hipMemsetAsync(q.d_ctr, 0, sizeof(DCounters), st));
     if (d_rgb_f64) PRT_HIP(hipMemsetAsync(d_rgb_f64, 0, npx * sizeof(double), st));
     if (d_rgb_f32) PRT_HIP(hipMemsetAsync(d_rgb_f32, 0, npx * sizeof(float), st));
-    PRT_HIP(hipEventRecord(q.ev0, st));
+    PRT_HIP(q.start(st));
     // maxDepth < 0: RayColor returns 0 before it traces anything (Camera.cpp:121) — the cleared framebuffer is the frame
     if (P.max_depth < 0) P.n_items = 0;
     if (P.n_items) {
         const uint64_t want = (P.n_items + PRT_BLOCK - 1) / PRT_BLOCK;
         const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s->n_cu * bpc));
-        if ((rc = set_slot_pointers(s, q, st, grid, pass.d_list, nullptr))) return rc;
+        PRT_HIP(q.set_pointers(st, pass.d_list, nullptr));
         if (const char* e = dev_env("PRT_TUNE_DUMP_RAYS")) { // "<max rays>,<file>" (counting launches only)
             const std::string v(e);
             const size_t comma = v.find(',');
             if (count && comma != std::string::npos) {
                 dump_cap = std::strtoull(v.substr(0, comma).c_str(), nullptr, 10);
                 dump_path = v.substr(comma + 1);
-                PRT_HIP(hipMalloc(&dump_buf, (size_t)dump_cap * sizeof(PrtRay)));
-                const unsigned long long vals[3] = {(unsigned long long)(uintptr_t)dump_buf, dump_cap, 0ULL};
-                PRT_HIP(hipMemcpyAsync(reinterpret_cast<char*>(q.d_ctr) + offsetof(DCounters, ray_dump), vals, sizeof(vals), hipMemcpyHostToDevice, st));
+                PRT_HIP(dev_alloc(dump_buf, (size_t)dump_cap * sizeof(PrtRay)));
+                const unsigned long long vals[3] = {(unsigned long long)(uintptr_t)dump_buf.get(), dump_cap, 0ULL};
+                PRT_HIP(hipMemcpyAsync(reinterpret_cast<char*>(q.d_ctr.get()) + offsetof(DCounters, ray_dump), vals, sizeof(vals), hipMemcpyHostToDevice, st));
             }
         }
-        if (f32) {
-            // the same camera and parameters rounded to float (K5 below works from the fp64 originals: it only maps pixels)
-            DCameraT<float> C32;
-            conv_arr(C32.center, C.center, 3); conv_arr(C32.pixel00, C.pixel00, 3);
-            conv_arr(C32.du, C.du, 3); conv_arr(C32.dv, C.dv, 3);
-            C32.width = C.width; C32.height = C.height;
-            DRenderParamsT<float> P32;
-            std::memset(&P32, 0, sizeof(P32));
-            P32.spp = P.spp; P32.max_depth = P.max_depth; P32.sample_lights = P.sample_lights; P32.chunks = P.chunks;
-            P32.rr = (float)P.rr; P32.inv_rr = (float)P.inv_rr;
-            conv_arr(P32.background, P.background, 3);
-            P32.seed_key = P.seed_key;
-            P32.tile = P.tile; P32.tiles_x = P.tiles_x; P32.tiles_y = P.tiles_y; P32.n_tiles = P.n_tiles;
-            P32.rank = P.rank; P32.nranks = P.nranks; P32.owned_tiles = P.owned_tiles; P32.jitter = P.jitter;
-            P32.keep = P.keep; P32.leaf_batch = P.leaf_batch; P32.inner_min = P.inner_min; P32.scramble = P.scramble; P32.cached_min = P.cached_min;
-            P32.light_lds = s->light_lds32; P32.mat_lds = s->mat_lds32; P32.ltri_lds = s->ltri_lds32;
-            P32.stack_depth = s->stack_depth32;
-            P32.items_per_chunk = P.items_per_chunk; P32.n_items = P.n_items;
-            std::memcpy(P32.chunk_begin, P.chunk_begin, sizeof(P.chunk_begin));
-            prt32::launch_render(s->d32, C32, P32, q.d_partial, q.d_ctr, count, s->feat, grid, st);
-        } else {
-            prt::launch_render(s->d_k3, C, P, q.d_partial, q.d_ctr, count, s->feat, grid, st);
-        }
+        // fp32: the same camera and parameters rounded to float (K5 below works from the fp64 originals: it only maps pixels)
+        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st);
+        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st);
         PRT_HIP(hipGetLastError());
     }
-    PRT_HIP(hipEventRecord(q.ev1, st));
+    PRT_HIP(q.stop(st));
     if (dump_buf) { // developer experiment: write K3's ray stream to the file (synchronous)
         PRT_HIP(hipStreamSynchronize(st));
         DCounters h;
-        PRT_HIP(hipMemcpy(&h, q.d_ctr, sizeof(h), hipMemcpyDeviceToHost));
+        PRT_HIP(hipMemcpy(&h, q.d_ctr.get(), sizeof(h), hipMemcpyDeviceToHost));
         const size_t nd = (size_t)std::min<unsigned long long>(h.ray_dump_n, dump_cap);
         std::vector<PrtRay> rays(nd);
-        PRT_HIP(hipMemcpy(rays.data(), dump_buf, nd * sizeof(PrtRay), hipMemcpyDeviceToHost));
-        (void)hipFree(dump_buf);
+        PRT_HIP(hipMemcpy(rays.data(), dump_buf.get(), nd * sizeof(PrtRay), hipMemcpyDeviceToHost));
+        dump_buf.reset();
         if (FILE* f = std::fopen(dump_path.c_str(), "wb")) {
             std::fwrite(rays.data(), sizeof(PrtRay), nd, f);
             std::fclose(f);
@@ -1344,29 +1390,17 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     }
     if (pass.d_list) {
         // maxDepth < 0: no item ran, and every sample is 0; the counts still grow
-        if (!P.n_items) PRT_HIP(hipMemsetAsync(q.d_partial, 0, need * sizeof(double), st));
-        prt::launch_accumulate_list(P, q.d_partial, pass.d_list, (uint32_t)pass.batch, (uint32_t)spp, pass.d_sum, pass.d_moment,
+        if (!P.n_items) PRT_HIP(hipMemsetAsync(d_partial, 0, need * sizeof(double), st));
+        prt::launch_accumulate_list(P, d_partial, pass.d_list, (uint32_t)pass.batch, (uint32_t)spp, pass.d_sum, pass.d_moment,
                                     pass.d_count, st);
         PRT_HIP(hipGetLastError());
     } else if (P.n_items) {
-        if (pass.d_sum) prt::launch_accumulate(C, P, q.d_partial, pass.d_sum, st);
-        else prt::launch_finalize(C, P, q.d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
+        if (pass.d_sum) prt::launch_accumulate(C, P, d_partial, pass.d_sum, st);
+        else prt::launch_finalize(C, P, d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
         PRT_HIP(hipGetLastError());
     }
-    PRT_HIP(hipEventRecord(q.done, st));
-    q.timed = true;
-    q.counted = count;
-    q.samples = 0;
-    if (pass.d_list) {
-        q.samples = P.n_items ? (uint64_t)pass.list_n * (uint64_t)spp : 0;
-    } else if (P.n_items) { // pixels of this rank's tiles that lie inside the image, times spp
-        uint64_t px = 0;
-        for (int k = P.rank; k < P.n_tiles; k += P.nranks) {
-            const int ty = k / P.tiles_x, kx = k - ty * P.tiles_x, tx = (kx + 3 * ty) % P.tiles_x; // prt_device.h, owned_to_pixel
-            px += (uint64_t)std::max(0, std::min(tile, C.width - tx * tile)) * (uint64_t)std::max(0, std::min(tile, C.height - ty * tile));
-        }
-        q.samples = px * (uint64_t)spp;
-    }
+    const uint64_t samples = !P.n_items ? 0 : pass.d_list ? (uint64_t)pass.list_n * (uint64_t)spp : L.owned_pixels() * (uint64_t)spp;
+    PRT_HIP(q.finish(st, count, samples));
     return PRT_OK;
 }
 
@@ -1376,26 +1410,14 @@ int prt_render(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, doub
     if (!cam || !p) return fail(PRT_E_INVALID, "prt_render: null argument");
     if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, "prt_render: bad image size");
     const size_t npx = (size_t)cam->width * cam->height * 3;
-    void *d64 = nullptr, *d32 = nullptr;
-    if (rgb_f64) PRT_HIP(hipMalloc(&d64, npx * sizeof(double)));
-    if (rgb_f32) {
-        if (hipMalloc(&d32, npx * sizeof(float)) != hipSuccess) {
-            if (d64) (void)hipFree(d64);
-            return fail(PRT_E_OOM, "prt_render: hipMalloc failed");
-        }
-    }
-    rc = prt_render_device(s, cam, p, d64, d32, 0, nullptr);
-    if (rc == PRT_OK) {
-        hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(PRT_E_HIP, std::string("prt_render: ") + hipGetErrorString(e));
-    }
-    if (rc == PRT_OK && rgb_f64 && hipMemcpy(rgb_f64, d64, npx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(PRT_E_HIP, "prt_render: D2H copy failed");
-    if (rc == PRT_OK && rgb_f32 && hipMemcpy(rgb_f32, d32, npx * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(PRT_E_HIP, "prt_render: D2H copy failed");
-    if (d64) (void)hipFree(d64);
-    if (d32) (void)hipFree(d32);
-    return rc;
+    Staging b;
+    void* d64 = rgb_f64 ? b.out(npx * sizeof(double)) : nullptr;
+    void* d32 = rgb_f32 ? b.out(npx * sizeof(float)) : nullptr;
+    if ((rc = b.status("prt_render")) || (rc = prt_render_device(s, cam, p, d64, d32, 0, nullptr))) return rc;
+    b.sync();
+    if (rgb_f64) b.down(rgb_f64, d64, npx * sizeof(double));
+    if (rgb_f32) b.down(rgb_f32, d32, npx * sizeof(float));
+    return b.status("prt_render");
 }
 
 // Test hook (prt.h): single camera samples through K3.  One work item per (listed pixel, sample): the sample chunks of a
@@ -1403,7 +1425,8 @@ int prt_render(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, doub
 // partial sum IS the sample's RayColor.
 int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, const int32_t* pixel_xy, size_t n_pixels,
                        int32_t sample_begin, int32_t sample_count, double* radiance, int32_t* trace) {
-    int rc = require_uploaded(s, "prt_render_samples");
+    const char* who = "prt_render_samples";
+    int rc = require_uploaded(s, who);
     if (rc) return rc;
     if (!cam || !p || (n_pixels && (!pixel_xy || !radiance))) return fail(PRT_E_INVALID, "prt_render_samples: null argument");
     if (cam->width < 1 || cam->height < 1) return fail(PRT_E_INVALID, "prt_render_samples: bad image size");
@@ -1419,67 +1442,43 @@ int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams*
     }
     DCamera C;
     prt::setup_camera(*cam, C);
-    DRenderParams P;
-    std::memset(&P, 0, sizeof(P));
+    DRenderParams P = base_params(s, p);
     P.spp = 1;
-    P.max_depth = p->max_depth;
-    P.sample_lights = p->sample_lights ? 1 : 0;
-    P.rr = p->russian_roulette;
-    P.inv_rr = 1.0 / p->russian_roulette;
-    P.keep = s->feat == 0 ? 28 : 20;
-    P.leaf_batch = s->feat == 0 ? 48 : (s->feat & 2) ? 32 : 40; // (2 = Phong, as in s->feat above)
-    P.inner_min = s->feat == 0 ? 20 : 12;
     P.scramble = PRT_ITEMS_FROM_LIST;
     P.cached_min = 65;
-    for (int c = 0; c < 3; ++c) P.background[c] = p->background[c];
-    P.seed_key = prt::seed_key(p->seed);
-    P.tile = 8;
-    P.tiles_x = P.tiles_y = P.n_tiles = 1;
-    P.rank = 0;
-    P.nranks = 1;
-    P.owned_tiles = 1;
-    P.jitter = p->pixel_jitter ? 1 : 0;
-    P.light_lds = s->light_lds;
-    P.mat_lds = s->mat_lds;
-    P.ltri_lds = s->ltri_lds;
-    P.stack_depth = s->stack_depth;
+    P.tile = 8; P.tiles_x = P.tiles_y = P.n_tiles = 1; P.rank = 0; P.nranks = 1; P.owned_tiles = 1; // (the items come from the list)
     P.items_per_chunk = n_pixels;
     const bool count = trace != nullptr;
-    const int bpc = s->blocks_per_cu[count ? 1 : 0];
-    int32_t *d_pix = nullptr, *d_trace = nullptr;
-    double* d_part = nullptr;
+    const int bpc = s->k64.blocks_per_cu[count ? 1 : 0];
     const size_t per_launch = n_pixels * (size_t)std::min<int>(sample_count, PRT_MAX_CHUNKS);
-    PRT_HIP(hipMalloc(reinterpret_cast<void**>(&d_pix), n_pixels * sizeof(int32_t)));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_part), per_launch * 3 * sizeof(double));
-    if (e == hipSuccess && trace) e = hipMalloc(reinterpret_cast<void**>(&d_trace), per_launch * PRT_TRACE_WORDS * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(d_pix, pix.data(), n_pixels * sizeof(int32_t), hipMemcpyHostToDevice);
+    Staging b;
+    const int32_t* d_pix = static_cast<const int32_t*>(b.in(pix.data(), n_pixels * sizeof(int32_t)));
+    double* d_part = static_cast<double*>(b.out(per_launch * 3 * sizeof(double)));
+    int32_t* d_trace = trace ? static_cast<int32_t*>(b.out(per_launch * PRT_TRACE_WORDS * sizeof(int32_t))) : nullptr;
+    if ((rc = b.status(who))) return rc;
     std::vector<double> part(per_launch * 3);
     std::vector<int32_t> tr(trace ? per_launch * PRT_TRACE_WORDS : 0);
-    hipError_t we = hipSuccess;
-    for (int32_t s0 = 0; e == hipSuccess && s0 < sample_count; s0 += PRT_MAX_CHUNKS) {
+    for (int32_t s0 = 0; s0 < sample_count; s0 += PRT_MAX_CHUNKS) {
         const int chunks = std::min<int>(PRT_MAX_CHUNKS, sample_count - s0);
         for (int c = 0; c <= chunks; ++c) P.chunk_begin[c] = sample_begin + s0 + c;
         P.chunks = chunks;
         P.n_items = P.items_per_chunk * (uint64_t)chunks;
+        hipError_t we;
         PrtScene::CallSlot& q = *s->next_slot(nullptr, &we);
-        if ((e = we) != hipSuccess) break;
-        if ((e = hipMemsetAsync(q.d_ctr, 0, sizeof(DCounters), nullptr)) != hipSuccess) break;
+        PRT_HIP_AS(who, we);
         const uint64_t want = (P.n_items + PRT_BLOCK - 1) / PRT_BLOCK;
         const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s->n_cu * bpc));
-        if (set_slot_pointers(s, q, nullptr, grid, d_pix, d_trace) != PRT_OK) { e = hipErrorUnknown; break; }
-        if (d_trace && (e = hipMemset(d_trace, 0, (size_t)P.n_items * PRT_TRACE_WORDS * sizeof(int32_t))) != hipSuccess) break;
-        (void)hipEventRecord(q.ev0, nullptr);
-        if (P.max_depth >= 0) prt::launch_render(s->d_k3, C, P, d_part, q.d_ctr, count, s->feat, grid, nullptr);
-        else if ((e = hipMemset(d_part, 0, (size_t)P.n_items * 3 * sizeof(double))) != hipSuccess) break;
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        (void)hipEventRecord(q.ev1, nullptr);
-        (void)hipEventRecord(q.done, nullptr);
-        q.timed = true;
-        q.counted = count;
-        q.samples = P.max_depth >= 0 ? P.n_items : 0;
-        if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-        if ((e = hipMemcpy(part.data(), d_part, (size_t)P.n_items * 3 * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) break;
-        if (trace && (e = hipMemcpy(tr.data(), d_trace, (size_t)P.n_items * PRT_TRACE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
+        if (d_trace) PRT_HIP_AS(who, hipMemset(d_trace, 0, (size_t)P.n_items * PRT_TRACE_WORDS * sizeof(int32_t)));
+        PRT_HIP_AS(who, q.start(nullptr));
+        PRT_HIP_AS(who, q.set_pointers(nullptr, d_pix, d_trace));
+        if (P.max_depth >= 0) prt::launch_render(s->k64.d, C, P, d_part, q.d_ctr.get(), count, s->feat, grid, nullptr);
+        else PRT_HIP_AS(who, hipMemset(d_part, 0, (size_t)P.n_items * 3 * sizeof(double)));
+        PRT_HIP_AS(who, hipGetLastError());
+        PRT_HIP_AS(who, q.stop(nullptr));
+        PRT_HIP_AS(who, q.finish(nullptr, count, P.max_depth >= 0 ? P.n_items : 0));
+        PRT_HIP_AS(who, hipDeviceSynchronize());
+        PRT_HIP_AS(who, hipMemcpy(part.data(), d_part, (size_t)P.n_items * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        if (trace) PRT_HIP_AS(who, hipMemcpy(tr.data(), d_trace, (size_t)P.n_items * PRT_TRACE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (int c = 0; c < chunks; ++c)
             for (size_t k = 0; k < n_pixels; ++k) { // item = chunk * n_pixels + k  ->  out[k][s0 + c]
                 const size_t item = (size_t)c * n_pixels + k, o = k * (size_t)sample_count + (size_t)(s0 + c);
@@ -1487,10 +1486,6 @@ int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams*
                 if (trace) std::memcpy(trace + o * PRT_TRACE_WORDS, tr.data() + item * PRT_TRACE_WORDS, PRT_TRACE_WORDS * sizeof(int32_t));
             }
     }
-    (void)hipFree(d_pix);
-    if (d_part) (void)hipFree(d_part);
-    if (d_trace) (void)hipFree(d_trace);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_render_samples: ") + hipGetErrorString(e));
     return PRT_OK;
 }
 
@@ -1539,18 +1534,12 @@ int render_multi_impl(PrtScene* const* scenes, int n, const PrtCamera* cam, cons
     for (int r = 0; r < n; ++r) {
         PrtScene* s = scenes[r];
         PRT_HIP(hipSetDevice(s->device));
-        if (s->multi_fb_cap < npx) {
-            if (s->multi_fb) (void)hipFree(s->multi_fb);
-            s->multi_fb = nullptr;
-            s->multi_fb_cap = 0;
-            PRT_HIP(hipMalloc(reinterpret_cast<void**>(&s->multi_fb), npx * sizeof(float)));
-            s->multi_fb_cap = npx;
-        }
+        PRT_HIP(s->multi_fb.reserve(npx * sizeof(float), nullptr));
         PrtRenderParams pr = *p;
         pr.tile_size = n > 1 ? 16 : p->tile_size;
         pr.rank = r;
         pr.nranks = n;
-        const int rc = prt_render_device(s, cam, &pr, nullptr, s->multi_fb, 0, nullptr);
+        const int rc = prt_render_device(s, cam, &pr, nullptr, s->multi_fb.get<void>(), 0, nullptr);
         if (rc != PRT_OK) return rc;
     }
     // test hooks (PRT_DEV_HOOKS builds only).  PRT_TEST_FORCE_RCCL: a single scene goes through the RCCL branch as well (a
@@ -1561,7 +1550,7 @@ int render_multi_impl(PrtScene* const* scenes, int n, const PrtCamera* cam, cons
     if (n > 1 && all_same) {
         // tile shares of one device (replicas; a rehearsal of the multi-GPU path on one GPU): summed where they are
         PRT_HIP(hipSetDevice(devs[0]));
-        for (int r = 1; r < n; ++r) prt::launch_add_f32(scenes[0]->multi_fb, scenes[r]->multi_fb, npx, nullptr);
+        for (int r = 1; r < n; ++r) prt::launch_add_f32(scenes[0]->multi_fb.get<float>(), scenes[r]->multi_fb.get<float>(), npx, nullptr);
         PRT_HIP(hipGetLastError());
     } else if (n > 1 || force_rccl) {
         // ONE collective: reduce(sum) of the fp32 framebuffers to the first device over RCCL (xGMI between the GPUs of a
@@ -1595,7 +1584,7 @@ int render_multi_impl(PrtScene* const* scenes, int n, const PrtCamera* cam, cons
                 break;
             }
             nr = (inject && !std::strcmp(inject, "reduce")) ? ncclInternalError
-                 : ncclReduce(scenes[r]->multi_fb, scenes[r]->multi_fb, npx, ncclFloat, ncclSum, 0, cs.comms[r], nullptr);
+                 : ncclReduce(scenes[r]->multi_fb.get<float>(), scenes[r]->multi_fb.get<float>(), npx, ncclFloat, ncclSum, 0, cs.comms[r], nullptr);
         }
         const ncclResult_t ne = ncclGroupEnd();
         if (nr == ncclSuccess) nr = ne;
@@ -1610,7 +1599,7 @@ int render_multi_impl(PrtScene* const* scenes, int n, const PrtCamera* cam, cons
     }
     PRT_HIP(hipSetDevice(devs[0]));
     PRT_HIP(hipDeviceSynchronize());
-    PRT_HIP(hipMemcpy(rgb_f32, scenes[0]->multi_fb, npx * sizeof(float), hipMemcpyDeviceToHost));
+    PRT_HIP(hipMemcpy(rgb_f32, scenes[0]->multi_fb.get<float>(), npx * sizeof(float), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 } // namespace
@@ -1643,11 +1632,11 @@ int prt_get_counters(PrtScene* s, PrtCounters* out) {
     PrtScene::CallSlot& q = s->slots[s->cur];
     if (s->device >= 0 && q.timed) {
         PRT_HIP(hipSetDevice(s->device));
-        PRT_HIP(hipEventSynchronize(q.ev1));
+        PRT_HIP(hipEventSynchronize(q.ev1.get()));
         float ms = 0.f;
-        PRT_HIP(hipEventElapsedTime(&ms, q.ev0, q.ev1));
+        PRT_HIP(hipEventElapsedTime(&ms, q.ev0.get(), q.ev1.get()));
         DCounters h;
-        PRT_HIP(hipMemcpy(&h, q.d_ctr, sizeof(h), hipMemcpyDeviceToHost));
+        PRT_HIP(hipMemcpy(&h, q.d_ctr.get(), sizeof(h), hipMemcpyDeviceToHost));
         c.rays_closest = h.rays_closest;
         c.rays_shadow = h.rays_shadow;
         c.node_fetches = h.node_fetches;
@@ -1679,27 +1668,27 @@ struct PrtAccum {
     uint64_t samples = 0;
     uint64_t fingerprint = 0;
     size_t n = 0; // W * H * 3
-    double* d_sum = nullptr;
-    hipEvent_t done = nullptr;
+    DevBuf<double> d_sum;
+    Event done;
     // adaptive accumulators (prt_accum_create_adaptive): `samples` is the global count n, and per pixel a second moment and
     // a sample count; a round's active pixels are listed in d_list (d_seg: the select's per-segment counts, d_active: the
     // list's length, read back through the pinned h_active)
     bool adaptive = false;
     PrtAdaptiveParams ad{}; // with the effective batch
-    double* d_moment = nullptr;
-    uint32_t* d_count = nullptr;
-    int32_t* d_list = nullptr;
-    uint32_t* d_seg = nullptr;
-    uint32_t* d_active = nullptr;
-    uint32_t* h_active = nullptr;
+    DevBuf<double> d_moment;
+    DevBuf<uint32_t> d_count;
+    DevBuf<int32_t> d_list;
+    DevBuf<uint32_t> d_seg;
+    DevBuf<uint32_t> d_active;
+    std::unique_ptr<uint32_t, HipHostFree> h_active;
     // prt_accum_resolve_denoised: the cached features (albedo [n], normal [n], depth [n / 3] floats) of scene generation
     // feat_gen traced with feat_spp samples, the resolved fp32 frame and the denoised one (when the caller wants only bytes)
-    float* d_feat = nullptr;
+    DevBuf<float> d_feat;
     bool feat_valid = false;
     uint64_t feat_gen = 0;
     int32_t feat_spp = 0;
-    float* d_res32 = nullptr;
-    float* d_dn32 = nullptr;
+    DevBuf<float> d_res32;
+    DevBuf<float> d_dn32;
 };
 
 namespace {
@@ -1722,43 +1711,12 @@ uint64_t accum_fingerprint(const PrtScene* s, const PrtCamera& c, const PrtRende
     f.add(p.max_depth); f.add(p.russian_roulette); f.add((int32_t)(p.sample_lights ? 1 : 0)); f.add(p.precision);
     for (int k = 0; k < 3; ++k) f.add(p.background[k]);
     f.add(p.seed);
-    int tile = p.tile_size > 0 ? p.tile_size : 32; // as render_impl rounds it
-    tile = std::max(8, (tile + 7) / 8 * 8);
-    f.add((int32_t)tile); f.add(p.rank); f.add(p.nranks); f.add((int32_t)(p.pixel_jitter ? 1 : 0));
+    f.add((int32_t)TileLayout(c, p).tile); f.add(p.rank); f.add(p.nranks); f.add((int32_t)(p.pixel_jitter ? 1 : 0));
     f.add((uint64_t)s->tris.size()); f.add((uint64_t)s->mesh_mat.size()); f.add((uint64_t)s->mats.size());
     if (ad) {
         f.add(ad->min_spp); f.add(ad->max_spp); f.add(ad->batch); f.add(ad->rel_tol); f.add(ad->abs_tol);
     }
     return f.h;
-}
-// The tile layout render_impl gives the accumulator's launches (owned item oi -> pixel as in K3), for the adaptive select.
-void accum_layout(const PrtAccum* a, DCamera& C, DRenderParams& P) {
-    prt::setup_camera(a->cam, C);
-    std::memset(&P, 0, sizeof(P));
-    int tile = a->params.tile_size > 0 ? a->params.tile_size : 32;
-    tile = std::max(8, (tile + 7) / 8 * 8);
-    P.tile = tile;
-    P.tiles_x = (C.width + tile - 1) / tile;
-    P.tiles_y = (C.height + tile - 1) / tile;
-    P.n_tiles = P.tiles_x * P.tiles_y;
-    P.rank = a->params.rank;
-    P.nranks = a->params.nranks;
-    P.owned_tiles = P.n_tiles > P.rank ? (P.n_tiles - P.rank + P.nranks - 1) / P.nranks : 0;
-    P.items_per_chunk = (uint64_t)P.owned_tiles * tile * tile;
-}
-// Pixel j*W+i belongs to the accumulator's rank (tile_pixel in prt_device.h, inverted).
-std::vector<uint8_t> accum_owned(const PrtAccum* a) {
-    DCamera C;
-    DRenderParams P;
-    accum_layout(a, C, P);
-    std::vector<uint8_t> own((size_t)C.width * C.height, 0);
-    for (int py = 0; py < C.height; ++py)
-        for (int px = 0; px < C.width; ++px) {
-            const int tx = px / P.tile, ty = py / P.tile;
-            const int kx = ((tx - 3 * ty) % P.tiles_x + P.tiles_x) % P.tiles_x;
-            own[(size_t)py * C.width + px] = (ty * P.tiles_x + kx) % P.nranks == P.rank ? 1 : 0;
-        }
-    return own;
 }
 int not_adaptive(const PrtAccum* a, const char* who, const char* instead) {
     if (a && a->adaptive)
@@ -1773,21 +1731,14 @@ int accum_ready(PrtAccum* a, const char* who) {
     if (a->scene->device != a->device) return fail(PRT_E_INVALID, std::string(who) + ": the scene was uploaded to another device since the accumulator was created");
     return PRT_OK;
 }
-} // namespace
-
-extern "C" {
-
-} // extern "C"
-
-namespace {
 // Zeroed state of an accumulator (ad: adaptive, its batch already resolved and checked).
 hipError_t accum_zero(PrtAccum* a) {
     const size_t npx = a->n / 3;
-    hipError_t e = hipMemsetAsync(a->d_sum, 0, a->n * sizeof(double), nullptr);
-    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_moment, 0, npx * sizeof(double), nullptr);
-    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_count, 0, npx * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipEventRecord(a->done, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(a->done);
+    hipError_t e = hipMemsetAsync(a->d_sum.get(), 0, a->n * sizeof(double), nullptr);
+    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_moment.get(), 0, npx * sizeof(double), nullptr);
+    if (e == hipSuccess && a->adaptive) e = hipMemsetAsync(a->d_count.get(), 0, npx * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipEventRecord(a->done.get(), nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(a->done.get());
     return e;
 }
 
@@ -1828,24 +1779,24 @@ int accum_create(const char* who, PrtScene* s, const PrtCamera* cam, const PrtRe
     a->fingerprint = accum_fingerprint(s, *cam, *p, ad ? &A : nullptr);
     a->n = (size_t)cam->width * cam->height * 3;
     const size_t npx = a->n / 3;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->d_sum), a->n * sizeof(double));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
+    hipError_t e = dev_alloc(a->d_sum, a->n * sizeof(double));
+    if (e == hipSuccess) e = make_event(a->done, hipEventDisableTiming);
     if (a->adaptive) {
-        DCamera C;
-        DRenderParams P;
-        accum_layout(a, C, P);
-        const size_t items = std::max<size_t>(1, P.items_per_chunk), segs = std::max<uint32_t>(1, prt::adapt_segments(P.items_per_chunk));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_moment), npx * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_count), npx * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_list), items * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_seg), segs * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->d_active), sizeof(uint32_t));
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&a->h_active), sizeof(uint32_t), hipHostMallocDefault);
+        const uint64_t owned = TileLayout(*cam, *p).items_per_chunk;
+        const size_t items = std::max<size_t>(1, owned), segs = std::max<uint32_t>(1, prt::adapt_segments(owned));
+        if (e == hipSuccess) e = dev_alloc(a->d_moment, npx * sizeof(double));
+        if (e == hipSuccess) e = dev_alloc(a->d_count, npx * sizeof(uint32_t));
+        if (e == hipSuccess) e = dev_alloc(a->d_list, items * sizeof(int32_t));
+        if (e == hipSuccess) e = dev_alloc(a->d_seg, segs * sizeof(uint32_t));
+        if (e == hipSuccess) e = dev_alloc(a->d_active, sizeof(uint32_t));
+        void* h = nullptr;
+        if (e == hipSuccess && (e = hipHostMalloc(&h, sizeof(uint32_t), hipHostMallocDefault)) == hipSuccess)
+            a->h_active.reset(static_cast<uint32_t*>(h));
     }
     if (e == hipSuccess) e = accum_zero(a);
     if (e != hipSuccess) {
         prt_accum_destroy(a);
-        return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, w + ": " + hipGetErrorString(e));
+        return hip_fail(w, e);
     }
     *out = a;
     return PRT_OK;
@@ -1869,20 +1820,7 @@ int prt_accum_create_adaptive(PrtScene* s, const PrtCamera* cam, const PrtRender
 void prt_accum_destroy(PrtAccum* a) {
     if (!a) return;
     if (a->device >= 0) (void)hipSetDevice(a->device);
-    if (a->done) {
-        (void)hipEventSynchronize(a->done);
-        (void)hipEventDestroy(a->done);
-    }
-    if (a->d_sum) (void)hipFree(a->d_sum);
-    if (a->d_moment) (void)hipFree(a->d_moment);
-    if (a->d_count) (void)hipFree(a->d_count);
-    if (a->d_list) (void)hipFree(a->d_list);
-    if (a->d_seg) (void)hipFree(a->d_seg);
-    if (a->d_active) (void)hipFree(a->d_active);
-    if (a->h_active) (void)hipHostFree(a->h_active);
-    if (a->d_feat) (void)hipFree(a->d_feat);
-    if (a->d_res32) (void)hipFree(a->d_res32);
-    if (a->d_dn32) (void)hipFree(a->d_dn32);
+    if (a->done) (void)hipEventSynchronize(a->done.get()); // nothing is freed under a running pass
     delete a;
 }
 
@@ -1895,13 +1833,13 @@ int prt_accum_render(PrtAccum* a, int32_t n_samples, void* stream) {
     if (a->generation != a->scene->generation)
         return fail(PRT_E_INVALID, "prt_accum_render: the scene's vertices were updated since these sums were rendered (prt_accum_reset first)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
     RenderPass pass;
     pass.spp = n_samples;
     pass.first = (int32_t)a->samples;
-    pass.d_sum = a->d_sum;
+    pass.d_sum = a->d_sum.get();
     if ((rc = render_impl(a->scene, "prt_accum_render", &a->cam, &a->params, pass, nullptr, nullptr, 0, st))) return rc;
-    PRT_HIP(hipEventRecord(a->done, st));
+    PRT_HIP(hipEventRecord(a->done.get(), st));
     a->samples += (uint64_t)n_samples;
     return PRT_OK;
 }
@@ -1915,7 +1853,7 @@ int prt_accum_samples(const PrtAccum* a, uint64_t* n) {
 int prt_accum_reset(PrtAccum* a) {
     int rc = accum_ready(a, "prt_accum_reset");
     if (rc) return rc;
-    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
     PRT_HIP(accum_zero(a));
     a->samples = 0;
     a->generation = a->scene->generation;
@@ -1928,11 +1866,11 @@ int prt_accum_resolve(PrtAccum* a, void* d_rgb_f64, void* d_rgb_f32, void* d_rgb
     if (rc) return rc;
     if (!d_rgb_f64 && !d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, "prt_accum_resolve: no output buffer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
-    prt::launch_resolve(a->d_sum, a->n, a->samples, a->adaptive ? a->d_count : nullptr, static_cast<double*>(d_rgb_f64),
+    PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
+    prt::launch_resolve(a->d_sum.get(), a->n, a->samples, a->adaptive ? a->d_count.get() : nullptr, static_cast<double*>(d_rgb_f64),
                         static_cast<float*>(d_rgb_f32), static_cast<uint8_t*>(d_rgb_u8), st);
     PRT_HIP(hipGetLastError());
-    PRT_HIP(hipEventRecord(a->done, st));
+    PRT_HIP(hipEventRecord(a->done.get(), st));
     return PRT_OK;
 }
 
@@ -1940,30 +1878,22 @@ int prt_accum_read(PrtAccum* a, double* rgb_f64, float* rgb_f32) {
     int rc = accum_ready(a, "prt_accum_read");
     if (rc) return rc;
     if (!rgb_f64 && !rgb_f32) return fail(PRT_E_INVALID, "prt_accum_read: no output buffer");
-    void *d64 = nullptr, *d32 = nullptr;
-    hipError_t e = rgb_f64 ? hipMalloc(&d64, a->n * sizeof(double)) : hipSuccess;
-    if (e == hipSuccess && rgb_f32) e = hipMalloc(&d32, a->n * sizeof(float));
-    if (e == hipSuccess) {
-        rc = prt_accum_resolve(a, d64, d32, nullptr, nullptr);
-        if (rc == PRT_OK) {
-            e = hipEventSynchronize(a->done);
-            if (e == hipSuccess && rgb_f64) e = hipMemcpy(rgb_f64, d64, a->n * sizeof(double), hipMemcpyDeviceToHost);
-            if (e == hipSuccess && rgb_f32) e = hipMemcpy(rgb_f32, d32, a->n * sizeof(float), hipMemcpyDeviceToHost);
-        }
-    }
-    if (d64) (void)hipFree(d64);
-    if (d32) (void)hipFree(d32);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, std::string("prt_accum_read: ") + hipGetErrorString(e));
-    return PRT_OK;
+    Staging b;
+    void* d64 = rgb_f64 ? b.out(a->n * sizeof(double)) : nullptr;
+    void* d32 = rgb_f32 ? b.out(a->n * sizeof(float)) : nullptr;
+    if ((rc = b.status("prt_accum_read")) || (rc = prt_accum_resolve(a, d64, d32, nullptr, nullptr))) return rc;
+    b.sync(a->done.get());
+    if (rgb_f64) b.down(rgb_f64, d64, a->n * sizeof(double));
+    if (rgb_f32) b.down(rgb_f32, d32, a->n * sizeof(float));
+    return b.status("prt_accum_read");
 }
 
 int prt_accum_export(const PrtAccum* a, double* sums, uint64_t* samples, uint64_t* fingerprint) {
     if (!a || !sums || !samples || !fingerprint) return fail(PRT_E_INVALID, "prt_accum_export: null argument");
     if (int rc = not_adaptive(a, "prt_accum_export", "prt_accum_export_adaptive")) return rc;
     PRT_HIP(hipSetDevice(a->device));
-    PRT_HIP(hipEventSynchronize(a->done));
-    PRT_HIP(hipMemcpy(sums, a->d_sum, a->n * sizeof(double), hipMemcpyDeviceToHost));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
+    PRT_HIP(hipMemcpy(sums, a->d_sum.get(), a->n * sizeof(double), hipMemcpyDeviceToHost));
     *samples = a->samples;
     *fingerprint = a->fingerprint;
     return PRT_OK;
@@ -1976,8 +1906,8 @@ int prt_accum_import(PrtAccum* a, const double* sums, uint64_t samples, uint64_t
     if (fingerprint != a->fingerprint)
         return fail(PRT_E_INVALID, "prt_accum_import: fingerprint mismatch (other camera, render parameters or scene counts)");
     if (samples > (uint64_t)INT32_MAX) return fail(PRT_E_LIMIT, "prt_accum_import: more than INT32_MAX samples");
-    PRT_HIP(hipEventSynchronize(a->done));
-    PRT_HIP(hipMemcpy(a->d_sum, sums, a->n * sizeof(double), hipMemcpyHostToDevice));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
+    PRT_HIP(hipMemcpy(a->d_sum.get(), sums, a->n * sizeof(double), hipMemcpyHostToDevice));
     a->samples = samples;
     a->generation = a->scene->generation;
     return PRT_OK;
@@ -1995,11 +1925,13 @@ int prt_accum_render_adaptive(PrtAccum* a, int32_t n_samples, uint64_t* n_active
     if (a->generation != a->scene->generation)
         return fail(PRT_E_INVALID, "prt_accum_render_adaptive: the scene's vertices were updated since these sums were rendered (prt_accum_reset first)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
+    PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
     // (1) + (2): the active pixels, listed on the device; their number is the one value a round reads back
-    DCamera C;
+    DCamera C; // (the select maps owned item oi to its pixel as K3 does: the camera and the tile layout are what it reads)
+    prt::setup_camera(a->cam, C);
     DRenderParams P;
-    accum_layout(a, C, P);
+    std::memset(&P, 0, sizeof(P));
+    TileLayout(a->cam, a->params).set(P);
     DAdaptRule R;
     R.n = (uint32_t)a->samples;
     R.min_spp = (uint32_t)A.min_spp;
@@ -2007,14 +1939,14 @@ int prt_accum_render_adaptive(PrtAccum* a, int32_t n_samples, uint64_t* n_active
     R.batch = (uint32_t)A.batch;
     R.rel_tol = A.rel_tol;
     R.abs_tol = A.abs_tol;
-    prt::launch_adapt_select(C, P, R, a->d_sum, a->d_moment, a->d_count, a->d_seg, a->d_list, a->d_active, st);
+    prt::launch_adapt_select(C, P, R, a->d_sum.get(), a->d_moment.get(), a->d_count.get(), a->d_seg.get(), a->d_list.get(), a->d_active.get(), st);
     PRT_HIP(hipGetLastError());
-    PRT_HIP(hipMemcpyAsync(a->h_active, a->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PRT_HIP(hipMemcpyAsync(a->h_active.get(), a->d_active.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PRT_HIP(hipStreamSynchronize(st));
     const uint32_t listed = *a->h_active;
     if (listed > P.items_per_chunk) return fail(PRT_E_HIP, "prt_accum_render_adaptive: the select listed more pixels than are owned");
     if (listed == 0) {
-        PRT_HIP(hipEventRecord(a->done, st));
+        PRT_HIP(hipEventRecord(a->done.get(), st));
         return PRT_OK;
     }
     // (3) + (4): samples [n, n + k) of the listed pixels, at most PRT_MAX_CHUNKS batches per launch
@@ -2024,15 +1956,15 @@ int prt_accum_render_adaptive(PrtAccum* a, int32_t n_samples, uint64_t* n_active
         RenderPass pass;
         pass.spp = (int)std::min<int64_t>(per_launch, k - s0);
         pass.first = (int32_t)(a->samples + s0);
-        pass.d_sum = a->d_sum;
-        pass.d_list = a->d_list;
+        pass.d_sum = a->d_sum.get();
+        pass.d_list = a->d_list.get();
         pass.list_n = listed;
         pass.batch = A.batch;
-        pass.d_moment = a->d_moment;
-        pass.d_count = a->d_count;
+        pass.d_moment = a->d_moment.get();
+        pass.d_count = a->d_count.get();
         if ((rc = render_impl(a->scene, who, &a->cam, &a->params, pass, nullptr, nullptr, 0, st))) return rc;
     }
-    PRT_HIP(hipEventRecord(a->done, st));
+    PRT_HIP(hipEventRecord(a->done.get(), st));
     a->samples += (uint64_t)k;
     *n_active = listed;
     return PRT_OK;
@@ -2042,12 +1974,13 @@ int prt_accum_pixel_samples(PrtAccum* a, uint32_t* counts) {
     int rc = accum_ready(a, "prt_accum_pixel_samples");
     if (rc) return rc;
     if (!counts) return fail(PRT_E_INVALID, "prt_accum_pixel_samples: null argument");
-    PRT_HIP(hipEventSynchronize(a->done));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
     if (a->adaptive) {
-        PRT_HIP(hipMemcpy(counts, a->d_count, a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        PRT_HIP(hipMemcpy(counts, a->d_count.get(), a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     } else { // every owned pixel has every sample
-        const std::vector<uint8_t> own = accum_owned(a);
-        for (size_t i = 0; i < own.size(); ++i) counts[i] = own[i] ? (uint32_t)a->samples : 0u;
+        const TileLayout L(a->cam, a->params);
+        for (int y = 0; y < L.height; ++y)
+            for (int x = 0; x < L.width; ++x) counts[(size_t)y * L.width + x] = L.owns(x, y) ? (uint32_t)a->samples : 0u;
     }
     return PRT_OK;
 }
@@ -2057,10 +1990,10 @@ int prt_accum_export_adaptive(const PrtAccum* a, double* sums, double* moments, 
     if (!a || !sums || !moments || !counts || !samples || !fingerprint) return fail(PRT_E_INVALID, "prt_accum_export_adaptive: null argument");
     if (!a->adaptive) return fail(PRT_E_INVALID, "prt_accum_export_adaptive: not an adaptive accumulator (prt_accum_export)");
     PRT_HIP(hipSetDevice(a->device));
-    PRT_HIP(hipEventSynchronize(a->done));
-    PRT_HIP(hipMemcpy(sums, a->d_sum, a->n * sizeof(double), hipMemcpyDeviceToHost));
-    PRT_HIP(hipMemcpy(moments, a->d_moment, a->n / 3 * sizeof(double), hipMemcpyDeviceToHost));
-    PRT_HIP(hipMemcpy(counts, a->d_count, a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
+    PRT_HIP(hipMemcpy(sums, a->d_sum.get(), a->n * sizeof(double), hipMemcpyDeviceToHost));
+    PRT_HIP(hipMemcpy(moments, a->d_moment.get(), a->n / 3 * sizeof(double), hipMemcpyDeviceToHost));
+    PRT_HIP(hipMemcpy(counts, a->d_count.get(), a->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *samples = a->samples;
     *fingerprint = a->fingerprint;
     return PRT_OK;
@@ -2077,17 +2010,17 @@ int prt_accum_import_adaptive(PrtAccum* a, const double* sums, const double* mom
     if (samples > (uint64_t)INT32_MAX) return fail(PRT_E_LIMIT, "prt_accum_import_adaptive: more than INT32_MAX samples");
     if (samples > (uint64_t)a->ad.max_spp || samples % (uint64_t)a->ad.batch)
         return fail(PRT_E_INVALID, "prt_accum_import_adaptive: samples must be a multiple of batch and <= max_spp");
-    const std::vector<uint8_t> own = accum_owned(a);
-    for (size_t i = 0; i < own.size(); ++i) {
+    const TileLayout L(a->cam, a->params);
+    for (size_t i = 0; i < a->n / 3; ++i) {
         if (counts[i] > samples || counts[i] % (uint32_t)a->ad.batch)
             return fail(PRT_E_INVALID, "prt_accum_import_adaptive: a count above samples or not a multiple of batch");
-        if (!own[i] && counts[i]) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: samples on a pixel this rank does not own");
+        if (counts[i] && !L.owns((int)(i % L.width), (int)(i / L.width))) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: samples on a pixel this rank does not own");
         if (!std::isfinite(moments[i]) || moments[i] < 0) return fail(PRT_E_INVALID, "prt_accum_import_adaptive: a negative or non-finite moment");
     }
-    PRT_HIP(hipEventSynchronize(a->done));
-    PRT_HIP(hipMemcpy(a->d_sum, sums, a->n * sizeof(double), hipMemcpyHostToDevice));
-    PRT_HIP(hipMemcpy(a->d_moment, moments, a->n / 3 * sizeof(double), hipMemcpyHostToDevice));
-    PRT_HIP(hipMemcpy(a->d_count, counts, a->n / 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PRT_HIP(hipEventSynchronize(a->done.get()));
+    PRT_HIP(hipMemcpy(a->d_sum.get(), sums, a->n * sizeof(double), hipMemcpyHostToDevice));
+    PRT_HIP(hipMemcpy(a->d_moment.get(), moments, a->n / 3 * sizeof(double), hipMemcpyHostToDevice));
+    PRT_HIP(hipMemcpy(a->d_count.get(), counts, a->n / 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
     a->samples = samples;
     a->generation = a->scene->generation;
     return PRT_OK;
@@ -2142,7 +2075,7 @@ int features_impl(PrtScene* s, const std::string& w, const PrtCamera* cam, const
     if (!albedo && !normal && !depth && !prim) return fail(PRT_E_INVALID, w + ": no output buffer");
     DCamera C;
     prt::setup_camera(*cam, C);
-    prt::launch_features(s->d, C, prt::seed_key(p->seed), p->pixel_jitter ? 1 : 0, feature_spp, albedo, normal, depth, prim, st);
+    prt::launch_features(s->k64.d, C, prt::seed_key(p->seed), p->pixel_jitter ? 1 : 0, feature_spp, albedo, normal, depth, prim, st);
     PRT_HIP(hipGetLastError());
     return PRT_OK;
 }
@@ -2160,41 +2093,15 @@ int denoise_impl(PrtScene* s, const std::string& w, int32_t W, int32_t H, const 
         PRT_HIP(hipMemcpyAsync(out, rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
         return PRT_OK;
     }
-    const size_t need = prt::denoise_scratch_bytes(W, H);
-    if (!s->dn_done) PRT_HIP(hipEventCreateWithFlags(&s->dn_done, hipEventDisableTiming));
-    else PRT_HIP(hipStreamWaitEvent(st, s->dn_done, 0)); // the scratch is the previous call's until that call has ended
-    if (s->dn_cap < need) {
-        PRT_HIP(hipEventSynchronize(s->dn_done));
-        if (s->d_dn) (void)hipFree(s->d_dn);
-        s->d_dn = nullptr;
-        s->dn_cap = 0;
-        if (hipMalloc(&s->d_dn, need) != hipSuccess) return fail(PRT_E_OOM, w + ": hipMalloc of the filter scratch failed");
-        s->dn_cap = need;
-    }
+    PRT_HIP_AS(w, s->dn.reserve(prt::denoise_scratch_bytes(W, H), st));
     const float sigma[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
     prt::launch_denoise(W, H, static_cast<const float*>(rgb), static_cast<const float*>(albedo), static_cast<const float*>(normal),
-                        static_cast<const float*>(depth), p->iterations, p->demodulate, sigma, s->d_dn, static_cast<float*>(out), st);
+                        static_cast<const float*>(depth), p->iterations, p->demodulate, sigma, s->dn.get<void>(), static_cast<float*>(out), st);
     PRT_HIP(hipGetLastError());
-    PRT_HIP(hipEventRecord(s->dn_done, st));
+    PRT_HIP(s->dn.used(st));
     return PRT_OK;
 }
 
-// Device buffers of a host-side call, freed on every way out.
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    void* get(size_t bytes, hipError_t& e) {
-        void* q = nullptr;
-        if (e == hipSuccess) e = hipMalloc(&q, bytes);
-        if (q) p.push_back(q);
-        return q;
-    }
-};
-int hip_fail(const std::string& w, hipError_t e) {
-    return fail(e == hipErrorOutOfMemory ? PRT_E_OOM : PRT_E_HIP, w + ": " + hipGetErrorString(e));
-}
 } // namespace
 
 extern "C" {
@@ -2214,22 +2121,20 @@ int prt_render_features(PrtScene* s, const PrtCamera* cam, const PrtRenderParams
     if (rc) return rc;
     if (!cam || cam->width < 1 || cam->height < 1) return features_impl(s, w, cam, p, feature_spp, albedo, normal, depth, prim, nullptr);
     const size_t npx = (size_t)cam->width * cam->height;
-    DevBufs b;
-    hipError_t e = hipSuccess;
-    void* da = albedo ? b.get(npx * 3 * sizeof(float), e) : nullptr;
-    void* dn = normal ? b.get(npx * 3 * sizeof(float), e) : nullptr;
-    void* dz = depth ? b.get(npx * sizeof(float), e) : nullptr;
-    void* dp = prim ? b.get(npx * sizeof(int32_t), e) : nullptr;
-    if (e != hipSuccess) return hip_fail(w, e);
-    if ((rc = features_impl(s, w, cam, p, feature_spp, static_cast<float*>(da), static_cast<float*>(dn), static_cast<float*>(dz),
-                            static_cast<int32_t*>(dp), nullptr)))
+    Staging b;
+    void* da = albedo ? b.out(npx * 3 * sizeof(float)) : nullptr;
+    void* dn = normal ? b.out(npx * 3 * sizeof(float)) : nullptr;
+    void* dz = depth ? b.out(npx * sizeof(float)) : nullptr;
+    void* dp = prim ? b.out(npx * sizeof(int32_t)) : nullptr;
+    if ((rc = b.status(w)) || (rc = features_impl(s, w, cam, p, feature_spp, static_cast<float*>(da), static_cast<float*>(dn),
+                                                  static_cast<float*>(dz), static_cast<int32_t*>(dp), nullptr)))
         return rc;
-    e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess && albedo) e = hipMemcpy(albedo, da, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && normal) e = hipMemcpy(normal, dn, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && depth) e = hipMemcpy(depth, dz, npx * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && prim) e = hipMemcpy(prim, dp, npx * sizeof(int32_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? PRT_OK : hip_fail(w, e);
+    b.sync();
+    if (albedo) b.down(albedo, da, npx * 3 * sizeof(float));
+    if (normal) b.down(normal, dn, npx * 3 * sizeof(float));
+    if (depth) b.down(depth, dz, npx * sizeof(float));
+    if (prim) b.down(prim, dp, npx * sizeof(int32_t));
+    return b.status(w);
 }
 
 int prt_denoise_device(PrtScene* s, int32_t w, int32_t h, const void* d_rgb, const void* d_albedo, const void* d_normal,
@@ -2249,22 +2154,16 @@ int prt_denoise(PrtScene* s, int32_t w, int32_t h, const float* rgb, const float
     if ((uint64_t)w * (uint64_t)h >= (1ull << 31)) return fail(PRT_E_LIMIT, who + ": more than 2^31 pixels");
     if (!rgb || !albedo || !normal || !depth || !out) return fail(PRT_E_INVALID, who + ": null buffer");
     const size_t npx = (size_t)w * h, b3 = npx * 3 * sizeof(float), b1 = npx * sizeof(float);
-    DevBufs b;
-    hipError_t e = hipSuccess;
-    void* dc = b.get(b3, e);
-    void* da = b.get(b3, e);
-    void* dn = b.get(b3, e);
-    void* dz = b.get(b1, e);
-    void* dout = b.get(b3, e);
-    if (e == hipSuccess) e = hipMemcpy(dc, rgb, b3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(da, albedo, b3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dn, normal, b3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dz, depth, b1, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(who, e);
-    if ((rc = denoise_impl(s, who, w, h, dc, da, dn, dz, p, dout, nullptr))) return rc;
-    e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, b3, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? PRT_OK : hip_fail(who, e);
+    Staging b;
+    void* dc = b.in(rgb, b3);
+    void* da = b.in(albedo, b3);
+    void* dn = b.in(normal, b3);
+    void* dz = b.in(depth, b1);
+    void* dout = b.out(b3);
+    if ((rc = b.status(who)) || (rc = denoise_impl(s, who, w, h, dc, da, dn, dz, p, dout, nullptr))) return rc;
+    b.sync();
+    b.down(out, dout, b3);
+    return b.status(who);
 }
 
 int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
@@ -2275,11 +2174,11 @@ int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_r
     if (!d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, w + ": no output buffer");
     const size_t npx = a->n / 3;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PRT_HIP(hipStreamWaitEvent(st, a->done, 0));
-    if (!a->d_feat) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_feat), npx * 7 * sizeof(float)));
-    if (!a->d_res32) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_res32), a->n * sizeof(float)));
-    if (!d_rgb_f32 && !a->d_dn32) PRT_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_dn32), a->n * sizeof(float)));
-    float* alb = a->d_feat;
+    PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
+    if (!a->d_feat) PRT_HIP(dev_alloc(a->d_feat, npx * 7 * sizeof(float)));
+    if (!a->d_res32) PRT_HIP(dev_alloc(a->d_res32, a->n * sizeof(float)));
+    if (!d_rgb_f32 && !a->d_dn32) PRT_HIP(dev_alloc(a->d_dn32, a->n * sizeof(float)));
+    float* alb = a->d_feat.get();
     float* nrm = alb + a->n;
     float* dep = nrm + a->n;
     if (!a->feat_valid || a->feat_gen != a->scene->generation || a->feat_spp != p->feature_spp) {
@@ -2289,15 +2188,15 @@ int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_r
         a->feat_gen = a->scene->generation;
         a->feat_spp = p->feature_spp;
     }
-    prt::launch_resolve(a->d_sum, a->n, a->samples, a->adaptive ? a->d_count : nullptr, nullptr, a->d_res32, nullptr, st);
+    prt::launch_resolve(a->d_sum.get(), a->n, a->samples, a->adaptive ? a->d_count.get() : nullptr, nullptr, a->d_res32.get(), nullptr, st);
     PRT_HIP(hipGetLastError());
-    float* out = d_rgb_f32 ? static_cast<float*>(d_rgb_f32) : a->d_dn32;
-    if ((rc = denoise_impl(a->scene, w, a->cam.width, a->cam.height, a->d_res32, alb, nrm, dep, p, out, st))) return rc;
+    float* out = d_rgb_f32 ? static_cast<float*>(d_rgb_f32) : a->d_dn32.get();
+    if ((rc = denoise_impl(a->scene, w, a->cam.width, a->cam.height, a->d_res32.get(), alb, nrm, dep, p, out, st))) return rc;
     if (d_rgb_u8) {
         prt::launch_tonemap(out, a->n, static_cast<uint8_t*>(d_rgb_u8), st);
         PRT_HIP(hipGetLastError());
     }
-    PRT_HIP(hipEventRecord(a->done, st));
+    PRT_HIP(hipEventRecord(a->done.get(), st));
     return PRT_OK;
 }
 
@@ -2306,14 +2205,12 @@ int prt_accum_read_denoised(PrtAccum* a, const PrtDenoiseParams* p, float* rgb_f
     int rc = accum_ready(a, w.c_str());
     if (rc) return rc;
     if (!rgb_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
-    DevBufs b;
-    hipError_t e = hipSuccess;
-    void* d = b.get(a->n * sizeof(float), e);
-    if (e != hipSuccess) return hip_fail(w, e);
-    if ((rc = prt_accum_resolve_denoised(a, p, d, nullptr, nullptr))) return rc;
-    e = hipEventSynchronize(a->done);
-    if (e == hipSuccess) e = hipMemcpy(rgb_f32, d, a->n * sizeof(float), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? PRT_OK : hip_fail(w, e);
+    Staging b;
+    void* d = b.out(a->n * sizeof(float));
+    if ((rc = b.status(w)) || (rc = prt_accum_resolve_denoised(a, p, d, nullptr, nullptr))) return rc;
+    b.sync(a->done.get());
+    b.down(rgb_f32, d, a->n * sizeof(float));
+    return b.status(w);
 }
 
 } // extern "C"
