@@ -205,8 +205,17 @@ typedef struct PrtBvhInfo {
     uint32_t render_blocks_wanted;    /* ... the register allocation of the scene's material permutation leaves room for */
     uint32_t lds_materials, lds_light_nodes, lds_light_tris; /* shading tables K3 stages in LDS (0: read from global memory) */
     uint32_t stack_need;              /* traversal stack entries this tree can need (<= 40, the builders' bound) */
-    uint32_t reserved_;
+    /* which production instantiation of K3 a render of this scene launches: bits 0-7 the fp64 kernel, bits 8-15 the fp32 one
+     * (0 until the first PRT_PRECISION_F32 call has made the fp32 tables); each byte is a PRT_VARIANT_* word (0 before upload) */
+    uint32_t render_variant;
 } PrtBvhInfo;
+
+/* PrtBvhInfo.render_variant, per precision byte */
+#define PRT_VARIANT_PERM_MASK 0x07u /* material permutation: 0 lean, 1 textures, 2 Phong, 4 CookTorrance, 7 all of them */
+#define PRT_VARIANT_LLDS 0x08u      /* shading tables staged in LDS */
+#define PRT_VARIANT_PAD 0x10u       /* intersection records padded to one cache line each */
+#define PRT_VARIANT_EXTRA 0x20u     /* light tables or plain texel arrays (the scene's kernels compiled with both paths) */
+#define PRT_VARIANT_VALID 0x80u     /* the byte describes a kernel */
 
 typedef struct PrtScene PrtScene;
 

@@ -98,8 +98,12 @@ class PrtBvhInfo(C.Structure):
         ("lds_light_nodes", C.c_uint32),
         ("lds_light_tris", C.c_uint32),
         ("stack_need", C.c_uint32),
-        ("reserved_", C.c_uint32),
+        ("render_variant", C.c_uint32),
     ]
+
+
+# PrtBvhInfo.render_variant, per precision byte (prt.h PRT_VARIANT_*)
+VARIANT_PERM_MASK, VARIANT_LLDS, VARIANT_PAD, VARIANT_EXTRA, VARIANT_VALID = 0x07, 0x08, 0x10, 0x20, 0x80
 
 
 class PrtCamera(C.Structure):

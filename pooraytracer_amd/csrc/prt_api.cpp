@@ -426,6 +426,17 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
     return wanted;
 }
 
+// The PRT_VARIANT_* byte of the production K3 instantiation a render in precision R launches: the choice launch_render makes,
+// from the same fields.
+template <typename R>
+static uint32_t render_variant(const PrtScene* s, const KernelConfig<R>& k) {
+    const bool llds = k.mat_lds != 0 || k.ltri_lds != 0 || k.light_lds != 0;
+    const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
+    const bool extra = k.d.light_tab != nullptr || k.d.tex_compact != 0;
+    return PRT_VARIANT_VALID | ((uint32_t)s->feat & PRT_VARIANT_PERM_MASK) | (llds ? PRT_VARIANT_LLDS : 0u) |
+           (pad ? PRT_VARIANT_PAD : 0u) | (extra ? PRT_VARIANT_EXTRA : 0u);
+}
+
 // The host's tile layout of a frame (the device has its own copy: tile_pixel in prt_device.h).  tile_size 0 means 32, and
 // the tile is rounded up to a multiple of 8 (at least 8); tiles are dealt round-robin over the ranks in row-major order,
 // and tile row ty is rotated by 3 * ty.
@@ -661,7 +672,7 @@ int prt_scene_bvh_info(const PrtScene* s, PrtBvhInfo* out) {
     out->lds_light_nodes = up ? (uint32_t)s->k64.light_lds : 0u;
     out->lds_light_tris = up ? (uint32_t)s->k64.ltri_lds : 0u;
     out->stack_need = up ? (uint32_t)s->stack_need : 0u;
-    out->reserved_ = 0;
+    out->render_variant = up ? render_variant(s, s->k64) | (s->f32_ready ? render_variant(s, s->k32) << 8 : 0u) : 0u;
     return PRT_OK;
 }
 
@@ -1268,9 +1279,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     P.cached_min = 24; // measured: veach-mis -1 %, the others flat
     // (developer overrides of the wave scheduling thresholds through the environment, for sweeps)
     if (const char* e = dev_env("PRT_TUNE_CACHED_MIN")) P.cached_min = std::max(1, std::atoi(e)); // (0 would keep a wave passing for ever)
-    if (const char* e = dev_env("PRT_TUNE_KEEP")) P.keep = std::atoi(e);
-    if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::atoi(e);
-    if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::atoi(e);
+    if (const char* e = dev_env("PRT_TUNE_KEEP")) P.keep = std::min(64, std::max(0, std::atoi(e))); // (< 0 would keep a wave traversing once every lane is idle)
+    if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::min(64, std::max(1, std::atoi(e))); // (a batch is 1 to 64 lanes of a wave)
+    if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::min(64, std::max(0, std::atoi(e))); // (< 0 would never test the leaves of a wave whose lanes are all parked)
     if (const char* e = dev_env("PRT_TUNE_SCRAMBLE")) P.scramble = std::atoi(e) ? 1 : 0; // experiment: incoherent pixel order (PRT_ITEMS_FROM_LIST is set by adaptive rounds below and by prt_render_samples)
     const TileLayout L(*cam, *p);
     L.set(P);

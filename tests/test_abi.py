@@ -26,14 +26,16 @@ def test_header_symbols_all_exported(prt_lib):
 def test_struct_layouts_match_header(tmp_path):
     src = tmp_path / "sz.c"
     src.write_text(
-        '#include <stdio.h>\n#include "prt.h"\n#include "oracle.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+        '#include <stddef.h>\n#include <stdio.h>\n#include "prt.h"\n#include "oracle.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
         "sizeof(PrtMaterial),sizeof(PrtTexture),sizeof(PrtSceneDesc),sizeof(PrtCamera),sizeof(PrtRenderParams),"
         "sizeof(PrtRay),sizeof(PrtHit),sizeof(PrtLightSample),sizeof(PrtCounters),sizeof(PrtBvhInfo));"
         'printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n",sizeof(OrcMaterial),sizeof(OrcTexture),sizeof(OrcSceneDesc),'
-        "sizeof(OrcCamera),sizeof(OrcRenderParams),sizeof(OrcRay),sizeof(OrcHit),sizeof(OrcLightSample));return 0;}\n")
+        "sizeof(OrcCamera),sizeof(OrcRenderParams),sizeof(OrcRay),sizeof(OrcHit),sizeof(OrcLightSample));"
+        'printf("%zu %u %u %u %u %u\\n",offsetof(PrtBvhInfo,render_variant),PRT_VARIANT_PERM_MASK,PRT_VARIANT_LLDS,PRT_VARIANT_PAD,'
+        "PRT_VARIANT_EXTRA,PRT_VARIANT_VALID);return 0;}\n")
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "oracle"), str(src), "-o", str(exe)])
-    a, b = subprocess.check_output([str(exe)]).decode().strip().split("\n")
+    a, b, v = subprocess.check_output([str(exe)]).decode().strip().split("\n")
     prt_sizes = [int(x) for x in a.split()]
     orc_sizes = [int(x) for x in b.split()]
     py = [C.sizeof(t) for t in (_abi.PrtMaterial, _abi.PrtTexture, _abi.PrtSceneDesc, _abi.PrtCamera,
@@ -41,6 +43,9 @@ def test_struct_layouts_match_header(tmp_path):
                                 _abi.PrtBvhInfo)]
     assert prt_sizes == py
     assert orc_sizes == py[:8]
+    # the render-variant word: where the header puts it, and its bits
+    assert [int(x) for x in v.split()] == [_abi.PrtBvhInfo.render_variant.offset, _abi.VARIANT_PERM_MASK, _abi.VARIANT_LLDS,
+                                           _abi.VARIANT_PAD, _abi.VARIANT_EXTRA, _abi.VARIANT_VALID]
 
 
 def test_scene_create_and_light_order_without_gpu(prt_lib):
@@ -51,6 +56,7 @@ def test_scene_create_and_light_order_without_gpu(prt_lib):
     assert cnt["bvh_nodes"] >= 1 and cnt["bvh_depth"] <= 30
     info = sc.bvh_info()
     assert info["n_nodes"] == cnt["bvh_nodes"] and info["built_on_device"] == 0 and info["build_ms"] >= 0
+    assert info["render_variant"] == 0  # no kernel is chosen before upload
     sc.close()
     # PRT_SCENE_DEVICE_BVH defers the build to upload(): create succeeds without a GPU, nothing is built yet
     sc = api.Scene(scenes.tiny_scene(), device_bvh=True)

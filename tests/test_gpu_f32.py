@@ -80,6 +80,28 @@ def test_f32_hits_with_either_builder_and_a_deep_tree(gpu, device_bvh):
     check_hits_tier2(trace(sc, rays, F32), want)
 
 
+def oracle_tier2_reference(data, spp, **kw):
+    """The oracle's frame of `spp` samples per pixel and each pixel's per-sample standard deviation, (H, W, 3) each."""
+    cam = data.camera
+    px = np.stack(np.meshgrid(np.arange(cam.width), np.arange(cam.height)), -1).reshape(-1, 2)
+    samples = oracle.Oracle(data).render_samples(px, spp=spp, **kw)              # (pixels, spp, 3) radiance of every sample
+    ref = samples.mean(axis=1).reshape(cam.height, cam.width, 3)
+    sigma = samples.std(axis=1, ddof=1).reshape(cam.height, cam.width, 3)
+    return ref, sigma
+
+
+def check_image_tier2(img, ref, sigma, spp):
+    """An fp32 frame against the oracle's frame of the same seeds (oracle_tier2_reference), at the second tolerance tier."""
+    assert np.isfinite(img).all()
+    tol = 3.0 * sigma / np.sqrt(spp) + 1e-3 * np.maximum(1.0, np.abs(ref))
+    bad = (np.abs(img - ref) > tol).any(-1)
+    assert bad.mean() <= 1e-3, f"{bad.sum()} of {bad.size} pixels outside 3 sigma / sqrt(spp) + 1e-3"
+    assert abs(img.mean() - ref.mean()) <= 1e-3 * abs(ref.mean())
+    # the bulk of the pixels took exactly the oracle's paths: they agree to fp32 rounding, not merely statistically
+    close = (np.abs(img - ref) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all(-1)
+    assert close.mean() >= 0.97, float(close.mean())
+
+
 @pytest.mark.parametrize("scene_fn,spp,depth", [
     (lambda: scenes.cornell_box(ball_subdiv=2, width=48, height=48), 64, 10),
     (lambda: scenes.mixed_materials(40, 40), 64, 12),
@@ -89,21 +111,10 @@ def test_f32_hits_with_either_builder_and_a_deep_tree(gpu, device_bvh):
 def test_f32_images_within_tier2_of_the_oracle(gpu, scene_fn, spp, depth):
     data = scene_fn()
     cam = data.camera
-    orc = oracle.Oracle(data)
-    px = np.stack(np.meshgrid(np.arange(cam.width), np.arange(cam.height)), -1).reshape(-1, 2)
-    samples = orc.render_samples(px, spp=spp, max_depth=depth, seed=9)          # (pixels, spp, 3) radiance of every sample
-    ref = samples.mean(axis=1).reshape(cam.height, cam.width, 3)
-    sigma = samples.std(axis=1, ddof=1).reshape(cam.height, cam.width, 3)
+    ref, sigma = oracle_tier2_reference(data, spp, max_depth=depth, seed=9)
     sc = api.Scene(data).upload(gpu)
     img = sc.render(spp=spp, max_depth=depth, seed=9, precision=F32)
-    assert np.isfinite(img).all()
-    tol = 3.0 * sigma / np.sqrt(spp) + 1e-3 * np.maximum(1.0, np.abs(ref))
-    bad = (np.abs(img - ref) > tol).any(-1)
-    assert bad.mean() <= 1e-3, f"{bad.sum()} of {bad.size} pixels outside 3 sigma / sqrt(spp) + 1e-3"
-    assert abs(img.mean() - ref.mean()) <= 1e-3 * abs(ref.mean())
-    # the bulk of the pixels took exactly the oracle's paths: they agree to fp32 rounding, not merely statistically
-    close = (np.abs(img - ref) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all(-1)
-    assert close.mean() >= 0.97, float(close.mean())
+    check_image_tier2(img, ref, sigma, spp)
     cnt = sc.counters()
     assert cnt["samples"] == cam.width * cam.height * spp
 
