@@ -3,9 +3,10 @@
 // On the host the scene-graph classes are DESCRIPTORS: they carry the same public data and
 // constructors as the reference's, and Camera::Render flattens them into a PrtSceneDesc for the HIP
 // library (include/prt.h).  Intersection itself never runs on the host: the base Hittable::Hit /
-// Sample below forward single queries to the device through the same C ABI (K1 / k_sample_lights).
+// Occluded / Sample below forward single queries to the device through the same C ABI (K1 / k_sample_lights).
 #pragma once
 #include <memory>
+#include <vector>
 
 #include "AABB.h"
 #include "Math.h"
@@ -33,6 +34,11 @@ public:
     virtual ~Hittable();
     // world.Hit(ray, domain, record): one-ray batch through prt_trace_closest (device).
     virtual bool Hit(const Ray& ray, Interval domain, HitRecord& record) const;
+    // Hit's return value where the record is not wanted (shadow, visibility, line of sight): the any-hit query,
+    // prt_trace_occluded (device).  The batch form answers every ray over the one domain in ONE launch: out[i] for rays[i].
+    // Not virtual: nothing overrides them, and the vtable layout of existing clients stays as it was.
+    bool Occluded(const Ray& ray, Interval domain) const;
+    std::vector<bool> Occluded(const std::vector<Ray>& rays, Interval domain) const;
     virtual AABB BoundingBox() const = 0;
     // lights.Sample(origin, record, pdf): one sample through prt_sample_lights (device).
     virtual void Sample(const point3& origin, HitRecord& samplePointRecord, double& pdf) const;

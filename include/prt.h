@@ -11,6 +11,7 @@
  *                         (Mesh/Triangle ctor precompute Source/Triangle.cpp:11-53,
  *                          two-level BVHNode build Source/BVH.cpp:6-49, lights list main.cpp:40-45)
  *   prt_trace_closest     replaces world.Hit(ray, Interval(tmin,tmax), record)
+ *   prt_trace_occluded    the same call where only its bool result is wanted (any-hit)
  *                         (Source/HittableList.h:26-39 -> Source/BVH.cpp:51-61)
  *   prt_render            replaces Camera::Render(world, lights)      (Source/Camera.cpp:21-73)
  *   prt_render_device     same, framebuffer left in device memory for an RCCL reduce
@@ -265,6 +266,27 @@ int prt_trace_closest_device_prec(PrtScene* scene, const void* d_rays, size_t n,
  * more than it returns. */
 int prt_trace_closest_sorted_device(PrtScene* scene, const void* d_rays, size_t n, void* d_hits,
                                     int count_work, int precision, void* hip_stream);
+
+/* Any-hit occlusion queries: world.Hit(ray, Interval(tmin, tmax), record) != miss, for a batch.  occluded[i] = 1 iff some
+ * triangle is accepted in [rays[i].tmin, rays[i].tmax], else 0 — one byte per ray, nothing else is written (bytes beyond n
+ * stay as they are).  The any-hit form of K1: the traversal ends at the first accepted triangle and fetches neither the
+ * triangle's normal nor its shading record, so a visibility / shadow / line-of-sight test does not pay for a
+ * nearest-hit search and a PrtHit per ray.
+ * Contract: occluded[i] == (hits[i].prim >= 0) of prt_trace_closest_device_prec for the same ray record and the same
+ * precision, on EVERY ray — whichever builder made the tree, and whether or not the batch was sorted.  (A triangle is
+ * accepted by the same test against the same interval in both kernels; exact ties, which may change WHICH triangle the
+ * closest-hit call reports, cannot change a boolean.)
+ * Arguments, checks and error codes are those of the closest-hit calls: PRT_E_NO_DEVICE on a scene that is not uploaded,
+ * PRT_E_INVALID for a null buffer with n > 0, an unknown precision, or n >= 2^32 in the sorted call; n == 0 is PRT_OK.
+ * Afterwards prt_get_counters reports rays_shadow == n, rays_closest == 0, samples == 0 and kernel_ms (keys + sort + trace
+ * for the sorted call); with count_work != 0 also node_fetches / tri_tests / tri_full. */
+int prt_trace_occluded(PrtScene* scene, const PrtRay* rays, size_t n, uint8_t* occluded, int count_work);
+/* On device-resident buffers (d_rays: n PrtRay, d_occluded: n bytes); stream may be NULL. */
+int prt_trace_occluded_device(PrtScene* scene, const void* d_rays, size_t n, void* d_occluded,
+                              int count_work, int precision, void* hip_stream);
+/* K4 first, as prt_trace_closest_sorted_device: same bytes, the batch traced in a locality order. */
+int prt_trace_occluded_sorted_device(PrtScene* scene, const void* d_rays, size_t n, void* d_occluded,
+                                     int count_work, int precision, void* hip_stream);
 
 /* NEE point selection for (pixel, sample) keys 0..n-1 of `seed` from given origins (test hook). */
 int prt_sample_lights(PrtScene* scene, const double* origins, size_t n, uint64_t seed,

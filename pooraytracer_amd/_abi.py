@@ -235,6 +235,9 @@ EXPORTS = [
     "prt_trace_closest_device",
     "prt_trace_closest_device_prec",
     "prt_trace_closest_sorted_device",
+    "prt_trace_occluded",
+    "prt_trace_occluded_device",
+    "prt_trace_occluded_sorted_device",
     "prt_sample_lights",
     "prt_render",
     "prt_render_device",

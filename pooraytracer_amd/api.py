@@ -59,6 +59,9 @@ def load():
     L.prt_trace_closest_device.argtypes = [vp, vp, sz, vp, i32, vp]
     L.prt_trace_closest_device_prec.argtypes = [vp, vp, sz, vp, i32, i32, vp]
     L.prt_trace_closest_sorted_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
+    L.prt_trace_occluded.argtypes = [vp, vp, sz, vp, i32]
+    L.prt_trace_occluded_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
+    L.prt_trace_occluded_sorted_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
     L.prt_sample_lights.argtypes = [vp, vp, sz, u64, vp]
     L.prt_render.argtypes = [vp, vp, vp, vp, vp]
     L.prt_render_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
@@ -224,6 +227,18 @@ class Scene:
         first — the batch is traced in a locality order (same hits, for scenes that do not fit the caches)."""
         fn = self._L.prt_trace_closest_sorted_device if sort else self._L.prt_trace_closest_device_prec
         _check(fn(self._h, d_rays_ptr, n, d_hits_ptr, int(count_work), int(precision), stream))
+
+    def trace_occluded(self, rays, count_work=False):
+        """Any-hit query: uint8 [n], 1 where some triangle lies in the ray's [tmin, tmax] (== trace_closest's prim >= 0)."""
+        rays = np.ascontiguousarray(rays, dtype=_abi.RAY_DTYPE)
+        occ = np.zeros(rays.shape[0], dtype=np.uint8)
+        _check(self._L.prt_trace_occluded(self._h, rays.ctypes.data, rays.shape[0], occ.ctypes.data, int(count_work)), self._L)
+        return occ
+
+    def trace_occluded_device(self, d_rays_ptr, n, d_out_ptr, count_work=False, stream=None, precision=0, sort=False):
+        """The any-hit kernel on device buffers: one byte per ray into d_out_ptr; precision and sort as trace_closest_device."""
+        fn = self._L.prt_trace_occluded_sorted_device if sort else self._L.prt_trace_occluded_device
+        _check(fn(self._h, d_rays_ptr, n, d_out_ptr, int(count_work), int(precision), stream))
 
     def sample_lights(self, origins, seed=1):
         origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

@@ -29,6 +29,8 @@ int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
 void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, PrtHit* d_hits, DCounters* d_ctr, bool count, int n_cu,
                   hipStream_t st, const uint32_t* d_perm = nullptr);
+void launch_trace_occluded(const DScene& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
+                           int n_cu, hipStream_t st, const uint32_t* d_perm = nullptr);
 // K4 (ray_sort.hip): a permutation of a ray batch in which consecutive rays start close together
 size_t ray_sort_scratch_bytes(size_t n, std::string* err);
 const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
@@ -74,6 +76,8 @@ int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
 void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, PrtHit* d_hits, DCounters* d_ctr, bool count, int n_cu,
                   hipStream_t st, const uint32_t* d_perm = nullptr);
+void launch_trace_occluded(const Scene32& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
+                           int n_cu, hipStream_t st, const uint32_t* d_perm = nullptr);
 void launch_render(const Scene32& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
                    DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st);
 void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
@@ -1098,7 +1102,14 @@ int prt_trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_
     return prt_trace_closest_device_prec(s, d_rays, n, d_hits, count_work, PRT_PRECISION_F64, stream);
 }
 
-static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision, void* stream, bool sorted);
+// One body for the four device batch calls: `occluded` picks the any-hit kernel (d_out = one byte per ray) over the
+// closest-hit one (d_out = one PrtHit per ray); `who` names the public function in error messages.
+static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
+                              bool sorted, bool occluded, const char* who);
+static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision, void* stream, bool sorted) {
+    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, sorted, false,
+                              sorted ? "prt_trace_closest_sorted_device" : "prt_trace_closest_device");
+}
 int prt_trace_closest_device_prec(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                   void* stream) {
     return trace_closest_device(s, d_rays, n, d_hits, count_work, precision, stream, false);
@@ -1107,12 +1118,22 @@ int prt_trace_closest_sorted_device(PrtScene* s, const void* d_rays, size_t n, v
                                     void* stream) {
     return trace_closest_device(s, d_rays, n, d_hits, count_work, precision, stream, true);
 }
-static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision, void* stream, bool sorted) {
-    int rc = require_uploaded(s, "prt_trace_closest_device");
+int prt_trace_occluded_device(PrtScene* s, const void* d_rays, size_t n, void* d_occluded, int count_work, int precision,
+                              void* stream) {
+    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, false, true, "prt_trace_occluded_device");
+}
+int prt_trace_occluded_sorted_device(PrtScene* s, const void* d_rays, size_t n, void* d_occluded, int count_work, int precision,
+                                     void* stream) {
+    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, true, true,
+                              "prt_trace_occluded_sorted_device");
+}
+static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
+                              bool sorted, bool occluded, const char* who) {
+    int rc = require_uploaded(s, who);
     if (rc) return rc;
-    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, "prt_trace_closest_sorted_device: more than 2^32 - 1 rays in one batch");
-    if (n && (!d_rays || !d_hits)) return fail(PRT_E_INVALID, "prt_trace_closest_device: null buffer");
-    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, "prt_trace_closest_device: unsupported precision");
+    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, std::string(who) + ": more than 2^32 - 1 rays in one batch");
+    if (n && (!d_rays || !d_out)) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
+    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, std::string(who) + ": unsupported precision");
     if (precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipError_t we;
@@ -1123,7 +1144,7 @@ static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void*
         std::string err;
         const size_t need = prt::ray_sort_scratch_bytes(n, &err);
         if (!need) return fail(PRT_E_HIP, err);
-        PRT_HIP_AS("prt_trace_closest_sorted_device", s->sort.reserve(need, st));
+        PRT_HIP_AS(who, s->sort.reserve(need, st));
     }
     PRT_HIP(q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
     const uint32_t* d_perm = nullptr;
@@ -1133,15 +1154,22 @@ static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void*
                                s->sort.cap, st, &err);
         if (!d_perm) return fail(PRT_E_HIP, err);
     }
-    if (precision == PRT_PRECISION_F32)
-        prt32::launch_trace(s->k32.d, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr.get(),
-                            count_work != 0, s->n_cu, st, d_perm);
-    else
-        prt::launch_trace(s->k64.d, static_cast<const PrtRay*>(d_rays), n, static_cast<PrtHit*>(d_hits), q.d_ctr.get(),
-                          count_work != 0, s->n_cu, st, d_perm);
+    const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
+    const bool count = count_work != 0;
+    if (occluded) {
+        if (precision == PRT_PRECISION_F32)
+            prt32::launch_trace_occluded(s->k32.d, rays, n, static_cast<uint8_t*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
+        else
+            prt::launch_trace_occluded(s->k64.d, rays, n, static_cast<uint8_t*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
+    } else {
+        if (precision == PRT_PRECISION_F32)
+            prt32::launch_trace(s->k32.d, rays, n, static_cast<PrtHit*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
+        else
+            prt::launch_trace(s->k64.d, rays, n, static_cast<PrtHit*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
+    }
     PRT_HIP(hipGetLastError());
     PRT_HIP(q.stop(st));
-    PRT_HIP(q.finish(st, count_work != 0, 0));
+    PRT_HIP(q.finish(st, count, 0));
     if (d_perm) PRT_HIP(s->sort.used(st));
     return PRT_OK;
 }
@@ -1158,6 +1186,20 @@ int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, i
     b.sync();
     b.down(hits, dh, n * sizeof(PrtHit));
     return b.status("prt_trace_closest");
+}
+
+int prt_trace_occluded(PrtScene* s, const PrtRay* rays, size_t n, uint8_t* occluded, int count_work) {
+    int rc = require_uploaded(s, "prt_trace_occluded");
+    if (rc) return rc;
+    if (n == 0) return PRT_OK;
+    if (!rays || !occluded) return fail(PRT_E_INVALID, "prt_trace_occluded: null buffer");
+    Staging b;
+    void* dr = b.in(rays, n * sizeof(PrtRay));
+    void* dh = b.out(n);
+    if ((rc = b.status("prt_trace_occluded")) || (rc = prt_trace_occluded_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr))) return rc;
+    b.sync();
+    b.down(occluded, dh, n);
+    return b.status("prt_trace_occluded");
 }
 
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {

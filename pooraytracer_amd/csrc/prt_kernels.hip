@@ -189,6 +189,88 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1_WAVES) void k_trace_closest(DScen
     }
 }
 
+// ------------------------------------------------------------------------------------------- K1o
+// Any-hit form of K1: is some triangle accepted in the ray's [tmin, tmax]?  Same persistent waves, wave-local ray pool and
+// refill as k_trace_closest; the traversal ends at the first accepted triangle (Trav's any-hit mode, K3's shadow rays) and
+// the write-out is ONE byte per ray — no normal fetch, no barycentrics, no S.shade lookup.  The byte equals
+// (prim >= 0) of k_trace_closest for the same ray: a triangle is accepted by the same test against the same interval in
+// either kernel, the box tests only ever cull what cannot be accepted, and an exact tie cannot change a boolean.
+#ifndef PRT_K1O_KEEP
+#define PRT_K1O_KEEP PRT_K1_KEEP
+#endif
+#ifndef PRT_K1O_WAVES
+#define PRT_K1O_WAVES PRT_K1_WAVES
+#endif
+template <bool COUNT, bool PAD>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_K1O_WAVES) void k_trace_occluded(DScene S, const PrtRay* __restrict__ rays, size_t n,
+                                                               uint8_t* __restrict__ occluded, DCounters* ctr,
+                                                               const uint32_t* __restrict__ perm) { // K4's order (ray_sort.hip) or null
+    __shared__ uint32_t s_stack[PRT_BLOCK / 64][PRT_STACK_DEPTH][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t* stk = &s_stack[wave][0][lane];
+    WorkCount wc{0, 0, 0, 0, 0};
+    uint32_t nrays = 0;
+    Trav<PAD> tr;
+    tr.init(S, mk3(0, 0, 0), mk3(0, 0, 1), RL(0.0), RL(0.0));
+    tr.active = false;
+    bool have = false;
+    size_t my = 0;
+    unsigned long long pool_next = 0, pool_end = 0; // wave-local ray pool, as in K1
+    bool exhausted = false; // wave-uniform
+    for (;;) {
+        if (!tr.active && have) {
+            occluded[my] = tr.hit.tri >= 0 ? 1 : 0;
+            have = false;
+        }
+        {
+            const unsigned long long need = __ballot(!tr.active);
+            if (need != 0ULL && !exhausted) {
+                if (pool_next >= pool_end) {
+                    unsigned long long base = 0;
+                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
+                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
+                    pool_next = base;
+                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
+                    if (base >= (unsigned long long)n) exhausted = true;
+                }
+                if (!exhausted && !tr.active) {
+                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
+                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
+                    if (idx < pool_end) {
+                        const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
+                        const double4* rp = reinterpret_cast<const double4*>(rays + ri);
+                        const double4 r0 = rp[0], r1 = rp[1];
+                        tr.init(S, mk3((real)r0.x, (real)r0.y, (real)r0.z), mk3((real)r1.x, (real)r1.y, (real)r1.z), (real)r0.w, (real)r1.w);
+                        my = ri;
+                        have = true;
+                        nrays++;
+                    }
+                }
+                if (!exhausted) {
+                    const unsigned long long taken = (unsigned long long)__popcll(need);
+                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
+                }
+            }
+        }
+        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
+        do {
+            tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, /*any_hit=*/true);
+        } while (wave_count(tr.active) > PRT_K1O_KEEP);
+    }
+    unsigned long long a = wave_sum((unsigned long long)nrays);
+    unsigned long long b = wave_sum((unsigned long long)wc.nodes);
+    unsigned long long c = wave_sum((unsigned long long)wc.tris);
+    unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
+    if (lane == 0) {
+        atomicAdd(&ctr->rays_shadow, a);
+        if (COUNT) {
+            atomicAdd(&ctr->node_fetches, b);
+            atomicAdd(&ctr->tri_tests, c);
+            atomicAdd(&ctr->tri_full, f);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------- K3
 enum : int { ST_FETCH = 0, ST_NEW_SAMPLE = 1, ST_CLOSEST = 2, ST_SHADOW = 3, ST_DONE = 4, ST_PRIMARY = 5, ST_CACHED = 6 };
 // The camera ray of a pixel is the same for every sample (Camera.cpp:53-57: GetRay once per pixel, no jitter): K3 traces
@@ -1155,6 +1237,19 @@ void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, PrtHit* d_hit
     auto k = count ? (pad ? k_trace_closest<true, true> : k_trace_closest<true, false>)
                    : (pad ? k_trace_closest<false, true> : k_trace_closest<false, false>);
     hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, d_hits, d_ctr, d_perm);
+}
+
+// The any-hit batch: the same grid and PAD choice as launch_trace, one byte per ray out.
+void launch_trace_occluded(const DScene& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
+                           int n_cu, hipStream_t st, const uint32_t* d_perm) {
+    if (n == 0) return;
+    size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
+    const size_t per_cu = std::max<size_t>(1, (160u * 1024u) / (sizeof(uint32_t) * PRT_STACK_DEPTH * PRT_BLOCK)); // LDS stacks per CU
+    unsigned grid = (unsigned)std::min<size_t>(want, (size_t)n_cu * per_cu);
+    const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
+    auto k = count ? (pad ? k_trace_occluded<true, true> : k_trace_occluded<true, false>)
+                   : (pad ? k_trace_occluded<false, true> : k_trace_occluded<false, false>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, d_occluded, d_ctr, d_perm);
 }
 
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,

@@ -147,6 +147,23 @@ bool Hittable::Hit(const Ray& ray, Interval domain, HitRecord& record) const {
     return true;
 }
 
+std::vector<bool> Hittable::Occluded(const std::vector<Ray>& rays, Interval domain) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    std::vector<PrtRay> r(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        r[i].o[0] = rays[i].origin.x; r[i].o[1] = rays[i].origin.y; r[i].o[2] = rays[i].origin.z;
+        r[i].d[0] = rays[i].direction.x; r[i].d[1] = rays[i].direction.y; r[i].d[2] = rays[i].direction.z;
+        r[i].tmin = domain.min;
+        r[i].tmax = domain.max;
+    }
+    std::vector<uint8_t> occ(rays.size());
+    check(prt_trace_occluded(dc.scene, r.data(), r.size(), occ.data(), 0), "prt_trace_occluded");
+    return std::vector<bool>(occ.begin(), occ.end());
+}
+
+bool Hittable::Occluded(const Ray& ray, Interval domain) const { return Occluded(std::vector<Ray>(1, ray), domain)[0]; }
+
 void Hittable::Sample(const point3& origin, HitRecord& rec, double& pdf) const {
     DeviceCache& dc = Device();
     dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);

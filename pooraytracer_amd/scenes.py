@@ -392,6 +392,31 @@ def camera_rays(cam, n, seed=12345, tmin=1e-4, tmax=np.inf):
     return rays
 
 
+def surface_points(scene, n, rng):
+    """n points uniform by area on the scene's triangles."""
+    v = np.asarray(scene.vertices, dtype=np.float64)
+    cdf = np.cumsum(0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=-1))
+    tri = np.minimum(np.searchsorted(cdf, rng.random(n) * cdf[-1]), v.shape[0] - 1)
+    u, w = rng.random(n), rng.random(n)
+    flip = u + w > 1.0
+    u, w = np.where(flip, 1.0 - u, u), np.where(flip, 1.0 - w, w)
+    return v[tri, 0] + u[:, None] * (v[tri, 1] - v[tri, 0]) + w[:, None] * (v[tri, 2] - v[tri, 0])
+
+
+def shadow_segments(scene, n, seed=12345):
+    """K3's shadow-ray form: from one random surface point towards another, unit direction, over [1e-3, dist - 1e-3].
+    Pairs closer than 1e-2 are dropped (their interval would be next to empty), so slightly fewer than n rays may return."""
+    rng = np.random.default_rng(seed)
+    p, q = surface_points(scene, n, rng), surface_points(scene, n, rng)
+    dist = np.linalg.norm(q - p, axis=-1)
+    keep = dist > 1e-2
+    p, q, dist = p[keep], q[keep], dist[keep]
+    rays = np.zeros(p.shape[0], dtype=_abi.RAY_DTYPE)
+    rays["o"], rays["d"] = p, (q - p) / dist[:, None]
+    rays["tmin"], rays["tmax"] = 1e-3, dist - 1e-3
+    return rays
+
+
 def tiny_scene() -> SceneData:
     """A 64x64 cornell with a coarse ball: the smoke / unit-test workload (runs in ms on the CPU)."""
     return cornell_box(ball_subdiv=1, width=64, height=64)
