@@ -27,10 +27,8 @@ int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_dep
 int render_permutation(int feat);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, PrtHit* d_hits, DCounters* d_ctr, bool count, int n_cu,
-                  hipStream_t st, const uint32_t* d_perm = nullptr);
-void launch_trace_occluded(const DScene& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
-                           int n_cu, hipStream_t st, const uint32_t* d_perm = nullptr);
+void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
+                  int n_cu, hipStream_t st, const uint32_t* d_perm);
 // K4 (ray_sort.hip): a permutation of a ray batch in which consecutive rays start close together
 size_t ray_sort_scratch_bytes(size_t n, std::string* err);
 const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
@@ -74,10 +72,8 @@ typedef DSceneT<float> Scene32;
 int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, PrtHit* d_hits, DCounters* d_ctr, bool count, int n_cu,
-                  hipStream_t st, const uint32_t* d_perm = nullptr);
-void launch_trace_occluded(const Scene32& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
-                           int n_cu, hipStream_t st, const uint32_t* d_perm = nullptr);
+void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
+                  int n_cu, hipStream_t st, const uint32_t* d_perm);
 void launch_render(const Scene32& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
                    DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st);
 void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
@@ -1106,17 +1102,14 @@ int prt_trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_
 // closest-hit one (d_out = one PrtHit per ray); `who` names the public function in error messages.
 static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
                               bool sorted, bool occluded, const char* who);
-static int trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision, void* stream, bool sorted) {
-    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, sorted, false,
-                              sorted ? "prt_trace_closest_sorted_device" : "prt_trace_closest_device");
-}
 int prt_trace_closest_device_prec(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                   void* stream) {
-    return trace_closest_device(s, d_rays, n, d_hits, count_work, precision, stream, false);
+    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, false, false, "prt_trace_closest_device");
 }
 int prt_trace_closest_sorted_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                     void* stream) {
-    return trace_closest_device(s, d_rays, n, d_hits, count_work, precision, stream, true);
+    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, true, false,
+                              "prt_trace_closest_sorted_device");
 }
 int prt_trace_occluded_device(PrtScene* s, const void* d_rays, size_t n, void* d_occluded, int count_work, int precision,
                               void* stream) {
@@ -1156,17 +1149,10 @@ static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d
     }
     const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
     const bool count = count_work != 0;
-    if (occluded) {
-        if (precision == PRT_PRECISION_F32)
-            prt32::launch_trace_occluded(s->k32.d, rays, n, static_cast<uint8_t*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
-        else
-            prt::launch_trace_occluded(s->k64.d, rays, n, static_cast<uint8_t*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
-    } else {
-        if (precision == PRT_PRECISION_F32)
-            prt32::launch_trace(s->k32.d, rays, n, static_cast<PrtHit*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
-        else
-            prt::launch_trace(s->k64.d, rays, n, static_cast<PrtHit*>(d_out), q.d_ctr.get(), count, s->n_cu, st, d_perm);
-    }
+    if (precision == PRT_PRECISION_F32)
+        prt32::launch_trace(s->k32.d, rays, n, d_out, q.d_ctr.get(), count, occluded, s->n_cu, st, d_perm);
+    else
+        prt::launch_trace(s->k64.d, rays, n, d_out, q.d_ctr.get(), count, occluded, s->n_cu, st, d_perm);
     PRT_HIP(hipGetLastError());
     PRT_HIP(q.stop(st));
     PRT_HIP(q.finish(st, count, 0));
@@ -1174,32 +1160,29 @@ static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d
     return PRT_OK;
 }
 
-int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, int count_work) {
-    int rc = require_uploaded(s, "prt_trace_closest");
+// One body for the two host-buffer batch calls (fp64, unsorted): `elem` = bytes per ray of the output (a PrtHit, or the
+// any-hit byte); `who` names the public function in error messages, and its device call (`who`_device) does the work.
+static int trace_batch_host(PrtScene* s, const PrtRay* rays, size_t n, void* out, size_t elem, int count_work, bool occluded,
+                            const char* who) {
+    int rc = require_uploaded(s, who);
     if (rc) return rc;
     if (n == 0) return PRT_OK;
-    if (!rays || !hits) return fail(PRT_E_INVALID, "prt_trace_closest: null buffer");
+    if (!rays || !out) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
     Staging b;
     void* dr = b.in(rays, n * sizeof(PrtRay));
-    void* dh = b.out(n * sizeof(PrtHit));
-    if ((rc = b.status("prt_trace_closest")) || (rc = prt_trace_closest_device(s, dr, n, dh, count_work, nullptr))) return rc;
+    void* dh = b.out(n * elem);
+    const std::string dev = std::string(who) + "_device";
+    if ((rc = b.status(who)) || (rc = trace_batch_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr, false, occluded, dev.c_str())))
+        return rc;
     b.sync();
-    b.down(hits, dh, n * sizeof(PrtHit));
-    return b.status("prt_trace_closest");
+    b.down(out, dh, n * elem);
+    return b.status(who);
 }
-
+int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, int count_work) {
+    return trace_batch_host(s, rays, n, hits, sizeof(PrtHit), count_work, false, "prt_trace_closest");
+}
 int prt_trace_occluded(PrtScene* s, const PrtRay* rays, size_t n, uint8_t* occluded, int count_work) {
-    int rc = require_uploaded(s, "prt_trace_occluded");
-    if (rc) return rc;
-    if (n == 0) return PRT_OK;
-    if (!rays || !occluded) return fail(PRT_E_INVALID, "prt_trace_occluded: null buffer");
-    Staging b;
-    void* dr = b.in(rays, n * sizeof(PrtRay));
-    void* dh = b.out(n);
-    if ((rc = b.status("prt_trace_occluded")) || (rc = prt_trace_occluded_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr))) return rc;
-    b.sync();
-    b.down(occluded, dh, n);
-    return b.status("prt_trace_occluded");
+    return trace_batch_host(s, rays, n, occluded, 1, count_work, true, "prt_trace_occluded");
 }
 
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {

@@ -1,6 +1,6 @@
 // prt_kernels.hip — gfx950 kernels of the path-tracing hot path and their launchers.
 //
-//   K1 k_trace_closest   closest hit for a ray batch               (world.Hit, BVH.cpp:51-61)
+//   K1 k_trace           closest hit / any hit for a ray batch     (world.Hit, BVH.cpp:51-61)
 //   K3 k_render          persistent-wavefront path tracer          (Camera::Render/RayColor, Camera.cpp:21-204)
 //   K5 k_finalize        ordered sum of per-chunk partial sums -> f64 / f32 framebuffer
 //      k_sample_lights   lights.Sample test hook                   (BVH.cpp:62-67,86-100)
@@ -23,6 +23,8 @@
 //   * results are deterministic: per-sample keyed RNG, per-item partial sums combined in a fixed
 //     order by K5 (no float atomics on the framebuffer).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/prt.h"
 #include "prt_device.h"
@@ -99,9 +101,21 @@ __device__ __forceinline__ T wave_sum(T v) {
 // Persistent waves; every lane pulls its next ray from a global counter the moment its traversal
 // ends.  The stepping loop is left (and the finished lanes refilled) once no more than
 // PRT_K1_KEEP lanes are still traversing.
-template <bool COUNT, bool PAD>
-__global__ __launch_bounds__(PRT_BLOCK, PRT_K1_WAVES) void k_trace_closest(DScene S, const PrtRay* __restrict__ rays, size_t n,
-                                                             PrtHit* __restrict__ hits, DCounters* ctr,
+// ANY = false is the closest-hit batch (one PrtHit per ray; counter rays_closest).  ANY = true is its any-hit form (K1o):
+// is some triangle accepted in the ray's [tmin, tmax]?  The traversal ends at the first accepted triangle (Trav's any-hit
+// mode, K3's shadow rays) and the write-out is ONE byte per ray — no normal fetch, no barycentrics, no S.shade lookup
+// (counter rays_shadow; PRT_K1O_KEEP / PRT_K1O_WAVES, K1's values unless set).  The byte equals (prim >= 0) of the
+// closest-hit kernel for the same ray: a triangle is accepted by the same test against the same interval in either
+// form, the box tests only ever cull what cannot be accepted, and an exact tie cannot change a boolean.
+#ifndef PRT_K1O_KEEP
+#define PRT_K1O_KEEP PRT_K1_KEEP
+#endif
+#ifndef PRT_K1O_WAVES
+#define PRT_K1O_WAVES PRT_K1_WAVES
+#endif
+template <bool COUNT, bool PAD, bool ANY>
+__global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void k_trace(DScene S, const PrtRay* __restrict__ rays, size_t n,
+                                                             typename std::conditional<ANY, uint8_t, PrtHit>::type* __restrict__ out, DCounters* ctr,
                                                              const uint32_t* __restrict__ perm) { // K4's order (ray_sort.hip) or null
     __shared__ uint32_t s_stack[PRT_BLOCK / 64][PRT_STACK_DEPTH][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,7 +124,7 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1_WAVES) void k_trace_closest(DScen
     uint32_t nrays = 0;
     Trav<PAD> tr;
     tr.init(S, mk3(0, 0, 0), mk3(0, 0, 1), RL(0.0), RL(0.0));
-    tr.hit.alpha = tr.hit.beta = RL(0.0);
+    if (!ANY) tr.hit.alpha = tr.hit.beta = RL(0.0);
     tr.active = false;
     bool have = false;
     size_t my = 0;
@@ -119,26 +133,28 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1_WAVES) void k_trace_closest(DScen
     unsigned long long pool_next = 0, pool_end = 0;
     bool exhausted = false; // wave-uniform
     for (;;) {
-        if (!tr.active) {
-            if (have) {
-                PrtHit out;
+        if (!tr.active && have) {
+            if constexpr (ANY) {
+                out[my] = tr.hit.tri >= 0 ? 1 : 0;
+            } else {
+                PrtHit h;
                 if (tr.hit.tri >= 0) {
                     const DTri* T = tri_at<PAD>(S, (uint32_t)tr.hit.tri);
                     const d3 nrm = mk3(T->n[0], T->n[1], T->n[2]);
-                    out.t = tr.hit.t;
-                    out.alpha = tr.hit.alpha;
-                    out.beta = tr.hit.beta;
-                    out.prim = S.shade[tr.hit.tri].prim;
-                    out.front = dot(tr.d, nrm) < RL(0.) ? 1 : 0; // HitRecord::SetFaceNormal, Hittable.cpp:8-13
+                    h.t = tr.hit.t;
+                    h.alpha = tr.hit.alpha;
+                    h.beta = tr.hit.beta;
+                    h.prim = S.shade[tr.hit.tri].prim;
+                    h.front = dot(tr.d, nrm) < RL(0.) ? 1 : 0; // HitRecord::SetFaceNormal, Hittable.cpp:8-13
                 } else {
-                    out.t = PRT_INF;
-                    out.alpha = out.beta = 0;
-                    out.prim = -1;
-                    out.front = 0;
+                    h.t = PRT_INF;
+                    h.alpha = h.beta = 0;
+                    h.prim = -1;
+                    h.front = 0;
                 }
-                hits[my] = out;
-                have = false;
+                out[my] = h;
             }
+            have = false;
         }
         {
             const unsigned long long need = __ballot(!tr.active);
@@ -172,97 +188,15 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1_WAVES) void k_trace_closest(DScen
         }
         if (__ballot(tr.active || have) == 0ULL && exhausted) break;
         do {
-            tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, false);
-        } while (wave_count(tr.active) > PRT_K1_KEEP);
+            tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, ANY);
+        } while (wave_count(tr.active) > (ANY ? PRT_K1O_KEEP : PRT_K1_KEEP));
     }
     unsigned long long a = wave_sum((unsigned long long)nrays);
     unsigned long long b = wave_sum((unsigned long long)wc.nodes);
     unsigned long long c = wave_sum((unsigned long long)wc.tris);
     unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
     if (lane == 0) {
-        atomicAdd(&ctr->rays_closest, a);
-        if (COUNT) {
-            atomicAdd(&ctr->node_fetches, b);
-            atomicAdd(&ctr->tri_tests, c);
-            atomicAdd(&ctr->tri_full, f);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------- K1o
-// Any-hit form of K1: is some triangle accepted in the ray's [tmin, tmax]?  Same persistent waves, wave-local ray pool and
-// refill as k_trace_closest; the traversal ends at the first accepted triangle (Trav's any-hit mode, K3's shadow rays) and
-// the write-out is ONE byte per ray — no normal fetch, no barycentrics, no S.shade lookup.  The byte equals
-// (prim >= 0) of k_trace_closest for the same ray: a triangle is accepted by the same test against the same interval in
-// either kernel, the box tests only ever cull what cannot be accepted, and an exact tie cannot change a boolean.
-#ifndef PRT_K1O_KEEP
-#define PRT_K1O_KEEP PRT_K1_KEEP
-#endif
-#ifndef PRT_K1O_WAVES
-#define PRT_K1O_WAVES PRT_K1_WAVES
-#endif
-template <bool COUNT, bool PAD>
-__global__ __launch_bounds__(PRT_BLOCK, PRT_K1O_WAVES) void k_trace_occluded(DScene S, const PrtRay* __restrict__ rays, size_t n,
-                                                               uint8_t* __restrict__ occluded, DCounters* ctr,
-                                                               const uint32_t* __restrict__ perm) { // K4's order (ray_sort.hip) or null
-    __shared__ uint32_t s_stack[PRT_BLOCK / 64][PRT_STACK_DEPTH][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t* stk = &s_stack[wave][0][lane];
-    WorkCount wc{0, 0, 0, 0, 0};
-    uint32_t nrays = 0;
-    Trav<PAD> tr;
-    tr.init(S, mk3(0, 0, 0), mk3(0, 0, 1), RL(0.0), RL(0.0));
-    tr.active = false;
-    bool have = false;
-    size_t my = 0;
-    unsigned long long pool_next = 0, pool_end = 0; // wave-local ray pool, as in K1
-    bool exhausted = false; // wave-uniform
-    for (;;) {
-        if (!tr.active && have) {
-            occluded[my] = tr.hit.tri >= 0 ? 1 : 0;
-            have = false;
-        }
-        {
-            const unsigned long long need = __ballot(!tr.active);
-            if (need != 0ULL && !exhausted) {
-                if (pool_next >= pool_end) {
-                    unsigned long long base = 0;
-                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
-                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                    pool_next = base;
-                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
-                    if (base >= (unsigned long long)n) exhausted = true;
-                }
-                if (!exhausted && !tr.active) {
-                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
-                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
-                    if (idx < pool_end) {
-                        const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
-                        const double4* rp = reinterpret_cast<const double4*>(rays + ri);
-                        const double4 r0 = rp[0], r1 = rp[1];
-                        tr.init(S, mk3((real)r0.x, (real)r0.y, (real)r0.z), mk3((real)r1.x, (real)r1.y, (real)r1.z), (real)r0.w, (real)r1.w);
-                        my = ri;
-                        have = true;
-                        nrays++;
-                    }
-                }
-                if (!exhausted) {
-                    const unsigned long long taken = (unsigned long long)__popcll(need);
-                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-                }
-            }
-        }
-        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
-        do {
-            tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, /*any_hit=*/true);
-        } while (wave_count(tr.active) > PRT_K1O_KEEP);
-    }
-    unsigned long long a = wave_sum((unsigned long long)nrays);
-    unsigned long long b = wave_sum((unsigned long long)wc.nodes);
-    unsigned long long c = wave_sum((unsigned long long)wc.tris);
-    unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
-    if (lane == 0) {
-        atomicAdd(&ctr->rays_shadow, a);
+        atomicAdd(ANY ? &ctr->rays_shadow : &ctr->rays_closest, a);
         if (COUNT) {
             atomicAdd(&ctr->node_fetches, b);
             atomicAdd(&ctr->tri_tests, c);
@@ -1227,29 +1161,29 @@ int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_dep
     return nb;
 }
 
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, PrtHit* d_hits, DCounters* d_ctr, bool count,
+// One batch of rays through K1: `any_hit` picks the any-hit form (d_out = one byte per ray) over the closest-hit one
+// (d_out = one PrtHit per ray).
+void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
                   int n_cu, hipStream_t st, const uint32_t* d_perm) {
     if (n == 0) return;
     size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
     const size_t per_cu = std::max<size_t>(1, (160u * 1024u) / (sizeof(uint32_t) * PRT_STACK_DEPTH * PRT_BLOCK)); // LDS stacks per CU
     unsigned grid = (unsigned)std::min<size_t>(want, (size_t)n_cu * per_cu);
     const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
-    auto k = count ? (pad ? k_trace_closest<true, true> : k_trace_closest<true, false>)
-                   : (pad ? k_trace_closest<false, true> : k_trace_closest<false, false>);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, d_hits, d_ctr, d_perm);
-}
-
-// The any-hit batch: the same grid and PAD choice as launch_trace, one byte per ray out.
-void launch_trace_occluded(const DScene& S, const PrtRay* d_rays, size_t n, uint8_t* d_occluded, DCounters* d_ctr, bool count,
-                           int n_cu, hipStream_t st, const uint32_t* d_perm) {
-    if (n == 0) return;
-    size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
-    const size_t per_cu = std::max<size_t>(1, (160u * 1024u) / (sizeof(uint32_t) * PRT_STACK_DEPTH * PRT_BLOCK)); // LDS stacks per CU
-    unsigned grid = (unsigned)std::min<size_t>(want, (size_t)n_cu * per_cu);
-    const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
-    auto k = count ? (pad ? k_trace_occluded<true, true> : k_trace_occluded<true, false>)
-                   : (pad ? k_trace_occluded<false, true> : k_trace_occluded<false, false>);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, d_occluded, d_ctr, d_perm);
+    const int pick = (count ? 4 : 0) | (pad ? 2 : 0) | (any_hit ? 1 : 0);
+    auto go = [&](auto k, auto* out) { hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, out, d_ctr, d_perm); };
+    PrtHit* hits = static_cast<PrtHit*>(d_out);
+    uint8_t* bytes = static_cast<uint8_t*>(d_out);
+    switch (pick) {
+    case 0: return go(k_trace<false, false, false>, hits);
+    case 1: return go(k_trace<false, false, true>, bytes);
+    case 2: return go(k_trace<false, true, false>, hits);
+    case 3: return go(k_trace<false, true, true>, bytes);
+    case 4: return go(k_trace<true, false, false>, hits);
+    case 5: return go(k_trace<true, false, true>, bytes);
+    case 6: return go(k_trace<true, true, false>, hits);
+    default: return go(k_trace<true, true, true>, bytes);
+    }
 }
 
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,

@@ -6,6 +6,7 @@ answers are made unambiguous by the intervals: [tmin, t(1-m)] in front of the or
 contains it, with m far above the hit tolerance of the precision (1e-6 against 1e-12 in fp64, 1e-3 against 1e-5 in fp32).
 Every case runs on host-built and device-built trees."""
 import dataclasses
+import functools
 import os
 import subprocess
 
@@ -244,6 +245,26 @@ def test_argument_checks_on_an_uploaded_scene(gpu):
     with pytest.raises(api.PrtError) as e:
         sc.trace_occluded_device(d_r.data_ptr(), 1 << 32, d_o.data_ptr(), sort=True)
     assert e.value.code == _abi.PRT_E_INVALID
+    # the messages of the seven public batch calls, closest-hit and any-hit, name the call (prt_trace_closest_device_prec
+    # is prt_trace_closest_device with a precision and reports under that name)
+    fresh = api.Scene(scenes.tiny_scene())
+    d_h = torch.zeros((4, 4), dtype=torch.float64, device="cuda")
+    h_r, h_h, h_o = np.zeros(4, dtype=_abi.RAY_DTYPE), np.zeros(4, dtype=_abi.HIT_DTYPE), np.zeros(4, dtype=np.uint8)
+    L = sc._L
+    for fn, who, rays_ptr, out_ptr, tail in (
+            (L.prt_trace_closest, "prt_trace_closest", h_r.ctypes.data, h_h.ctypes.data, (0,)),
+            (L.prt_trace_closest_device, "prt_trace_closest_device", d_r.data_ptr(), d_h.data_ptr(), (0, None)),
+            (L.prt_trace_closest_device_prec, "prt_trace_closest_device", d_r.data_ptr(), d_h.data_ptr(), (0, 0, None)),
+            (L.prt_trace_closest_sorted_device, "prt_trace_closest_sorted_device", d_r.data_ptr(), d_h.data_ptr(), (0, 0, None)),
+            (L.prt_trace_occluded, "prt_trace_occluded", h_r.ctypes.data, h_o.ctypes.data, (0,)),
+            (L.prt_trace_occluded_device, "prt_trace_occluded_device", d_r.data_ptr(), d_o.data_ptr(), (0, 0, None)),
+            (L.prt_trace_occluded_sorted_device, "prt_trace_occluded_sorted_device", d_r.data_ptr(), d_o.data_ptr(), (0, 0, None))):
+        for args in ((None, 4, out_ptr), (rays_ptr, 4, None)):
+            assert fn(sc._h, *args, *tail) == _abi.PRT_E_INVALID, who
+            assert L.prt_last_error().decode() == who + ": null buffer"
+        assert fn(fresh._h, rays_ptr, 4, out_ptr, *tail) == _abi.PRT_E_NO_DEVICE, who
+        assert L.prt_last_error().decode() == who + ": scene is not uploaded to a HIP device (no CPU path exists)"
+    fresh.close()
     sc.close()
 
 
@@ -269,6 +290,49 @@ def test_counters_and_the_early_out(gpu, device_bvh):
               f"triangle tests {c_any['tri_tests']} / {c_cl['tri_tests']}")
         # any-hit can only stop earlier: this, not the equality of answers, shows the early-out is live
         assert c_any["node_fetches"] <= c_cl["node_fetches"]
+    sc.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny_intervals(m):
+    """A shuffled batch of the three kinds of _oracle_intervals rays on the tiny scene and the oracle's answer per ray;
+    an odd number of rays above the pool chunk: a wave refills its pool, and the last pool and the last wave are partial."""
+    before, upto, missed = _oracle_intervals(scenes.tiny_scene(), 1500, m, seed=81)
+    rays = np.concatenate([before, upto, missed])
+    lower = np.concatenate([np.zeros(before.shape[0]), before["tmax"], np.zeros(missed.shape[0])])  # t of a hit lies above it
+    want = np.concatenate([np.zeros(before.shape[0], bool), np.ones(upto.shape[0], bool), np.zeros(missed.shape[0], bool)])
+    n = rays.shape[0] - (rays.shape[0] % 2 == 0)
+    order = np.random.default_rng(83).permutation(rays.shape[0])[:n]
+    assert n > 2 * K1_CHUNK and n % 64 and want[order].any() and not want[order].all()
+    rays, lower, want = rays[order], lower[order], want[order]
+    for a in (rays, lower, want):
+        a.setflags(write=False)
+    return rays, lower, want
+
+
+@pytest.mark.parametrize("device_bvh", BUILDERS)
+@pytest.mark.parametrize("prec,m", [(_abi.PRECISION_F64, 1e-6), (_abi.PRECISION_F32, 1e-3)])
+def test_counting_kernels_on_padded_records(gpu, dev_lib, monkeypatch, prec, m, device_bvh):
+    """The counting instantiations on records padded to one per cache line (a layout only scenes beyond
+    PRT_TRI_PADDED_ABOVE get by themselves), closest-hit and any-hit, plain and sorted."""
+    monkeypatch.setenv("PRT_TUNE_TRI_STRIDE", "128")
+    rays, lower, want = _tiny_intervals(m)
+    n = rays.shape[0]
+    sc = api.Scene(scenes.tiny_scene(), device_bvh=device_bvh).upload(gpu)
+    assert sc.bvh_info()["tri_stride"] == 128
+    d_r = _dev(rays.copy())
+    for sort in (False, True):
+        h = _closest(sc, rays, precision=prec, sort=sort, count_work=True, d_r=d_r)
+        c = sc.counters()
+        assert c["rays_closest"] == n and c["rays_shadow"] == 0 and c["node_fetches"] > 0 and 0 < c["tri_full"] <= c["tri_tests"]
+        bad = int(((h["prim"] >= 0) != want).sum())
+        print(f"device_bvh={device_bvh} prec={prec} sort={sort}: {n} rays, {int(want.sum())} hits, mismatches {bad}")
+        assert bad == 0
+        assert (h["t"][want] > lower[want]).all() and (h["t"][want] <= rays["tmax"][want]).all() and np.isinf(h["t"][~want]).all()
+        got = _occluded(sc, rays, precision=prec, sort=sort, count_work=True, d_r=d_r)
+        c = sc.counters()
+        assert c["rays_shadow"] == n and c["rays_closest"] == 0 and c["node_fetches"] > 0 and c["tri_tests"] > 0
+        assert set(np.unique(got)) <= {0, 1} and np.array_equal(got.astype(bool), h["prim"] >= 0)
     sc.close()
 
 

@@ -1,5 +1,5 @@
 """Developer tool: K4 (sorted ray batches) against plain K1 on the 8M-triangle soup; run under rocprofv3 --kernel-trace --stats
-to see the phases (k_ray_keys, rocprim's sort kernels, k_trace_closest)."""
+to see the phases (k_ray_keys, rocprim's sort kernels, k_trace)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -39,7 +39,7 @@ def main():
         name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
         name = re.sub(r"\(anonymous namespace\)::", "", name)
         name = re.sub(r"\(.*", "", name).replace("void ", "")
-        if not show_all and not name.startswith(("k_render<false", "k_trace_closest<false")):
+        if not show_all and not name.startswith(("k_render<false", "k_trace<false")):
             continue
         print(f"{name:36s} VGPR {r.get('VGPRs', '?'):>4s} AGPR {r.get('AGPRs', '?'):>3s} spillV {r.get('VGPRs Spill', '?'):>3s} "
               f"spillS {r.get('SGPRs Spill', '?'):>3s} scratch {r.get('ScratchSize [bytes/lane]', '?'):>4s} "

@@ -7,13 +7,14 @@
                                     that launch, so bench.py can scale them to the launch it times
 
 Usage: python tools/summarize_profile.py <tag> <workload> [rays_per_launch]
-The timed kernel is k_render<false, ...> for the render workloads and k_trace_closest<false> for the ray
+The timed kernel is k_render<false, ...> for the render workloads and k_trace<false, PAD, /*ANY=*/false> for the ray
 microbenchmarks.  HBM bytes are corrected as MI355X_MICROARCH.md prescribes for gfx950:
 bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (FETCH_SIZE tallies 128-byte requests as 64 bytes)."""
 import csv
 import glob
 import json
 import os
+import re
 import shutil
 import sys
 
@@ -22,12 +23,12 @@ workload = sys.argv[2] if len(sys.argv) > 2 else "cornell-box"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "gpurun_out", f"prof_{tag}")
 dst = os.path.join(root, "profiles")
-kernel_key = "k_trace_closest<false" if workload.startswith("s") and "rays" in workload else "k_render<false"
+kernel_key = r"k_trace<false, \w+, false>" if workload.startswith("s") and "rays" in workload else r"k_render<false"  # a regular expression
 scene_key = "T<float>" if workload.endswith("-f32") else "T<double>"  # DSceneT<..> (K1) / RenderArgsT<..> (K3); the fp32 workloads also render one fp64 frame (their parity check)
 
 
 def timed(name):
-    return kernel_key in name and scene_key in name
+    return re.search(kernel_key, name) is not None and scene_key in name
 
 
 ks = glob.glob(os.path.join(src, "trace", "**", "*_kernel_stats.csv"), recursive=True)
