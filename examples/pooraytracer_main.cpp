@@ -1,7 +1,7 @@
 // pooraytracer_main.cpp — the reference's main.cpp (main.cpp:6-55) against the drop-in host API, with
 // the hard-coded scene name / spp / depth turned into arguments:
 //   pooraytracer_main <resources_dir> <scene_name> [spp=100] [depth=100] [out_dir=.] [out.f64] [--ladder=S1,S2,...]
-//                     [--adaptive=REL_TOL [--min-spp=M] [--counts=counts.u32]]
+//                     [--adaptive=REL_TOL [--min-spp=M] [--counts=counts.u32] [--denoise-guided[=ITER]]] [--denoise[=ITER]]
 // Reads <resources_dir>/<scene>/<scene>.obj|.mtl|.xml like the reference, renders on the GPU, writes
 // <scene>_spp<S>-depth<D>_<seconds>s.png + .hdr (main.cpp:52 naming, timestamp omitted).
 // --ladder (anywhere on the line): one progressive render (Camera::RenderProgressive) that writes a .png + .hdr per rung
@@ -15,6 +15,9 @@
 // --denoise[=ITER] (anywhere on the line): every frame written (plain, each --ladder rung, --adaptive) is also denoised
 // (Camera::Denoise: the library's default parameters, ITER a-trous levels in 1..10 when given) and written next to it as
 // <name>_denoised.png + .hdr.
+// --denoise-guided[=ITER] (anywhere on the line, with --adaptive= only): the adaptive frame is also put through the
+// variance-guided filter (Camera::DenoiseGuided: prt_denoise_guided_defaults, ITER levels in 1..10 when given), driven by the
+// per-pixel variance the adaptive render estimated, and written next to it as <name>_guided.png + .hdr.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -35,22 +38,29 @@ int main(int argc_all, char** argv_all) {
     std::vector<int> ladder;
     std::vector<char*> args;
     std::string adaptive, minSppArg, countsPath;
-    bool denoise = false;
-    int denoiseIter = 0; // 0: the library's default
+    bool denoise = false, denoiseGuided = false;
+    int denoiseIter = 0, guidedIter = 0; // 0: the library's default
+    // --NAME or --NAME=ITER, ITER in 1..10
+    auto levelsArg = [](const std::string& a, const std::string& name, int& iter) {
+        if (a == name) return true;
+        const std::string v = a.substr(name.size() + 1);
+        char* end = nullptr;
+        const long n = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end != '\0' || n < 1 || n > 10) {
+            std::fprintf(stderr, "error: %s wants a number of a-trous levels in 1..10, got '%s'\n", name.c_str(), v.c_str());
+            return false;
+        }
+        iter = (int)n;
+        return true;
+    };
     for (int i = 0; i < argc_all; ++i) {
         const std::string a = argv_all[i];
         if (i > 0 && (a == "--denoise" || a.rfind("--denoise=", 0) == 0)) {
             denoise = true;
-            if (a != "--denoise") {
-                const std::string v = a.substr(10);
-                char* end = nullptr;
-                const long n = std::strtol(v.c_str(), &end, 10);
-                if (v.empty() || *end != '\0' || n < 1 || n > 10) {
-                    std::fprintf(stderr, "error: --denoise wants a number of a-trous levels in 1..10, got '%s'\n", v.c_str());
-                    return 2;
-                }
-                denoiseIter = (int)n;
-            }
+            if (!levelsArg(a, "--denoise", denoiseIter)) return 2;
+        } else if (i > 0 && (a == "--denoise-guided" || a.rfind("--denoise-guided=", 0) == 0)) {
+            denoiseGuided = true;
+            if (!levelsArg(a, "--denoise-guided", guidedIter)) return 2;
         } else if (i > 0 && a.rfind("--adaptive=", 0) == 0) {
             adaptive = a.substr(11);
         } else if (i > 0 && a.rfind("--min-spp=", 0) == 0) {
@@ -90,8 +100,12 @@ int main(int argc_all, char** argv_all) {
             return 2;
         }
     }
+    if (denoiseGuided && adaptive.empty()) {
+        std::fprintf(stderr, "error: --denoise-guided needs --adaptive=REL_TOL (the variance comes from the adaptive accumulator's moments)\n");
+        return 2;
+    }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...] [--adaptive=REL_TOL [--min-spp=M] [--counts=FILE]] [--denoise[=ITER]]\n", argv_all[0]);
+        std::fprintf(stderr, "usage: %s resources_dir scene_name [spp] [depth] [out_dir] [out.f64] [--ladder=S1,S2,...] [--adaptive=REL_TOL [--min-spp=M] [--counts=FILE] [--denoise-guided[=ITER]]] [--denoise[=ITER]]\n", argv_all[0]);
         return 2;
     }
     try {
@@ -146,6 +160,15 @@ int main(int argc_all, char** argv_all) {
             const std::string png = outDir + "/" + fileName + "_adaptive" + adaptive + "_" + camera.GetParametersStr() + "_" + t + ".png";
             camera.WriteColorAttachment(png);
             writeDenoised(png);
+            if (denoiseGuided) {
+                PrtDenoiseParams dp;
+                prt_denoise_guided_defaults(&dp);
+                if (guidedIter > 0) dp.iterations = guidedIter;
+                camera.DenoiseGuided(world, &dp);
+                const std::string out = png.substr(0, png.size() - 4) + "_guided.png";
+                camera.WriteDenoisedAttachment(out);
+                std::printf("  variance-guided denoise (%d levels) -> %s\n", dp.iterations, out.c_str());
+            }
             double total = 0;
             for (const uint32_t n : counts) total += n;
             std::printf("%s: %dx%d adaptive rel_tol %s, spp %d..%d, %d rounds, mean %.1f samples per pixel, %.3f s (includes BVH build + upload) -> %s\n",

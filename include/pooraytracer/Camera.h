@@ -47,7 +47,7 @@ public:
     // first round renders minSpp samples, every later one roundSpp (0: minSpp).  minSpp, maxSpp and roundSpp are multiples
     // of batch (0: the library's default, PRT_ADAPTIVE_DEFAULT_BATCH).  On return colorAttachment holds the frame,
     // samplesPerPixel the largest per-pixel count, and `counts` (when given) the W*H counts, row by row.  Returns the number
-    // of rounds that rendered.  Single device only, like RenderProgressive.
+    // of rounds that rendered.  Single device only, like RenderProgressive.  It also fills varianceAttachment (below).
     int RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int minSpp, int maxSpp,
                        std::vector<uint32_t>* counts = nullptr, double absTol = 0.0, int batch = 0, int roundSpp = 0);
     // Addition (not in the reference): the edge-aware a-trous denoiser (prt.h prt_denoise) on colorAttachment, guided by the
@@ -56,6 +56,14 @@ public:
     // colorAttachment is left as it is.  Single device only, like RenderProgressive.
     std::vector<color> denoisedAttachment;
     void Denoise(Hittable& world, const PrtDenoiseParams* params = nullptr);
+    // Addition: the variance-guided form of the filter (prt.h prt_denoise_guided), whose colour tolerance is each pixel's
+    // own estimated standard deviation.  Valid after RenderAdaptive on the same world, which leaves the variance of every
+    // pixel's mean luminance in varianceAttachment (W*H, row by row); params NULL = prt_denoise_guided_defaults.  It fills
+    // denoisedAttachment.  RenderAdaptive's accumulator, which holds the moments, does not outlive the call, so the variance
+    // cannot be computed on demand here: every RenderAdaptive reads it back (one small kernel and a W*H float copy), whether
+    // DenoiseGuided follows or not.
+    std::vector<float> varianceAttachment;
+    void DenoiseGuided(Hittable& world, const PrtDenoiseParams* params = nullptr);
     // 8-bit sRGB PNG (+ Radiance .hdr), Camera.cpp:279-331
     void WriteColorAttachment(const std::string& outputPath, bool bWriteHDR = true) const;
     // The same for denoisedAttachment.
@@ -83,5 +91,7 @@ private:
     Hittable::DeviceCache& PrepareScene(Hittable& world, Hittable& lights, const std::vector<int>& devs, PrtCamera& c,
                                         PrtRenderParams& p);
     void FillParams(PrtCamera& c, PrtRenderParams& p) const;
+    // Denoise / DenoiseGuided: the features of this camera and the filter on colorAttachment, into denoisedAttachment
+    void DenoiseInto(Hittable& world, const PrtDenoiseParams* params, bool guided);
 };
 } // namespace Pooraytracer

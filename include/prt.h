@@ -25,6 +25,7 @@
  *                         the *_adaptive ones stop each pixel once its noise estimate meets a tolerance
  *   prt_render_features   first-hit albedo / normal / depth / triangle per pixel (the inputs of a denoiser)
  *   prt_denoise           edge-aware a-trous filter guided by those; prt_accum_*_denoised: an accumulator's frame, denoised
+ *   prt_denoise_guided    the same filter with SVGF-style colour weights from a per-pixel variance (prt_accum_variance)
  *
  * Conventions: every function returns 0 on success or a negative PRT_E_* code and never throws;
  * prt_last_error() returns a thread-local message for the last failure.  All input buffers are
@@ -547,6 +548,56 @@ int prt_denoise_device(PrtScene* scene, int32_t w, int32_t h, const void* d_rgb,
 int prt_accum_resolve_denoised(PrtAccum* acc, const PrtDenoiseParams* params, void* d_rgb_f32, void* d_rgb_u8, void* hip_stream);
 /* Synchronous: the denoised frame into a W*H*3 host buffer. */
 int prt_accum_read_denoised(PrtAccum* acc, const PrtDenoiseParams* params, float* rgb_f32);
+
+/*
+ * Variance-guided filter (the spatial colour weights of SVGF: Schied et al., HPG 2017), driven by the moments an adaptive
+ * accumulator keeps.  A pixel's colour tolerance is its own estimated standard deviation: a firefly has a large variance,
+ * accepts its calm neighbours and is pulled down; a lamp has a small one and stays sharp.
+ *
+ * Variance of the mean, from an adaptive accumulator (the quantities of the adaptive rule above): per pixel
+ *     var_mean = max(0, moment - S^2 / n_p) / (C - 1) / n_p,   C = n_p / batch,  S = Y(sum)
+ * in fp64 without fused multiply-adds, rounded to fp32; 0 where n_p == 0 (not owned, or nothing rendered).  It is the
+ * variance of the pixel's mean luminance, in the units of the resolved frame.  An adaptive accumulator with min_spp ==
+ * max_spp is a uniform render, so every user has the variance for the price of the moments.
+ *
+ * Filter: the inputs of prt_denoise plus a variance plane [h][w] (fp32).  A variance that is negative, NaN or infinite is
+ * taken as 0; with demodulate = 1 it is divided by Y(max(a, 1e-3))^2 on the way in and multiplied back on the way out.
+ * Level i (step 2^i, the 5x5 B3 taps and the tap-skipping rules of prt_denoise: taps outside the image, taps with a
+ * non-finite colour, and hit / miss pairs while the depth term is on):
+ *     g_p  = 3x3 binomial blur ((1,2,1) x (1,2,1) / 16) of the current variance plane around p, with step 1 at every
+ *            level, renormalised over the taps inside the image
+ *     e_c  = |Y(c_p) - Y(c_q)| / (sigma_color sqrt(g_p) + 1e-4)      (the kernel evaluates it as |Y(c_p - c_q)|: Y is
+ *            linear, so the two are equal, and in fp32 close colours subtract exactly before the weighting)
+ *     w    = h(dx) h(dy) exp(-(e_c + |n_p-n_q|^2 / sigma_normal^2 + Dz + |a_p-a_q|^2 / sigma_albedo^2))
+ *     c'_p = sum w c_q / sum w,    v'_p = sum w^2 v_q / (sum w)^2
+ * sigma_color multiplies the standard deviation and is NOT halved per level (the shrinking variance does that job);
+ * sigma_color <= 0 or +inf switches the colour term off.  A non-finite centre colour gives colour 0 and variance 0.
+ * iterations = 0 copies the colour and the sanitised variance.  The restatement in numpy is
+ * tests/denoise_guided_model.py.  fp32, deterministic; the scratch is prt_denoise's (the variance rides in the colour
+ * plane's fourth lane).
+ */
+/* prt_denoise_defaults with the guided filter's sigma_color and levels (tools/denoise_guided_timing.py). */
+void prt_denoise_guided_defaults(PrtDenoiseParams* p);
+/* Synchronous, host buffers; variance [h][w], out_variance [h][w] may be NULL.  PRT_E_INVALID for a null required buffer
+ * or an output that aliases an input. */
+int prt_denoise_guided(PrtScene* scene, int32_t w, int32_t h, const float* rgb, const float* variance, const float* albedo,
+                       const float* normal, const float* depth, const PrtDenoiseParams* params, float* out, float* out_variance);
+/* Same on device buffers, asynchronous on hip_stream; ordered with prt_denoise_device calls on the scene (one scratch). */
+int prt_denoise_guided_device(PrtScene* scene, int32_t w, int32_t h, const void* d_rgb, const void* d_variance,
+                              const void* d_albedo, const void* d_normal, const void* d_depth, const PrtDenoiseParams* params,
+                              void* d_out, void* d_out_variance, void* hip_stream);
+/* The variance of the mean of every pixel into a W*H fp32 device buffer, asynchronous on hip_stream.  PRT_E_INVALID for a
+ * plain accumulator (it keeps no moments) and before 2 * batch samples (a pixel needs two batches). */
+int prt_accum_variance(PrtAccum* acc, void* d_var_f32, void* hip_stream);
+/* Synchronous: the same into a W*H host buffer. */
+int prt_accum_read_variance(PrtAccum* acc, float* var_f32);
+/* prt_accum_resolve's fp32 frame and prt_accum_variance through prt_denoise_guided_device, with the cached features of
+ * prt_accum_resolve_denoised (one cache, the same invalidation).  Outputs as there.  PRT_E_INVALID as for
+ * prt_accum_variance, and for nranks > 1. */
+int prt_accum_resolve_denoised_guided(PrtAccum* acc, const PrtDenoiseParams* params, void* d_rgb_f32, void* d_rgb_u8,
+                                      void* hip_stream);
+/* Synchronous: the guided-denoised frame into a W*H*3 host buffer. */
+int prt_accum_read_denoised_guided(PrtAccum* acc, const PrtDenoiseParams* params, float* rgb_f32);
 
 #ifdef __cplusplus
 }

@@ -267,6 +267,13 @@ EXPORTS = [
     "prt_denoise_device",
     "prt_accum_resolve_denoised",
     "prt_accum_read_denoised",
+    "prt_denoise_guided_defaults",
+    "prt_denoise_guided",
+    "prt_denoise_guided_device",
+    "prt_accum_variance",
+    "prt_accum_read_variance",
+    "prt_accum_resolve_denoised_guided",
+    "prt_accum_read_denoised_guided",
 ]
 
 

@@ -95,6 +95,14 @@ def load():
     L.prt_denoise_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.prt_accum_resolve_denoised.argtypes = [vp, vp, vp, vp, vp]
     L.prt_accum_read_denoised.argtypes = [vp, vp, vp]
+    L.prt_denoise_guided_defaults.argtypes = [vp]
+    L.prt_denoise_guided_defaults.restype = None
+    L.prt_denoise_guided.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.prt_denoise_guided_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.prt_accum_variance.argtypes = [vp, vp, vp]
+    L.prt_accum_read_variance.argtypes = [vp, vp]
+    L.prt_accum_resolve_denoised_guided.argtypes = [vp, vp, vp, vp, vp]
+    L.prt_accum_read_denoised_guided.argtypes = [vp, vp, vp]
     if L.prt_abi_version() != _abi.PRT_ABI_VERSION and os.environ.get("PRT_ABI_ANY") != "1":  # (PRT_ABI_ANY: A/B tools timing an older build)
         raise PrtError(-101, "ABI version mismatch between _abi.py and libprt_hip.so")
     try:
@@ -140,11 +148,12 @@ def _f64(a, k):
     return np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)
 
 
-def denoise_params(L=None, **params):
-    """A PrtDenoiseParams: prt_denoise_defaults, then the given fields (iterations, demodulate, sigma_color, sigma_normal,
-    sigma_depth, sigma_albedo, feature_spp)."""
+def denoise_params(L=None, guided=False, **params):
+    """A PrtDenoiseParams: prt_denoise_defaults (guided: prt_denoise_guided_defaults), then the given fields (iterations,
+    demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo, feature_spp)."""
     p = _abi.PrtDenoiseParams()
-    (L or load()).prt_denoise_defaults(C.byref(p))
+    L = L or load()
+    (L.prt_denoise_guided_defaults if guided else L.prt_denoise_defaults)(C.byref(p))
     names = {f for f, _ in _abi.PrtDenoiseParams._fields_} - {"reserved"}
     for k, v in params.items():
         if k not in names:
@@ -156,6 +165,12 @@ def denoise_params(L=None, **params):
 def denoise_defaults():
     """prt_denoise_defaults as a dict."""
     p = denoise_params()
+    return {f: getattr(p, f) for f, _ in _abi.PrtDenoiseParams._fields_ if f != "reserved"}
+
+
+def denoise_guided_defaults():
+    """prt_denoise_guided_defaults as a dict."""
+    p = denoise_params(guided=True)
     return {f: getattr(p, f) for f, _ in _abi.PrtDenoiseParams._fields_ if f != "reserved"}
 
 
@@ -344,6 +359,35 @@ class Scene:
         _check(self._L.prt_denoise_device(self._h, int(width), int(height), d_rgb, d_albedo, d_normal, d_depth, C.byref(p), d_out,
                                          stream), self._L)
 
+    def denoise_guided(self, rgb, variance, features, return_variance=False, **params):
+        """The variance-guided a-trous filter (prt_denoise_guided) on host arrays: rgb and features as for denoise(), variance
+        (H, W) the variance of each pixel's mean luminance (AdaptiveAccumulator.variance()).  params: fields of
+        PrtDenoiseParams, else the guided defaults.  Returns (H, W, 3) float32, and with return_variance=True also the
+        filtered variance (H, W) float32."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"denoise_guided: rgb must have shape (H, W, 3), got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        v = np.ascontiguousarray(variance, dtype=np.float32)
+        a = np.ascontiguousarray(features["albedo"], dtype=np.float32)
+        n = np.ascontiguousarray(features["normal"], dtype=np.float32)
+        z = np.ascontiguousarray(features["depth"], dtype=np.float32)
+        if a.shape != rgb.shape or n.shape != rgb.shape or z.shape != rgb.shape[:2] or v.shape != rgb.shape[:2]:
+            raise ValueError(f"denoise_guided: shapes {v.shape} {a.shape} {n.shape} {z.shape} do not match rgb {rgb.shape}")
+        p = denoise_params(self._L, guided=True, **params)
+        out = np.empty_like(rgb)
+        vout = np.empty_like(v) if return_variance else None
+        _check(self._L.prt_denoise_guided(self._h, w, h, rgb.ctypes.data, v.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
+                                         C.byref(p), out.ctypes.data, vout.ctypes.data if return_variance else None), self._L)
+        return (out, vout) if return_variance else out
+
+    def denoise_guided_device(self, width, height, d_rgb, d_variance, d_albedo, d_normal, d_depth, d_out, d_out_variance=None,
+                              stream=None, **params):
+        """prt_denoise_guided_device: asynchronous, on device buffers (raw pointers; d_out_variance may be None)."""
+        p = denoise_params(self._L, guided=True, **params)
+        _check(self._L.prt_denoise_guided_device(self._h, int(width), int(height), d_rgb, d_variance, d_albedo, d_normal, d_depth,
+                                                C.byref(p), d_out, d_out_variance, stream), self._L)
+
     def tonemap_srgb8(self, d_f32_ptr, width, height, d_u8_ptr, stream=None):
         _check(self._L.prt_tonemap_srgb8(self._h, d_f32_ptr, width, height, d_u8_ptr, stream), self._L)
 
@@ -437,6 +481,31 @@ class Accumulator:
         """Asynchronous prt_accum_resolve_denoised into device buffers (raw pointers)."""
         p = denoise_params(self._L, **params)
         _check(self._L.prt_accum_resolve_denoised(self._h, C.byref(p), d_f32_ptr, d_u8_ptr, stream), self._L)
+
+    def denoised_guided(self, **params):
+        """The frame of the samples so far through the variance-guided filter (prt_accum_read_denoised_guided): (H, W, 3)
+        float32.  params: fields of PrtDenoiseParams, else the guided defaults.  Adaptive accumulators only (a plain one keeps
+        no moments: PrtError), after at least two batches."""
+        p = denoise_params(self._L, guided=True, **params)
+        out = np.zeros(self._shape, dtype=np.float32)
+        _check(self._L.prt_accum_read_denoised_guided(self._h, C.byref(p), out.ctypes.data), self._L)
+        return out
+
+    def resolve_denoised_guided(self, d_f32_ptr=None, d_u8_ptr=None, stream=None, **params):
+        """Asynchronous prt_accum_resolve_denoised_guided into device buffers (raw pointers)."""
+        p = denoise_params(self._L, guided=True, **params)
+        _check(self._L.prt_accum_resolve_denoised_guided(self._h, C.byref(p), d_f32_ptr, d_u8_ptr, stream), self._L)
+
+    def variance(self, d_f32_ptr=None, stream=None):
+        """The variance of each pixel's mean luminance from the batch-means moments (prt_accum_read_variance): (H, W) float32,
+        0 where the pixel has no samples.  With d_f32_ptr: asynchronous prt_accum_variance into that device buffer instead.
+        Adaptive accumulators only, after at least two batches."""
+        if d_f32_ptr is not None:
+            _check(self._L.prt_accum_variance(self._h, d_f32_ptr, stream), self._L)
+            return None
+        out = np.zeros(self._shape[:2], dtype=np.float32)
+        _check(self._L.prt_accum_read_variance(self._h, out.ctypes.data), self._L)
+        return out
 
     def state(self):
         """Checkpoint: (sums (H, W, 3) float64, samples, fingerprint)."""

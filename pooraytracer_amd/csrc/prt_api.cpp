@@ -47,6 +47,8 @@ void launch_adapt_select(const DCamera& C, const DRenderParams& P, const DAdaptR
                          hipStream_t st);
 void launch_accumulate_list(const DRenderParams& P, const double* d_partial, const int32_t* d_list, uint32_t batch,
                             uint32_t samples, double* d_sum, double* d_moment, uint32_t* d_count, hipStream_t st);
+void launch_accum_variance(const double* d_sum, const double* d_moment, const uint32_t* d_count, size_t npx, uint32_t batch,
+                           float* d_var, hipStream_t st);
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
                           hipStream_t st);
 void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
@@ -55,6 +57,9 @@ void launch_features(const DScene& S, const DCamera& C, uint64_t seed_key, int j
 size_t denoise_scratch_bytes(int w, int h);
 void launch_denoise(int w, int h, const float* rgb, const float* albedo, const float* normal, const float* depth,
                     int iterations, int demod, const float sigma[4], void* scratch, float* out, hipStream_t st);
+void launch_denoise_guided(int w, int h, const float* rgb, const float* var, const float* albedo, const float* normal,
+                           const float* depth, int iterations, int demod, const float sigma[4], void* scratch, float* out,
+                           float* out_var, hipStream_t st);
 void launch_add_f32(float* dst, const float* src, size_t n, hipStream_t st);
 void launch_material_eval(const DScene& S, int material, const double* wi, const double* wo, const double* uv, size_t n,
                           uint64_t seed, double* out, hipStream_t st);
@@ -1725,6 +1730,7 @@ struct PrtAccum {
     int32_t feat_spp = 0;
     DevBuf<float> d_res32;
     DevBuf<float> d_dn32;
+    DevBuf<float> d_var32; // prt_accum_resolve_denoised_guided: the variance plane (W * H floats)
 };
 
 namespace {
@@ -2087,6 +2093,15 @@ void prt_denoise_defaults(PrtDenoiseParams* p) {
     p->reserved = 0;
 }
 
+void prt_denoise_guided_defaults(PrtDenoiseParams* p) {
+    if (!p) return;
+    prt_denoise_defaults(p);
+    // measured: tools/denoise_guided_timing.py, DESIGN.md §7 (the best point of its sweep around SVGF's published sigma_l = 4 and
+    // five levels, by mean log relMSE over cornell-box, veach-mis and bathroom2 at 16 and 64 spp)
+    p->iterations = 4;
+    p->sigma_color = 8.0f;
+}
+
 } // extern "C"
 
 namespace {
@@ -2116,26 +2131,134 @@ int features_impl(PrtScene* s, const std::string& w, const PrtCamera* cam, const
     return PRT_OK;
 }
 
-// The filter on device buffers through the scene's scratch.
-int denoise_impl(PrtScene* s, const std::string& w, int32_t W, int32_t H, const void* rgb, const void* albedo, const void* normal,
-                 const void* depth, const PrtDenoiseParams* p, void* out, hipStream_t st) {
+// What either form of the filter asks of its arguments, host or device pointers alike.  guided: the variance-guided form,
+// with `variance` in and `out_variance` (may be null) out; both are null for the plain filter.
+int check_denoise_args(const std::string& w, int32_t W, int32_t H, const void* rgb, const void* variance, const void* albedo,
+                       const void* normal, const void* depth, const PrtDenoiseParams* p, const void* out, const void* out_variance,
+                       bool guided) {
     int rc = check_denoise_params(p, w);
     if (rc) return rc;
     if (W < 1 || H < 1) return fail(PRT_E_INVALID, w + ": bad image size");
     if ((uint64_t)W * (uint64_t)H >= (1ull << 31)) return fail(PRT_E_LIMIT, w + ": more than 2^31 pixels");
-    if (!rgb || !albedo || !normal || !depth || !out) return fail(PRT_E_INVALID, w + ": null buffer");
-    const size_t npx = (size_t)W * H;
-    if (p->iterations == 0) {
-        PRT_HIP(hipMemcpyAsync(out, rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        return PRT_OK;
-    }
-    PRT_HIP_AS(w, s->dn.reserve(prt::denoise_scratch_bytes(W, H), st));
-    const float sigma[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
-    prt::launch_denoise(W, H, static_cast<const float*>(rgb), static_cast<const float*>(albedo), static_cast<const float*>(normal),
-                        static_cast<const float*>(depth), p->iterations, p->demodulate, sigma, s->dn.get<void>(), static_cast<float*>(out), st);
-    PRT_HIP(hipGetLastError());
-    PRT_HIP(s->dn.used(st));
+    if (!rgb || !albedo || !normal || !depth || !out || (guided && !variance)) return fail(PRT_E_INVALID, w + ": null buffer");
+    if (guided)
+        for (const void* in : {rgb, variance, albedo, normal, depth})
+            if (in == out || in == out_variance) return fail(PRT_E_INVALID, w + ": an output buffer aliases an input");
     return PRT_OK;
+}
+
+// The filter on device buffers through the scene's scratch; the arguments have passed check_denoise_args.
+int denoise_run(PrtScene* s, const std::string& w, int32_t W, int32_t H, const void* rgb, const void* variance, const void* albedo,
+                const void* normal, const void* depth, const PrtDenoiseParams* p, void* out, void* out_variance, bool guided,
+                hipStream_t st) {
+    const size_t npx = (size_t)W * H;
+    if (p->iterations == 0) PRT_HIP(hipMemcpyAsync(out, rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (p->iterations == 0 && !guided) return PRT_OK;
+    if (p->iterations > 0) PRT_HIP_AS(w, s->dn.reserve(prt::denoise_scratch_bytes(W, H), st));
+    const float sigma[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
+    if (guided)
+        prt::launch_denoise_guided(W, H, static_cast<const float*>(rgb), static_cast<const float*>(variance), static_cast<const float*>(albedo),
+                                   static_cast<const float*>(normal), static_cast<const float*>(depth), p->iterations, p->demodulate, sigma,
+                                   s->dn.get<void>(), static_cast<float*>(out), static_cast<float*>(out_variance), st);
+    else
+        prt::launch_denoise(W, H, static_cast<const float*>(rgb), static_cast<const float*>(albedo), static_cast<const float*>(normal),
+                            static_cast<const float*>(depth), p->iterations, p->demodulate, sigma, s->dn.get<void>(), static_cast<float*>(out), st);
+    PRT_HIP(hipGetLastError());
+    if (p->iterations > 0) PRT_HIP(s->dn.used(st));
+    return PRT_OK;
+}
+
+int denoise_impl(PrtScene* s, const std::string& w, int32_t W, int32_t H, const void* rgb, const void* variance, const void* albedo,
+                 const void* normal, const void* depth, const PrtDenoiseParams* p, void* out, void* out_variance, bool guided,
+                 hipStream_t st) {
+    int rc = check_denoise_args(w, W, H, rgb, variance, albedo, normal, depth, p, out, out_variance, guided);
+    return rc ? rc : denoise_run(s, w, W, H, rgb, variance, albedo, normal, depth, p, out, out_variance, guided, st);
+}
+
+// prt_denoise / prt_denoise_guided: the filter on host buffers, staged through the device.
+int denoise_host(PrtScene* s, const std::string& who, int32_t w, int32_t h, const float* rgb, const float* variance, const float* albedo,
+                 const float* normal, const float* depth, const PrtDenoiseParams* p, float* out, float* out_variance, bool guided) {
+    int rc = require_uploaded(s, who.c_str());
+    if (rc) return rc;
+    if ((rc = check_denoise_args(who, w, h, rgb, variance, albedo, normal, depth, p, out, out_variance, guided))) return rc;
+    const size_t npx = (size_t)w * h, b3 = npx * 3 * sizeof(float), b1 = npx * sizeof(float);
+    Staging b;
+    void* dc = b.in(rgb, b3);
+    void* dv = guided ? b.in(variance, b1) : nullptr;
+    void* da = b.in(albedo, b3);
+    void* dn = b.in(normal, b3);
+    void* dz = b.in(depth, b1);
+    void* dout = b.out(b3);
+    void* dvout = out_variance ? b.out(b1) : nullptr;
+    if ((rc = b.status(who)) || (rc = denoise_run(s, who, w, h, dc, dv, da, dn, dz, p, dout, dvout, guided, nullptr))) return rc;
+    b.sync();
+    b.down(out, dout, b3);
+    if (out_variance) b.down(out_variance, dvout, b1);
+    return b.status(who);
+}
+
+// What the variance of an accumulator needs: the moments of an adaptive one, and two batches in every rendered pixel
+// (min_spp >= 2 * batch, and the running pixels share the global count).
+int accum_variance_ready(const PrtAccum* a, const std::string& w) {
+    if (!a->adaptive) return fail(PRT_E_INVALID, w + ": a plain accumulator keeps no moments (use an adaptive one; min_spp == max_spp samples uniformly)");
+    if (a->samples < 2 * (uint64_t)a->ad.batch) return fail(PRT_E_INVALID, w + ": fewer than two batches of samples so far");
+    return PRT_OK;
+}
+
+// prt_accum_resolve_denoised[_guided]: the accumulator's fp32 frame (and, guided, its variance) through the filter, with
+// the cached features.
+int accum_resolve_denoised_impl(PrtAccum* a, const std::string& w, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream,
+                                bool guided) {
+    int rc = accum_ready(a, w.c_str());
+    if (rc || (rc = check_denoise_params(p, w))) return rc;
+    if (a->params.nranks > 1) return fail(PRT_E_INVALID, w + ": nranks > 1 (a tile share lacks its neighbours' pixels)");
+    if (!d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, w + ": no output buffer");
+    const size_t npx = a->n / 3;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (guided && (rc = accum_variance_ready(a, w))) return rc;
+    PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
+    if (guided) {
+        if (!a->d_var32) PRT_HIP(dev_alloc(a->d_var32, npx * sizeof(float)));
+        prt::launch_accum_variance(a->d_sum.get(), a->d_moment.get(), a->d_count.get(), npx, (uint32_t)a->ad.batch, a->d_var32.get(), st);
+        PRT_HIP(hipGetLastError());
+    }
+    if (!a->d_feat) PRT_HIP(dev_alloc(a->d_feat, npx * 7 * sizeof(float)));
+    if (!a->d_res32) PRT_HIP(dev_alloc(a->d_res32, a->n * sizeof(float)));
+    if (!d_rgb_f32 && !a->d_dn32) PRT_HIP(dev_alloc(a->d_dn32, a->n * sizeof(float)));
+    float* alb = a->d_feat.get();
+    float* nrm = alb + a->n;
+    float* dep = nrm + a->n;
+    if (!a->feat_valid || a->feat_gen != a->scene->generation || a->feat_spp != p->feature_spp) {
+        a->feat_valid = false;
+        if ((rc = features_impl(a->scene, w, &a->cam, &a->params, p->feature_spp, alb, nrm, dep, nullptr, st))) return rc;
+        a->feat_valid = true;
+        a->feat_gen = a->scene->generation;
+        a->feat_spp = p->feature_spp;
+    }
+    prt::launch_resolve(a->d_sum.get(), a->n, a->samples, a->adaptive ? a->d_count.get() : nullptr, nullptr, a->d_res32.get(), nullptr, st);
+    PRT_HIP(hipGetLastError());
+    float* out = d_rgb_f32 ? static_cast<float*>(d_rgb_f32) : a->d_dn32.get();
+    if ((rc = denoise_impl(a->scene, w, a->cam.width, a->cam.height, a->d_res32.get(), guided ? a->d_var32.get() : nullptr, alb, nrm, dep, p,
+                           out, nullptr, guided, st)))
+        return rc;
+    if (d_rgb_u8) {
+        prt::launch_tonemap(out, a->n, static_cast<uint8_t*>(d_rgb_u8), st);
+        PRT_HIP(hipGetLastError());
+    }
+    PRT_HIP(hipEventRecord(a->done.get(), st));
+    return PRT_OK;
+}
+
+int accum_read_denoised_impl(PrtAccum* a, const std::string& w, const PrtDenoiseParams* p, float* rgb_f32, bool guided) {
+    int rc = accum_ready(a, w.c_str());
+    if (rc) return rc;
+    if (!rgb_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
+    Staging b;
+    void* d = b.out(a->n * sizeof(float));
+    if ((rc = b.status(w)) || (rc = accum_resolve_denoised_impl(a, w, p, d, nullptr, nullptr, guided))) return rc;
+    b.sync(a->done.get());
+    b.down(rgb_f32, d, a->n * sizeof(float));
+    return b.status(w);
 }
 
 } // namespace
@@ -2177,76 +2300,71 @@ int prt_denoise_device(PrtScene* s, int32_t w, int32_t h, const void* d_rgb, con
                        const void* d_depth, const PrtDenoiseParams* p, void* d_out, void* stream) {
     int rc = require_uploaded(s, "prt_denoise_device");
     if (rc) return rc;
-    return denoise_impl(s, "prt_denoise_device", w, h, d_rgb, d_albedo, d_normal, d_depth, p, d_out, reinterpret_cast<hipStream_t>(stream));
+    return denoise_impl(s, "prt_denoise_device", w, h, d_rgb, nullptr, d_albedo, d_normal, d_depth, p, d_out, nullptr, false,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int prt_denoise_guided_device(PrtScene* s, int32_t w, int32_t h, const void* d_rgb, const void* d_variance, const void* d_albedo,
+                              const void* d_normal, const void* d_depth, const PrtDenoiseParams* p, void* d_out, void* d_out_variance,
+                              void* stream) {
+    int rc = require_uploaded(s, "prt_denoise_guided_device");
+    if (rc) return rc;
+    return denoise_impl(s, "prt_denoise_guided_device", w, h, d_rgb, d_variance, d_albedo, d_normal, d_depth, p, d_out, d_out_variance, true,
+                        reinterpret_cast<hipStream_t>(stream));
 }
 
 int prt_denoise(PrtScene* s, int32_t w, int32_t h, const float* rgb, const float* albedo, const float* normal, const float* depth,
                 const PrtDenoiseParams* p, float* out) {
-    const std::string who = "prt_denoise";
-    int rc = require_uploaded(s, who.c_str());
-    if (rc) return rc;
-    if ((rc = check_denoise_params(p, who))) return rc;
-    if (w < 1 || h < 1) return fail(PRT_E_INVALID, who + ": bad image size");
-    if ((uint64_t)w * (uint64_t)h >= (1ull << 31)) return fail(PRT_E_LIMIT, who + ": more than 2^31 pixels");
-    if (!rgb || !albedo || !normal || !depth || !out) return fail(PRT_E_INVALID, who + ": null buffer");
-    const size_t npx = (size_t)w * h, b3 = npx * 3 * sizeof(float), b1 = npx * sizeof(float);
-    Staging b;
-    void* dc = b.in(rgb, b3);
-    void* da = b.in(albedo, b3);
-    void* dn = b.in(normal, b3);
-    void* dz = b.in(depth, b1);
-    void* dout = b.out(b3);
-    if ((rc = b.status(who)) || (rc = denoise_impl(s, who, w, h, dc, da, dn, dz, p, dout, nullptr))) return rc;
-    b.sync();
-    b.down(out, dout, b3);
-    return b.status(who);
+    return denoise_host(s, "prt_denoise", w, h, rgb, nullptr, albedo, normal, depth, p, out, nullptr, false);
 }
 
-int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
-    const std::string w = "prt_accum_resolve_denoised";
+int prt_denoise_guided(PrtScene* s, int32_t w, int32_t h, const float* rgb, const float* variance, const float* albedo,
+                       const float* normal, const float* depth, const PrtDenoiseParams* p, float* out, float* out_variance) {
+    return denoise_host(s, "prt_denoise_guided", w, h, rgb, variance, albedo, normal, depth, p, out, out_variance, true);
+}
+
+int prt_accum_variance(PrtAccum* a, void* d_var_f32, void* stream) {
+    const std::string w = "prt_accum_variance";
     int rc = accum_ready(a, w.c_str());
-    if (rc || (rc = check_denoise_params(p, w))) return rc;
-    if (a->params.nranks > 1) return fail(PRT_E_INVALID, w + ": nranks > 1 (a tile share lacks its neighbours' pixels)");
-    if (!d_rgb_f32 && !d_rgb_u8) return fail(PRT_E_INVALID, w + ": no output buffer");
-    const size_t npx = a->n / 3;
+    if (rc) return rc;
+    if ((rc = accum_variance_ready(a, w))) return rc;
+    if (!d_var_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PRT_HIP(hipStreamWaitEvent(st, a->done.get(), 0));
-    if (!a->d_feat) PRT_HIP(dev_alloc(a->d_feat, npx * 7 * sizeof(float)));
-    if (!a->d_res32) PRT_HIP(dev_alloc(a->d_res32, a->n * sizeof(float)));
-    if (!d_rgb_f32 && !a->d_dn32) PRT_HIP(dev_alloc(a->d_dn32, a->n * sizeof(float)));
-    float* alb = a->d_feat.get();
-    float* nrm = alb + a->n;
-    float* dep = nrm + a->n;
-    if (!a->feat_valid || a->feat_gen != a->scene->generation || a->feat_spp != p->feature_spp) {
-        a->feat_valid = false;
-        if ((rc = features_impl(a->scene, w, &a->cam, &a->params, p->feature_spp, alb, nrm, dep, nullptr, st))) return rc;
-        a->feat_valid = true;
-        a->feat_gen = a->scene->generation;
-        a->feat_spp = p->feature_spp;
-    }
-    prt::launch_resolve(a->d_sum.get(), a->n, a->samples, a->adaptive ? a->d_count.get() : nullptr, nullptr, a->d_res32.get(), nullptr, st);
+    prt::launch_accum_variance(a->d_sum.get(), a->d_moment.get(), a->d_count.get(), a->n / 3, (uint32_t)a->ad.batch,
+                               static_cast<float*>(d_var_f32), st);
     PRT_HIP(hipGetLastError());
-    float* out = d_rgb_f32 ? static_cast<float*>(d_rgb_f32) : a->d_dn32.get();
-    if ((rc = denoise_impl(a->scene, w, a->cam.width, a->cam.height, a->d_res32.get(), alb, nrm, dep, p, out, st))) return rc;
-    if (d_rgb_u8) {
-        prt::launch_tonemap(out, a->n, static_cast<uint8_t*>(d_rgb_u8), st);
-        PRT_HIP(hipGetLastError());
-    }
     PRT_HIP(hipEventRecord(a->done.get(), st));
     return PRT_OK;
 }
 
-int prt_accum_read_denoised(PrtAccum* a, const PrtDenoiseParams* p, float* rgb_f32) {
-    const std::string w = "prt_accum_read_denoised";
+int prt_accum_read_variance(PrtAccum* a, float* var_f32) {
+    const std::string w = "prt_accum_read_variance";
     int rc = accum_ready(a, w.c_str());
     if (rc) return rc;
-    if (!rgb_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
+    if (!var_f32) return fail(PRT_E_INVALID, w + ": no output buffer");
     Staging b;
-    void* d = b.out(a->n * sizeof(float));
-    if ((rc = b.status(w)) || (rc = prt_accum_resolve_denoised(a, p, d, nullptr, nullptr))) return rc;
+    void* d = b.out(a->n / 3 * sizeof(float));
+    if ((rc = b.status(w)) || (rc = prt_accum_variance(a, d, nullptr))) return rc;
     b.sync(a->done.get());
-    b.down(rgb_f32, d, a->n * sizeof(float));
+    b.down(var_f32, d, a->n / 3 * sizeof(float));
     return b.status(w);
+}
+
+int prt_accum_resolve_denoised(PrtAccum* a, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
+    return accum_resolve_denoised_impl(a, "prt_accum_resolve_denoised", p, d_rgb_f32, d_rgb_u8, stream, false);
+}
+
+int prt_accum_read_denoised(PrtAccum* a, const PrtDenoiseParams* p, float* rgb_f32) {
+    return accum_read_denoised_impl(a, "prt_accum_read_denoised", p, rgb_f32, false);
+}
+
+int prt_accum_resolve_denoised_guided(PrtAccum* a, const PrtDenoiseParams* p, void* d_rgb_f32, void* d_rgb_u8, void* stream) {
+    return accum_resolve_denoised_impl(a, "prt_accum_resolve_denoised_guided", p, d_rgb_f32, d_rgb_u8, stream, true);
+}
+
+int prt_accum_read_denoised_guided(PrtAccum* a, const PrtDenoiseParams* p, float* rgb_f32) {
+    return accum_read_denoised_impl(a, "prt_accum_read_denoised_guided", p, rgb_f32, true);
 }
 
 } // extern "C"

@@ -905,6 +905,16 @@ PRT_DEV double luma(double r, double g, double b) {
     return 0.2126 * r + 0.7152 * g + 0.0722 * b;
 }
 
+// Batch means: the unbiased per-sample luminance variance of a pixel with c samples, var = max(0, moment - S^2 / c) /
+// (c / batch - 1); S = Y(sum) is returned too.  c >= 2 * batch.
+PRT_DEV double adapt_variance(const double* __restrict__ sum, const double* __restrict__ moment, uint32_t c, uint32_t batch,
+                              uint32_t pix, double& S) {
+#pragma clang fp contract(off)
+    S = luma(sum[(size_t)pix * 3], sum[(size_t)pix * 3 + 1], sum[(size_t)pix * 3 + 2]);
+    const double d = moment[pix] - S * S / (double)c;
+    return (d < 0.0 ? 0.0 : d) / (double)(c / batch - 1u);
+}
+
 // The activity rule: count == n, count < max_spp and not (count >= min_spp and converged).  Batch means: C = count / batch
 // batches of equal size, var = max(0, moment - S^2 / count) / (C - 1) estimates the per-sample luminance variance, and
 // the pixel has converged when sqrt(var / count) <= max(rel_tol |mean|, abs_tol).  Every comparison is false for NaN,
@@ -916,9 +926,8 @@ PRT_DEV bool adapt_active(const DAdaptRule& R, const double* __restrict__ sum, c
     if (c != R.n || c >= R.max_spp) return false;
     if (c < R.min_spp) return true;
     const double np = (double)c;
-    const double S = luma(sum[(size_t)pix * 3], sum[(size_t)pix * 3 + 1], sum[(size_t)pix * 3 + 2]);
-    const double d = moment[pix] - S * S / np;
-    const double var = (d < 0.0 ? 0.0 : d) / (double)(c / R.batch - 1u);
+    double S;
+    const double var = adapt_variance(sum, moment, c, R.batch, pix, S);
     const double se = sqrt(var / np);
     double thr = R.rel_tol * fabs(S / np);
     if (thr < R.abs_tol) thr = R.abs_tol;
@@ -987,6 +996,18 @@ __global__ void k_adapt_write(DCamera C, DRenderParams P, DAdaptRule R, const do
         for (uint32_t w = 0; w < wave; ++w) at += s_wave[w];
         if (a) list[at] = (int32_t)pix;
         __syncthreads(); // s_wave is reused by the next segment
+    }
+}
+
+// prt_accum_variance: the variance of each pixel's mean luminance, var / count in fp64 rounded to fp32; 0 where the count
+// is 0 (a pixel of another rank, or nothing rendered yet).
+__global__ void k_accum_variance(const double* __restrict__ sum, const double* __restrict__ moment, const uint32_t* __restrict__ count,
+                                 uint32_t npx, uint32_t batch, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t c = count[i];
+        double S;
+        out[i] = c ? (float)(adapt_variance(sum, moment, c, batch, (uint32_t)i, S) / (double)c) : 0.f;
     }
 }
 
@@ -1284,6 +1305,13 @@ void launch_accumulate_list(const DRenderParams& P, const double* d_partial, con
     if (P.items_per_chunk == 0) return;
     const unsigned grid = (unsigned)std::min<uint64_t>((P.items_per_chunk + 255) / 256, 2048);
     hipLaunchKernelGGL(k_accumulate_list, dim3(grid), dim3(256), 0, st, P, d_partial, d_list, batch, samples, d_sum, d_moment, d_count);
+}
+
+void launch_accum_variance(const double* d_sum, const double* d_moment, const uint32_t* d_count, size_t npx, uint32_t batch,
+                           float* d_var, hipStream_t st) {
+    if (npx == 0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((npx + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_accum_variance, dim3(grid), dim3(256), 0, st, d_sum, d_moment, d_count, (uint32_t)npx, batch, d_var);
 }
 
 void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,

@@ -506,6 +506,8 @@ int Camera::RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int
     check(prt_accum_read(acc, rgb.data(), nullptr), "prt_accum_read");
     colorAttachment.assign((size_t)imageWidth * imageHeight, color(0., 0., 0.));
     for (size_t i = 0; i < colorAttachment.size(); ++i) colorAttachment[i] = color(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
+    varianceAttachment.assign((size_t)imageWidth * imageHeight, 0.f);
+    check(prt_accum_read_variance(acc, varianceAttachment.data()), "prt_accum_read_variance");
     std::vector<uint32_t> n((size_t)imageWidth * imageHeight);
     check(prt_accum_pixel_samples(acc, n.data()), "prt_accum_pixel_samples");
     samplesPerPixel = n.empty() ? 0 : (int)*std::max_element(n.begin(), n.end());
@@ -692,14 +694,24 @@ void Camera::WriteDenoisedAttachment(const std::string& outputPath, bool bWriteH
     write_attachment(denoisedAttachment, imageWidth, imageHeight, outputPath, bWriteHDR);
 }
 
-void Camera::Denoise(Hittable& world, const PrtDenoiseParams* params) {
-    if (devices.size() > 1) throw std::invalid_argument("Camera::Denoise: one device only (`devices` lists several)");
+void Camera::Denoise(Hittable& world, const PrtDenoiseParams* params) { DenoiseInto(world, params, false); }
+
+void Camera::DenoiseGuided(Hittable& world, const PrtDenoiseParams* params) { DenoiseInto(world, params, true); }
+
+void Camera::DenoiseInto(Hittable& world, const PrtDenoiseParams* params, bool guided) {
+    const std::string who = guided ? "Camera::DenoiseGuided" : "Camera::Denoise";
+    if (devices.size() > 1) throw std::invalid_argument(who + ": one device only (`devices` lists several)");
     Hittable::DeviceCache& dc = world.Device();
-    if (!dc.scene) throw std::logic_error("Camera::Denoise: render this world first (Render, RenderProgressive or RenderAdaptive)");
+    if (!dc.scene)
+        throw std::logic_error(who + (guided ? ": render this world with RenderAdaptive first"
+                                             : ": render this world first (Render, RenderProgressive or RenderAdaptive)"));
     const size_t npx = (size_t)imageWidth * imageHeight;
-    if (colorAttachment.size() != npx) throw std::logic_error("Camera::Denoise: colorAttachment does not hold a frame of this size");
+    if (colorAttachment.size() != npx) throw std::logic_error(who + ": colorAttachment does not hold a frame of this size");
+    if (guided && varianceAttachment.size() != npx)
+        throw std::logic_error(who + ": varianceAttachment does not hold a frame of this size (RenderAdaptive fills it)");
     PrtDenoiseParams dp;
     if (params) dp = *params;
+    else if (guided) prt_denoise_guided_defaults(&dp);
     else prt_denoise_defaults(&dp);
     PrtCamera c;
     PrtRenderParams p;
@@ -711,7 +723,11 @@ void Camera::Denoise(Hittable& world, const PrtDenoiseParams* params) {
         rgb[i * 3 + 1] = (float)colorAttachment[i].y;
         rgb[i * 3 + 2] = (float)colorAttachment[i].z;
     }
-    check(prt_denoise(dc.scene, imageWidth, imageHeight, rgb.data(), albedo.data(), normal.data(), depth.data(), &dp, out.data()), "prt_denoise");
+    if (guided)
+        check(prt_denoise_guided(dc.scene, imageWidth, imageHeight, rgb.data(), varianceAttachment.data(), albedo.data(), normal.data(),
+                                 depth.data(), &dp, out.data(), nullptr), "prt_denoise_guided");
+    else
+        check(prt_denoise(dc.scene, imageWidth, imageHeight, rgb.data(), albedo.data(), normal.data(), depth.data(), &dp, out.data()), "prt_denoise");
     denoisedAttachment.assign(npx, color(0., 0., 0.));
     for (size_t i = 0; i < npx; ++i) denoisedAttachment[i] = color(out[i * 3], out[i * 3 + 1], out[i * 3 + 2]);
 }
