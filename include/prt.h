@@ -19,6 +19,8 @@
  *                         (replaces the std::thread row bands of Source/Camera.cpp:46-71)
  *   prt_sample_lights     replaces lights.Sample(origin, record, pdf) (Source/HittableList.h:44-59,
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
+ *   prt_scene_refit       new vertex positions for a resident scene: records and BVH boxes follow on the GPU, the tree's
+ *                         topology stays (the reference rebuilds its BVHNode graph instead, Source/BVH.cpp:7-48)
  *   prt_get_counters      rays / node fetches / triangle tests / kernel ms of the last call
  *   prt_accum_*           progressive, resumable rendering: the same frame built up over several calls
  *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel);
@@ -240,8 +242,65 @@ int prt_scene_upload(PrtScene* scene, int device);
  * precompute and the light tree; on an uploaded scene the BVH is REBUILT on the GPU (PRT_SCENE_DEVICE_BVH
  * path: 4 ms per 126k triangles, 17 ms per 8M).  Limitation: there is no topology-preserving refit (the
  * reference has none either — it rebuilds, Source/BVH.cpp:7-48); a caller that moves geometry every frame pays
- * the rebuild plus a re-upload of the triangle records each time. */
+ * the rebuild plus a re-upload of the triangle records each time.  (prt_scene_refit below is the in-place alternative for
+ * an uploaded scene whose emitters stay put.)  Replaces every host position: clears the stale mark prt_scene_refit_device sets. */
 int prt_scene_update_vertices(PrtScene* scene, const double* vertices, const double* normals);
+
+/*
+ * In-place geometry update of an UPLOADED scene with a BVH refit on the GPU: new positions for every triangle
+ * ([n_tris][3][xyz] fp64, the layout of PrtSceneDesc.vertices; normals in the same layout or NULL), the acceleration
+ * structure follows without a rebuild and nothing is reloaded.
+ *
+ * Scene state.  PRT_E_NO_DEVICE unless the scene is uploaded.  Topology, materials, texture coordinates, the leaf order
+ * and every node's refs stay as they are.  What changes is the geometry-derived data: the intersection records (the
+ * Triangle constructor precompute, Source/Triangle.cpp:11-53, incl. the degenerate-face fallback to the vertex normals),
+ * the tangent of the shading records, and the boxes of every resident node array (the 32-entry collapse of a deep
+ * host-built tree included: it shares the leaf order).  Host-built and device-built trees, 96- and 128-byte record
+ * strides.  Nothing is freed or re-uploaded: textures, materials, light tables, LDS sizing, render_variant, stack_need
+ * and n_nodes are untouched.  The first refit after an upload allocates its own working arrays (28 bytes per triangle,
+ * 8 per node) and keeps them.
+ * Grid.  The quantisation grid of the 16-bit boxes (origin, step, the slab test's scale) is recomputed from the new scene
+ * bounds on every refit by the builders' rule, so a scene that grows, shrinks or moves far away keeps tight,
+ * conservative boxes.
+ * Emitters do not move in this version: if a vertex of any triangle of a light mesh differs bitwise from the resident
+ * light triangle, the call fails with PRT_E_INVALID (use prt_scene_update_vertices, which rebuilds the light tree).
+ * A vertex coordinate that is not finite or beyond 1e18 is PRT_E_INVALID, as in prt_scene_update_vertices; the check
+ * runs on the device, where the coordinates are.
+ * All or nothing.  Both checks run in a read-only first phase over the new vertices, which also reduces the scene
+ * bounds; one small read-back then decides before anything resident is written.  A refused refit leaves the scene, its
+ * generation and its frames exactly as they were.  (A HIP error once the writing phases have been queued is no refusal:
+ * as in prt_scene_update_vertices the generation and the grid are already the new ones, the records may be partly
+ * rewritten, and the scene wants a prt_scene_update_vertices before it is used again.)
+ * Ordering.  That read-back is the ONE host synchronisation of a call (it waits for the first phase on hip_stream, not
+ * for the renders in flight).  The writing phases then wait, on hip_stream, for the in-flight work of both call slots and
+ * of the last prt_render_features* call, and every later call on any stream waits for the refit's end.  The vertex
+ * buffers must stay valid until the work on hip_stream has completed.
+ * Generation.  A successful refit bumps the scene's generation: accumulators and their feature caches behave as after
+ * prt_scene_update_vertices (PRT_E_INVALID until prt_accum_reset).
+ * fp32 tables, if they exist, are re-derived on the device from the new fp64 records.
+ * Host geometry.  prt_scene_refit (host pointers) also updates the scene's host triangles, so a later prt_scene_upload or
+ * prt_scene_update_vertices sees the new geometry (that upload builds a fresh tree on the GPU).  prt_scene_refit_device
+ * marks the host geometry stale: while it is, prt_scene_upload is refused with PRT_E_INVALID; prt_scene_update_vertices
+ * and prt_scene_refit replace every host position and clear the mark.
+ * Quality.  A refit keeps the tree's topology, so the tree decays as the geometry deforms; PrtRefitInfo.sah_ratio is the
+ * caller's signal that prt_scene_update_vertices (a rebuild) is due.  The library never rebuilds on its own.
+ * With PRT_TEST_DUMP_BVH (dev-hooks build) the refitted tree is dumped after every successful refit (synchronous).
+ */
+typedef struct PrtRefitInfo {
+    uint64_t refits;      /* successful refits since the last upload */
+    double records_ms;    /* hipEvent time of the last refit's triangle set-up (with the fp32 re-derivation, if any) */
+    double boxes_ms;      /* ... of its box refit over every resident node array, with the SAH reduction */
+    double sah_ratio;     /* SAH cost of the wide tree now / at the last build (node 1.0, triangle 1.5: the builders'
+                             constants); 1.0 before the first refit */
+    float grid_origin[3]; /* the current quantisation grid: box coordinate = grid_origin + q * grid_step */
+    float grid_step[3];
+    float slab_scale;     /* the largest extent of that grid (the slab test's pad scale) */
+    uint32_t host_stale;  /* 1 after prt_scene_refit_device until every host position is replaced */
+} PrtRefitInfo;
+int prt_scene_refit(PrtScene* scene, const double* vertices, const double* normals); /* host pointers */
+int prt_scene_refit_device(PrtScene* scene, const void* d_vertices, const void* d_normals, void* hip_stream);
+/* Synchronous: waits for the last refit's end (the times and the SAH ratio come from the device). */
+int prt_scene_refit_info(const PrtScene* scene, PrtRefitInfo* out);
 
 /* Number of light triangles and their order in the reference's area-CDF descent (BVH.cpp:86-100). */
 int prt_scene_bvh_info(const PrtScene* scene, PrtBvhInfo* out);

@@ -102,6 +102,19 @@ class PrtBvhInfo(C.Structure):
     ]
 
 
+class PrtRefitInfo(C.Structure):
+    _fields_ = [
+        ("refits", C.c_uint64),
+        ("records_ms", C.c_double),
+        ("boxes_ms", C.c_double),
+        ("sah_ratio", C.c_double),
+        ("grid_origin", C.c_float * 3),
+        ("grid_step", C.c_float * 3),
+        ("slab_scale", C.c_float),
+        ("host_stale", C.c_uint32),
+    ]
+
+
 # PrtBvhInfo.render_variant, per precision byte (prt.h PRT_VARIANT_*)
 VARIANT_PERM_MASK, VARIANT_LLDS, VARIANT_PAD, VARIANT_EXTRA, VARIANT_VALID = 0x07, 0x08, 0x10, 0x20, 0x80
 
@@ -228,6 +241,9 @@ EXPORTS = [
     "prt_scene_destroy",
     "prt_scene_upload",
     "prt_scene_update_vertices",
+    "prt_scene_refit",
+    "prt_scene_refit_device",
+    "prt_scene_refit_info",
     "prt_scene_bvh_info",
     "prt_scene_light_count",
     "prt_scene_light_order",

@@ -53,6 +53,9 @@ def load():
     L.prt_scene_upload.argtypes = [vp, i32]
     L.prt_scene_bvh_info.argtypes = [vp, vp]
     L.prt_scene_update_vertices.argtypes = [vp, vp, vp]
+    L.prt_scene_refit.argtypes = [vp, vp, vp]
+    L.prt_scene_refit_device.argtypes = [vp, vp, vp, vp]
+    L.prt_scene_refit_info.argtypes = [vp, vp]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
     L.prt_trace_closest.argtypes = [vp, vp, sz, vp, i32]
@@ -218,6 +221,45 @@ class Scene:
         n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
         _check(self._L.prt_scene_update_vertices(self._h, v.ctypes.data, None if n is None else n.ctypes.data), self._L)
         return self
+
+    def _refit_array(self, a, what):
+        """A caller's positions (or normals) as the C call wants them; shape and dtype errors are raised here, before any call."""
+        if not isinstance(a, np.ndarray):
+            raise TypeError(f"refit: {what} must be a numpy array, not {type(a).__name__}")
+        if a.dtype != np.float64:
+            raise TypeError(f"refit: {what} must be float64, not {a.dtype}")
+        if a.shape != self.data.vertices.shape:
+            raise ValueError(f"refit: {what} must have shape {self.data.vertices.shape}, not {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def refit(self, vertices, normals=None):
+        """New positions for the same triangles of an uploaded scene, in place: the records and the BVH's boxes follow on the
+        GPU, the tree keeps its topology and nothing is reloaded (prt_scene_refit).  Emitters must stay where they are."""
+        v = self._refit_array(vertices, "vertices")
+        n = None if normals is None else self._refit_array(normals, "normals")
+        _check(self._L.prt_scene_refit(self._h, v.ctypes.data, None if n is None else n.ctypes.data), self._L)
+        return self
+
+    def refit_device(self, d_vertices_ptr, d_normals_ptr=None, stream=None):
+        """The same from device memory: raw pointers to [n_tris][3][3] float64 arrays on the scene's device (e.g.
+        tensor.data_ptr() of a contiguous float64 tensor), asynchronous on `stream` after one small read-back.  The host
+        copy of the geometry goes stale: upload() is refused until update_vertices() or refit() has replaced every position."""
+        for name, p in (("d_vertices_ptr", d_vertices_ptr), ("d_normals_ptr", d_normals_ptr), ("stream", stream)):
+            if isinstance(p, bool) or not (p is None or isinstance(p, (int, np.integer))):
+                raise TypeError(f"refit_device: {name} must be an integer address or None, not {type(p).__name__}")
+        if not d_vertices_ptr and self.data.vertices.shape[0]:
+            raise ValueError("refit_device: d_vertices_ptr is null")
+        _check(self._L.prt_scene_refit_device(self._h, int(d_vertices_ptr or 0) or None, int(d_normals_ptr or 0) or None,
+                                              int(stream or 0) or None), self._L)
+        return self
+
+    def refit_info(self):
+        """PrtRefitInfo as a dict: refits since the upload, the last one's hipEvent times, the grid, sah_ratio (synchronous)."""
+        b = _abi.PrtRefitInfo()
+        _check(self._L.prt_scene_refit_info(self._h, C.byref(b)), self._L)
+        out = {f: getattr(b, f) for f, _ in _abi.PrtRefitInfo._fields_}
+        out["grid_origin"], out["grid_step"] = tuple(b.grid_origin), tuple(b.grid_step)
+        return out
 
     def bvh_info(self):
         b = _abi.PrtBvhInfo()

@@ -5,7 +5,8 @@ Every source is compiled to its own object (in parallel, only when it or a heade
   libprt_hip_dev.so  the same objects except prt_api.o, which is compiled with -DPRT_DEV_HOOKS=1: the PRT_TUNE_* / PRT_TEST_*
                      / PRT_VALIDATE_BVH hooks exist only there (failure-injection tests, sweep tools: api.dev_hooks()).
                      PRT_TEST_DUMP_BVH=<file> writes each scene's traversal tree (header, nodes, leaf order) when it is
-                     built: host trees at create and on a host rebuild, device trees at upload (tests/bvh_model.py reads it).
+                     built: host trees at create and on a host rebuild, device trees at upload, either after a refit
+                     (tests/bvh_model.py reads it).
 """
 import concurrent.futures
 import hashlib
@@ -18,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libprt_hip.so")
 DEV_LIB = os.path.join(HERE, "libprt_hip_dev.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["prt_api.cpp", "prt_kernels.hip", "prt_kernels_f32.hip", "bvh_build.cpp", "bvh_build_gpu.hip", "ray_sort.hip", "scene_setup.cpp", "prt_denoise.hip"]
+SOURCES = ["prt_api.cpp", "prt_kernels.hip", "prt_kernels_f32.hip", "bvh_build.cpp", "bvh_build_gpu.hip", "bvh_refit.hip", "ray_sort.hip", "scene_setup.cpp", "prt_denoise.hip"]
 HEADERS = ["prt_types.h", "prt_device.h", "prt_host.h", os.path.join("..", "..", "include", "prt.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-gpu-rdc"]

@@ -67,6 +67,22 @@ void launch_material_scatter(const DScene& S, int material, const double* rd, co
                              const double* uv, size_t n, uint64_t seed, double* wi_out, double* att_out, int32_t* ok_out,
                              hipStream_t st);
 void launch_texture_value(const DScene& S, int texture, const double* uv, size_t n, double* out, hipStream_t st);
+// bvh_refit.hip
+struct RefitCheck {
+    double lo[3], hi[3], scale;
+    uint32_t flags, pad_;
+};
+size_t refit_scratch_bytes();
+void launch_refit_check(const double* d_verts, uint32_t n, const DLightTriT<double>* d_ltris, uint32_t n_lights, void* d_scratch,
+                        RefitCheck* d_out, hipStream_t st);
+void launch_refit_tris(const double* d_verts, const double* d_normals, const uint32_t* d_order, uint32_t n, void* d_tris,
+                       uint32_t tri_stride, DTriShadeT<double>* d_shade, float* d_tbox, const double origin[3], double delta,
+                       hipStream_t st);
+void launch_refit_parents(const DNode* d_nodes, uint32_t n_nodes, uint32_t* d_parent, hipStream_t st);
+hipError_t launch_refit_boxes(DNode* d_nodes, uint32_t n_nodes, const uint32_t* d_parent, uint32_t* d_cnt, const float* d_tbox,
+                              uint32_t n_tris, const float step[3], hipStream_t st);
+void launch_refit_sah(const DNode* d_nodes, uint32_t n_nodes, const float origin[3], const float step[3], void* d_scratch,
+                      double* d_out, hipStream_t st);
 void launch_gather_tris(const DTri* tri_in, const DTriShade* shade_in, const uint32_t* order, uint32_t n, void* tri_out,
                         uint32_t tri_out_stride, DTriShade* shade_out, hipStream_t st);
 } // namespace prt
@@ -239,6 +255,29 @@ struct PrtScene {
     const DNode* d_nodes_shallow = nullptr;             // the same binary tree collapsed for PRT_STACK_SHALLOW entries (host build, deep trees), or null
     uint32_t n_nodes_shallow = 0;
     std::vector<DevBuf<>> allocs;
+    // prt_scene_refit: the leaf order stays resident from the upload on (4 bytes per triangle); the rest is allocated by
+    // the first refit after an upload and lives as long as the upload (all of it in `allocs`)
+    const uint32_t* d_order = nullptr; // BVH leaf position -> triangle index in description order
+    struct Refit {
+        float* d_tbox = nullptr;       // per leaf position the triangle's fp32 box (lo[3], hi[3]) relative to the grid origin
+        uint32_t *d_parent = nullptr, *d_cnt = nullptr;       // per node of d.nodes: its parent, the climb's arrival counter
+        uint32_t *d_parent_sh = nullptr, *d_cnt_sh = nullptr; // ... of d_nodes_shallow
+        void* d_scratch = nullptr;     // partials of the reductions
+        prt::RefitCheck* d_check = nullptr;
+        double* d_sah = nullptr;       // [0] SAH cost of the tree as built, [1] after the last refit
+        Event ev0, ev1, ev2;           // timed: start of the records, start of the boxes, end
+        Event done;                    // behind the refit's last kernel: every later call waits for it
+        bool pending = false;          // `done` has been recorded
+        uint64_t count = 0;            // successful refits since the upload
+    } refit;
+    Scratch refit_in;        // prt_scene_refit: device copies of the caller's host arrays (kept between calls)
+    bool host_stale = false; // prt_scene_refit_device moved the geometry past the host triangles
+    Event feat_done;         // behind the last prt_render_features* kernel (it uses no call slot): a refit waits for it
+    bool feat_pending = false;
+    // Every call that reads the geometry first waits, on its stream, for the last refit's end.
+    hipError_t after_refit(hipStream_t st) const {
+        return refit.pending ? hipStreamWaitEvent(st, refit.done.get(), 0) : hipSuccess;
+    }
     // Per-call device state, double-buffered: consecutive calls alternate slots, so a caller that
     // alternates two streams (and two framebuffers) can have frame k+1 filling the GPU while the last
     // long paths of frame k drain — the two launches never share counters, partial sums or events.
@@ -287,6 +326,7 @@ struct PrtScene {
         cur ^= 1;
         CallSlot& q = slots[cur];
         *err = q.timed ? hipStreamWaitEvent(st, q.done.get(), 0) : hipSuccess;
+        if (*err == hipSuccess) *err = after_refit(st);
         return &q;
     }
     PrtCounters last{};
@@ -322,6 +362,9 @@ struct PrtScene {
     void release() {
         if (device >= 0) (void)hipSetDevice(device);
         allocs.clear();
+        d_order = nullptr;
+        refit = Refit();
+        refit_in = Scratch();
         multi_fb = Scratch();
         sort = Scratch();
         dn = Scratch();
@@ -701,6 +744,9 @@ static int upload_impl(PrtScene* s, int device);
 // call can launch a kernel on a half-filled DScene.
 int prt_scene_upload(PrtScene* s, int device) {
     if (!s) return fail(PRT_E_INVALID, "prt_scene_upload: null scene");
+    if (s->host_stale)
+        return fail(PRT_E_INVALID, "prt_scene_upload: the host geometry is stale (prt_scene_refit_device moved the resident geometry; "
+                                   "pass every position to prt_scene_update_vertices or prt_scene_refit first)");
     const int rc = upload_impl(s, device);
     if (rc != PRT_OK) {
         const std::string keep = g_err;
@@ -786,7 +832,8 @@ static int upload_impl(PrtScene* s, int device) {
         std::string err;
         if (!prt::build_bvh_device(pb.data(), box_origin, n, db, &err)) return fail(PRT_E_HIP, "prt_scene_upload: " + err);
         s->allocs.emplace_back(db.d_nodes);
-        const DevBuf<> order(db.d_order); // the leaf order is needed only for the gather below
+        s->allocs.emplace_back(db.d_order); // the leaf order: the gather below, and prt_scene_refit later
+        s->d_order = db.d_order;
         d.nodes = db.d_nodes;
         if (dev_env("PRT_VALIDATE_BVH")) { // tests: check the device-built tree on the host before any ray visits it
             std::vector<DNode> hn(db.n_nodes);
@@ -831,6 +878,7 @@ static int upload_impl(PrtScene* s, int device) {
         if ((rc = s->up(s->bvh.nodes, &d.nodes))) return rc;
         if ((rc = up_tris(&d.tris))) return rc;
         if ((rc = s->up(ds, &d.shade))) return rc;
+        if ((rc = s->up(s->bvh.order, &s->d_order, false))) return rc; // (for prt_scene_refit; not one of the counted table uploads)
     }
     if ((rc = s->up(s->mats, &d.materials))) return rc;
     {
@@ -952,6 +1000,7 @@ int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double*
     ++s->generation; // the geometry changes from here on, even if the update fails half way
     try {
         prt::update_triangles(vertices, normals, s->tris);
+        s->host_stale = false; // every host position has been replaced
         PrtSceneDesc d;
         std::memset(&d, 0, sizeof(d));
         d.n_tris = s->tris.size();
@@ -1013,6 +1062,8 @@ static int ensure_f32_impl(PrtScene* s) {
     if ((rc = s->alloc(n * (size_t)stride, &t)) || (rc = s->alloc(n * sizeof(DTriShadeT<float>), &sh)) ||
         (rc = s->alloc(s->n_texel_reals * sizeof(float), &tx)))
         return rc;
+    // the conversions read the records a refit on another (non-blocking) stream may still be writing
+    PRT_HIP(s->after_refit(nullptr));
     prt32::launch_convert_tris(d.tris, d.tri_stride, (uint32_t)n, t, stride, nullptr);
     prt32::launch_convert_shade(d.shade, (uint32_t)n, static_cast<DTriShadeT<float>*>(sh), nullptr);
     prt32::launch_convert_reals(d.texels_lin, s->n_texel_reals, static_cast<float*>(tx), nullptr);
@@ -1096,6 +1147,248 @@ static int require_uploaded(PrtScene* s, const char* who) {
     if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
     if (s->device < 0) return fail(PRT_E_NO_DEVICE, std::string(who) + ": scene is not uploaded to a HIP device (no CPU path exists)");
     PRT_HIP(hipSetDevice(s->device));
+    return PRT_OK;
+}
+
+// ---- prt_scene_refit: new positions for a resident scene, the records and the tree's boxes follow on the GPU (bvh_refit.hip)
+namespace {
+float f32_round_down(double v) {
+    float f = (float)v;
+    if ((double)f > v) f = std::nextafter(f, -std::numeric_limits<float>::infinity());
+    return f;
+}
+float f32_round_up(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+    return f;
+}
+size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+} // namespace
+
+// What the first refit after an upload adds to the resident scene: its working arrays and events, the 32-entry collapse
+// of a deep host-built tree (so that every resident node array is refitted from the first time on), the parents of
+// every node, and the SAH cost of the tree as built.
+static int refit_prepare(PrtScene* s, hipStream_t st) {
+    PrtScene::Refit& R = s->refit;
+    const DScene& d = s->k64.d;
+    int rc;
+    if (!R.d_check) {
+        void *tbox, *parent, *cnt, *scratch, *check, *sah;
+        if ((rc = s->alloc((size_t)d.n_tris * 6 * sizeof(float), &tbox)) || (rc = s->alloc((size_t)d.n_nodes * sizeof(uint32_t), &parent)) ||
+            (rc = s->alloc(round16((size_t)d.n_nodes * sizeof(uint32_t)), &cnt)) || (rc = s->alloc(prt::refit_scratch_bytes(), &scratch)) ||
+            (rc = s->alloc(2 * sizeof(double), &sah)) || (rc = s->alloc(sizeof(prt::RefitCheck), &check)))
+            return rc;
+        PRT_HIP(make_event(R.ev0, hipEventDefault));
+        PRT_HIP(make_event(R.ev1, hipEventDefault));
+        PRT_HIP(make_event(R.ev2, hipEventDefault));
+        PRT_HIP(make_event(R.done, hipEventDisableTiming));
+        if (s->stack_need > PRT_STACK_SHALLOW && !s->d_nodes_shallow && !s->bvh_info.built_on_device && !s->bvh.nodes_shallow.empty()) {
+            if ((rc = s->up(s->bvh.nodes_shallow, &s->d_nodes_shallow, false))) return rc; // (ensure_f32 then finds it resident)
+            s->n_nodes_shallow = (uint32_t)s->bvh.nodes_shallow.size();
+        }
+        R.d_tbox = static_cast<float*>(tbox);
+        R.d_parent = static_cast<uint32_t*>(parent);
+        R.d_cnt = static_cast<uint32_t*>(cnt);
+        R.d_scratch = scratch;
+        R.d_sah = static_cast<double*>(sah);
+        prt::launch_refit_parents(d.nodes, d.n_nodes, R.d_parent, st);
+        prt::launch_refit_sah(d.nodes, d.n_nodes, d.grid_origin, d.grid_step, R.d_scratch, R.d_sah, st);
+        PRT_HIP(hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st));
+        PRT_HIP(hipGetLastError());
+        R.d_check = static_cast<prt::RefitCheck*>(check);
+    }
+    if (s->d_nodes_shallow && !R.d_parent_sh) {
+        void *parent, *cnt;
+        if ((rc = s->alloc((size_t)s->n_nodes_shallow * sizeof(uint32_t), &parent)) ||
+            (rc = s->alloc(round16((size_t)s->n_nodes_shallow * sizeof(uint32_t)), &cnt)))
+            return rc;
+        prt::launch_refit_parents(s->d_nodes_shallow, s->n_nodes_shallow, static_cast<uint32_t*>(parent), st);
+        PRT_HIP(hipGetLastError());
+        R.d_cnt_sh = static_cast<uint32_t*>(cnt);
+        R.d_parent_sh = static_cast<uint32_t*>(parent);
+    }
+    return PRT_OK;
+}
+
+// d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
+static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
+    DScene& d = s->k64.d;
+    const uint32_t n = d.n_tris;
+    if (n == 0) return PRT_OK; // nothing to move (the empty scene's root is never traversed)
+    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
+    PrtScene::Refit& R = s->refit;
+    PRT_HIP_AS(who, s->after_refit(st)); // one refit at a time: they share the working arrays
+    {
+        const size_t mark = s->allocs.size();
+        const bool fresh = !R.d_check;
+        const DNode* const shallow_before = s->d_nodes_shallow; // (ensure_f32 may have made it resident: k32 traverses it)
+        const uint32_t n_shallow_before = s->n_nodes_shallow;
+        const int rc = refit_prepare(s, st);
+        if (rc != PRT_OK) { // (nothing resident has been written)
+            const std::string keep = g_err;
+            if (fresh) {
+                (void)hipDeviceSynchronize();
+                s->allocs.resize(mark);
+                R = PrtScene::Refit();
+                s->d_nodes_shallow = shallow_before; // only what this call uploaded went with `mark`
+                s->n_nodes_shallow = n_shallow_before;
+            }
+            g_err = keep;
+            return rc;
+        }
+    }
+    // phase 1, read-only: vertex range, scene bounds, emitters in place; then the one read-back of the call
+    prt::launch_refit_check(d_verts, n, d.light_tris, (uint32_t)d.n_lights, R.d_scratch, R.d_check, st);
+    PRT_HIP_AS(who, hipGetLastError());
+    prt::RefitCheck c;
+    PRT_HIP_AS(who, hipMemcpyAsync(&c, R.d_check, sizeof(c), hipMemcpyDeviceToHost, st));
+    PRT_HIP_AS(who, hipEventRecord(R.done.get(), st)); // (the working arrays are in use until here, whatever the verdict)
+    R.pending = true;
+    PRT_HIP_AS(who, hipStreamSynchronize(st));
+    if (c.flags & 1u) return fail(PRT_E_INVALID, who + ": vertex coordinate is not finite (or beyond 1e18)");
+    if (c.flags & 2u)
+        return fail(PRT_E_INVALID, who + ": a vertex of a light mesh moved; emitters stay in place under a refit (the light tree is not "
+                                         "rebuilt) - use prt_scene_update_vertices");
+    // the quantisation grid of the new bounds: prim_boxes' origin and margin, quant_grid's steps.  The root box of the
+    // builders is the union of the triangles' fp32 boxes; rounding and the subtraction are monotone, so its upper corner
+    // is the box rule applied to the upper corner of the bounds.
+    const double extent = std::max(1.0, std::max(c.hi[0] - c.lo[0], std::max(c.hi[1] - c.lo[1], c.hi[2] - c.lo[2])));
+    const double delta = 1e-9 * extent + 256.0 * std::numeric_limits<double>::epsilon() * c.scale;
+    float origin[3], step[3], root_hi[3], rel0[3];
+    double origin_d[3];
+    for (int a = 0; a < 3; ++a) {
+        origin[a] = f32_round_down(c.lo[a] - 2.0 * delta);
+        origin_d[a] = (double)origin[a];
+        root_hi[a] = f32_round_up((c.hi[a] + delta) - origin_d[a]);
+    }
+    {
+        const float zero[3] = {0.f, 0.f, 0.f};
+        prt::quant_grid(zero, root_hi, false, rel0, step);
+    }
+    // phase 2 writes what calls in flight read: wait for both call slots and the last features call first
+    for (PrtScene::CallSlot& q : s->slots)
+        if (q.timed) PRT_HIP_AS(who, hipStreamWaitEvent(st, q.done.get(), 0));
+    if (s->feat_pending) PRT_HIP_AS(who, hipStreamWaitEvent(st, s->feat_done.get(), 0));
+    // The geometry changes from here on, even if a launch below fails half way (as in prt_scene_update_vertices): the
+    // generation and the grid, in every copy (the host tree's, both DScenes), go first, so that a scene whose records were
+    // partly rewritten never passes for the old one.
+    {
+        double e = 0.0;
+        for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)step[a]);
+        const float slab = std::nextafter((float)e, std::numeric_limits<float>::infinity());
+        float cs = std::max(root_hi[0], std::max(root_hi[1], root_hi[2]));
+        if (s->bvh_info.built_on_device) // (the device builder also covers the grid's far corner)
+            for (int a = 0; a < 3; ++a) cs = std::max(cs, (float)(65535.0 * (double)step[a]));
+        s->bvh.coord_scale = std::nextafter(cs, std::numeric_limits<float>::infinity());
+        for (int a = 0; a < 3; ++a) {
+            s->bvh.grid_origin[a] = d.grid_origin[a] = s->k32.d.grid_origin[a] = origin[a];
+            s->bvh.grid_step[a] = d.grid_step[a] = s->k32.d.grid_step[a] = step[a];
+        }
+        d.slab_scale = s->k32.d.slab_scale = slab;
+        ++s->generation;
+    }
+    PRT_HIP_AS(who, hipEventRecord(R.ev0.get(), st));
+    prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
+                           R.d_tbox, origin_d, delta, st);
+    if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
+        const DSceneT<float>& f = s->k32.d;
+        prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
+        prt32::launch_convert_shade(d.shade, n, const_cast<DTriShadeT<float>*>(f.shade), st);
+    }
+    PRT_HIP_AS(who, hipGetLastError());
+    PRT_HIP_AS(who, hipEventRecord(R.ev1.get(), st));
+    PRT_HIP_AS(who, prt::launch_refit_boxes(const_cast<DNode*>(d.nodes), d.n_nodes, R.d_parent, R.d_cnt, R.d_tbox, n, step, st));
+    if (s->d_nodes_shallow)
+        PRT_HIP_AS(who, prt::launch_refit_boxes(const_cast<DNode*>(s->d_nodes_shallow), s->n_nodes_shallow, R.d_parent_sh, R.d_cnt_sh,
+                                                R.d_tbox, n, step, st));
+    prt::launch_refit_sah(d.nodes, d.n_nodes, origin, step, R.d_scratch, R.d_sah + 1, st);
+    PRT_HIP_AS(who, hipGetLastError());
+    PRT_HIP_AS(who, hipEventRecord(R.ev2.get(), st));
+    PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
+    ++R.count;
+    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) { // the refitted tree, as the kernels now get it (synchronous)
+        std::vector<DNode> hn(d.n_nodes);
+        std::vector<uint32_t> ho(n);
+        PRT_HIP_AS(who, hipStreamSynchronize(st));
+        PRT_HIP_AS(who, hipMemcpy(hn.data(), d.nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+        PRT_HIP_AS(who, hipMemcpy(ho.data(), s->d_order, ho.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (const int rc = dump_bvh(path, s, hn.data(), hn.size(), ho.data(), s->stack_need)) return rc;
+    }
+    return PRT_OK;
+}
+
+int prt_scene_refit_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
+    int rc = require_uploaded(s, "prt_scene_refit_device");
+    if (rc) return rc;
+    rc = refit_impl(s, "prt_scene_refit_device", static_cast<const double*>(d_vertices), static_cast<const double*>(d_normals),
+                    reinterpret_cast<hipStream_t>(stream));
+    if (rc == PRT_OK && !s->tris.empty()) s->host_stale = true; // the host triangles still hold the old positions
+    return rc;
+}
+
+int prt_scene_refit(PrtScene* s, const double* vertices, const double* normals) {
+    int rc = require_uploaded(s, "prt_scene_refit");
+    if (rc) return rc;
+    const size_t n = s->tris.size(), bytes = n * 9 * sizeof(double);
+    if (n == 0) return PRT_OK;
+    if (!vertices) return fail(PRT_E_INVALID, "prt_scene_refit: null vertices");
+    // device copies of the caller's arrays, in a buffer the scene keeps (a previous refit may still be reading it)
+    PRT_HIP_AS("prt_scene_refit", s->refit_in.reserve(bytes * (normals ? 2 : 1), nullptr));
+    double* dv = s->refit_in.get<double>();
+    double* dn = normals ? dv + n * 9 : nullptr;
+    PRT_HIP(hipMemcpyAsync(dv, vertices, bytes, hipMemcpyHostToDevice, nullptr));
+    if (normals) PRT_HIP(hipMemcpyAsync(dn, normals, bytes, hipMemcpyHostToDevice, nullptr));
+    rc = refit_impl(s, "prt_scene_refit", dv, dn, nullptr);
+    PRT_HIP_AS("prt_scene_refit", s->refit_in.used(nullptr));
+    if (rc != PRT_OK) {
+        const std::string keep = g_err;
+        (void)hipStreamSynchronize(nullptr); // the caller's arrays are free again on every way out
+        g_err = keep;
+        return rc;
+    }
+    // the host triangles follow, so that a later upload or update sees this geometry; the host tree's boxes do not (they
+    // were refitted on the device only): that upload builds a fresh tree, on the GPU where there are two triangles to split
+    try {
+        prt::update_triangles(vertices, normals, s->tris);
+        s->host_stale = false;
+        if (!s->device_bvh) {
+            if (n >= 2) s->device_bvh = true;
+            else {
+                std::string err;
+                if (!prt::build_bvh(s->tris, s->bvh, &err)) return fail(PRT_E_LIMIT, "prt_scene_refit: " + err);
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        s->host_stale = true; // the device holds the new geometry, the host triangles may not
+        return fail(PRT_E_OOM, "prt_scene_refit: out of host memory (the resident scene was refitted)");
+    }
+    return PRT_OK;
+}
+
+int prt_scene_refit_info(const PrtScene* s, PrtRefitInfo* out) {
+    if (!s || !out) return fail(PRT_E_INVALID, "prt_scene_refit_info: null argument");
+    std::memset(out, 0, sizeof(*out));
+    const PrtScene::Refit& R = s->refit;
+    out->refits = R.count;
+    out->sah_ratio = 1.0;
+    out->host_stale = s->host_stale ? 1u : 0u;
+    for (int a = 0; a < 3; ++a) {
+        out->grid_origin[a] = s->bvh.grid_origin[a];
+        out->grid_step[a] = s->bvh.grid_step[a];
+    }
+    out->slab_scale = s->device >= 0 ? s->k64.d.slab_scale : 0.f;
+    if (s->device >= 0 && R.count) {
+        PRT_HIP(hipSetDevice(s->device));
+        PRT_HIP(hipEventSynchronize(R.ev2.get()));
+        float ms = 0.f;
+        PRT_HIP(hipEventElapsedTime(&ms, R.ev0.get(), R.ev1.get()));
+        out->records_ms = ms;
+        PRT_HIP(hipEventElapsedTime(&ms, R.ev1.get(), R.ev2.get()));
+        out->boxes_ms = ms;
+        double sah[2] = {0, 0};
+        PRT_HIP(hipMemcpy(sah, R.d_sah, sizeof(sah), hipMemcpyDeviceToHost));
+        out->sah_ratio = sah[0] > 0.0 ? sah[1] / sah[0] : 1.0;
+    }
     return PRT_OK;
 }
 
@@ -1200,6 +1493,7 @@ int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t see
     const double* dorg = static_cast<const double*>(b.in(origins, n * 3 * sizeof(double)));
     PrtLightSample* dout = static_cast<PrtLightSample*>(b.out(n * sizeof(PrtLightSample)));
     if ((rc = b.status("prt_sample_lights"))) return rc;
+    PRT_HIP(s->after_refit(nullptr));
     prt::launch_sample_lights(s->k64.d, dorg, n, seed, dout, nullptr);
     b.sync();
     b.down(out, dout, n * sizeof(PrtLightSample));
@@ -2126,8 +2420,12 @@ int features_impl(PrtScene* s, const std::string& w, const PrtCamera* cam, const
     if (!albedo && !normal && !depth && !prim) return fail(PRT_E_INVALID, w + ": no output buffer");
     DCamera C;
     prt::setup_camera(*cam, C);
+    PRT_HIP(s->after_refit(st));
     prt::launch_features(s->k64.d, C, prt::seed_key(p->seed), p->pixel_jitter ? 1 : 0, feature_spp, albedo, normal, depth, prim, st);
     PRT_HIP(hipGetLastError());
+    if (!s->feat_done) PRT_HIP(make_event(s->feat_done, hipEventDisableTiming));
+    PRT_HIP(hipEventRecord(s->feat_done.get(), st)); // a refit's writing phase waits for this reader too
+    s->feat_pending = true;
     return PRT_OK;
 }
 
