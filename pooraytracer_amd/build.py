@@ -27,8 +27,11 @@ DEV_FLAGS = ["-DPRT_DEV_HOOKS=1"]
 JOBS = max(1, min(6, (os.cpu_count() or 2)))
 
 
+INCLUDES = {"prt_kernels_f32.hip": ["prt_kernels.hip"]}  # sources that #include another source
+
+
 def _deps(src):
-    return [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
+    return [os.path.join(CSRC, f) for f in [src] + INCLUDES.get(src, []) + HEADERS] + [os.path.abspath(__file__)]
 
 
 def _obj_path(src, flags):

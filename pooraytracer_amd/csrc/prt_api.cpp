@@ -523,6 +523,11 @@ struct TileLayout {
 
 // What every K3 launch of the scene shares (render_impl, prt_render_samples); the callers set the samples, tiles, items
 // and chunks of their launch.
+// K3's one-pass vertex (prt_kernels.hip): lanes back from a shadow ray start their continuation ray between traversal
+// rounds once this many of a wave's lanes wait for it; 65 = never, the next pass starts them.
+#ifndef PRT_CHAIN_MIN_DEFAULT
+#define PRT_CHAIN_MIN_DEFAULT 8
+#endif
 static DRenderParams base_params(const PrtScene* s, const PrtRenderParams* p) {
     DRenderParams P;
     std::memset(&P, 0, sizeof(P));
@@ -536,6 +541,7 @@ static DRenderParams base_params(const PrtScene* s, const PrtRenderParams* p) {
     P.keep = s->feat == 0 ? 28 : 20;
     P.leaf_batch = s->feat == 0 ? 48 : (s->feat & 2) ? 32 : 40; // (2 = Phong, as in s->feat above)
     P.inner_min = s->feat == 0 ? 20 : 12;
+    P.chain_min = PRT_CHAIN_MIN_DEFAULT;
     for (int c = 0; c < 3; ++c) P.background[c] = p->background[c];
     P.seed_key = prt::seed_key(p->seed); // the seed is hashed on its own, once per launch (prt_device.h, Rng)
     P.jitter = p->pixel_jitter ? 1 : 0;
@@ -557,7 +563,7 @@ static DRenderParamsT<float> to_f32(const DRenderParams& P, const KernelConfig<f
     o.seed_key = P.seed_key;
     o.tile = P.tile; o.tiles_x = P.tiles_x; o.tiles_y = P.tiles_y; o.n_tiles = P.n_tiles;
     o.rank = P.rank; o.nranks = P.nranks; o.owned_tiles = P.owned_tiles; o.jitter = P.jitter;
-    o.keep = P.keep; o.leaf_batch = P.leaf_batch; o.inner_min = P.inner_min; o.scramble = P.scramble; o.cached_min = P.cached_min;
+    o.keep = P.keep; o.leaf_batch = P.leaf_batch; o.inner_min = P.inner_min; o.scramble = P.scramble; o.cached_min = P.cached_min; o.chain_min = P.chain_min;
     o.light_lds = k.light_lds; o.mat_lds = k.mat_lds; o.ltri_lds = k.ltri_lds;
     o.stack_depth = k.stack_depth;
     o.items_per_chunk = P.items_per_chunk; o.n_items = P.n_items;
@@ -1603,6 +1609,7 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     P.cached_min = 24; // measured: veach-mis -1 %, the others flat
     // (developer overrides of the wave scheduling thresholds through the environment, for sweeps)
     if (const char* e = dev_env("PRT_TUNE_CACHED_MIN")) P.cached_min = std::max(1, std::atoi(e)); // (0 would keep a wave passing for ever)
+    if (const char* e = dev_env("PRT_TUNE_CHAIN_MIN")) P.chain_min = std::min(65, std::max(1, std::atoi(e))); // (65: never between rounds; 0 would let a wave take chain steps that chain nothing, for ever)
     if (const char* e = dev_env("PRT_TUNE_KEEP")) P.keep = std::min(64, std::max(0, std::atoi(e))); // (< 0 would keep a wave traversing once every lane is idle)
     if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::min(64, std::max(1, std::atoi(e))); // (a batch is 1 to 64 lanes of a wave)
     if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::min(64, std::max(0, std::atoi(e))); // (< 0 would never test the leaves of a wave whose lanes are all parked)

@@ -206,6 +206,9 @@ __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void
 }
 
 // ------------------------------------------------------------------------------------------- K3
+#ifndef PRT_ONE_PASS_VERTEX
+#define PRT_ONE_PASS_VERTEX 1 // the lean and the CookTorrance permutation shade a path vertex in one pass (k_render, ONE_PASS)
+#endif
 enum : int { ST_FETCH = 0, ST_NEW_SAMPLE = 1, ST_CLOSEST = 2, ST_SHADOW = 3, ST_DONE = 4, ST_PRIMARY = 5, ST_CACHED = 6 };
 // The camera ray of a pixel is the same for every sample (Camera.cpp:53-57: GetRay once per pixel, no jitter): K3 traces
 // it ONCE per work item (ST_PRIMARY) and parks the ray's direction and its hit — t, triangle, barycentrics — in LDS,
@@ -365,6 +368,12 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
             }                                                                   \
         }                                                                       \
     } while (0)
+#define TRACE_FLAG_AT(v_, bit_)                                                 \
+    do {                                                                        \
+        if (TRACING) {                                                          \
+            if ((v_) < PRT_TRACE_VERTS) ctr->trace[(size_t)item * PRT_TRACE_WORDS + 2 + 2 * (v_)] |= (bit_); \
+        }                                                                       \
+    } while (0)
 #define TRACE_FLAG(bit_)                                                        \
     do {                                                                        \
         if (TRACING) {                                                          \
@@ -392,6 +401,20 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     int32_t sh_tri = -1;
     real ldist = 0;              // distance to the sampled light point (valid in ST_SHADOW)
     int32_t ltri = 0;
+    // ONE_PASS (the lean and the CookTorrance permutation; not Phong, whose Eval draws a random number only when the light is
+    // visible, and not the textured ones, which measure slower with it: DESIGN.md section 4): the pass that consumes a closest
+    // hit shades the WHOLE vertex — light pick, the light's contribution as if it were visible,
+    // roulette and Scatter — and the lane carries across its shadow traversal just that contribution, the scattered
+    // direction and whether the path goes on.  A returning shadow ray then needs no shading: add the term if nothing was
+    // hit, take the stored direction.  Lanes in that state are chained onto their continuation ray between traversal rounds
+    // (P.chain_min) or by the next pass.  Same draws in the same order, same operations on the same values: the frames are
+    // those of the two-pass flow bit for bit.  rd, sh_tri, ldist and ltri then live inside one pass only.
+    constexpr bool ONE_PASS = PRT_ONE_PASS_VERTEX && !(FEAT & (PRT_FEAT_PHONG | PRT_FEAT_TEX));
+    constexpr bool EVAL_FLAT = ONE_PASS && !(FEAT & PRT_FEAT_CT); // Lambertian / mirror / light only: Eval needs no shading frame
+    d3 pending = mk3(0, 0, 0);   // ONE_PASS, ST_SHADOW: (throughput * direct light) / spp, added if the shadow ray escapes
+    d3 next_d = mk3(0, 0, 1);    // ONE_PASS, ST_SHADOW: the scattered direction (valid if cont)
+    bool cont = false;           // ONE_PASS, ST_SHADOW: the path goes on after this vertex
+    int nee_v = 0;               // (tracing: the vertex the shadow ray belongs to, saved before depth--)
     Rng rng;
     rng.s = 0;
     const real inv_spp = RL(1.0) / (real)P.spp; // pixelSamplesScale, Camera.cpp:83
@@ -410,6 +433,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
         if (!tr.active) {
             // ---------------- a traversal has just finished on this lane: consume its result
             bool end_sample = false, do_scatter = false;
+            bool nee = false; // ONE_PASS: this pass found a light point worth a shadow ray (tr.d is the direction towards it)
             // The ray this lane traces next is written straight into tr.o / tr.d as soon as it is known (shadow ray:
             // origin = shading point, direction towards the light; continuation: same origin, scattered direction; new
             // sample: the camera ray) — no staging copies, no selects at the traversal set-up.  After a closest hit has
@@ -494,11 +518,52 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                                 ldist = dist;
                                 tr.d = ldir;
                                 TRACE_FLAG(PRT_TRACE_NEE);
-                                state = ST_SHADOW; // trace the shadow ray, then scatter
-                                do_scatter = false;
+                                if (ONE_PASS) {
+                                    nee = true; // the vertex is finished below; the shadow ray starts at the end of this pass
+                                    if (COUNT) nee_v = P.max_depth - depth;
+                                    if (EVAL_FLAT) {
+                                        // Eval reads the material alone here (albedo / pi, or 0) and cos(theta) is the dot product
+                                        // just tested — the shading frame's normal IS fn — so the light's contribution needs no
+                                        // shading context: the expressions of the two-pass flow's ST_SHADOW block, same order
+                                        d3 ln0;
+                                        real pdf;
+                                        int32_t lmat;
+                                        if (LLDS && P.ltri_lds > 0) {
+                                            const DLightTri* lt = lds_ltris + lp.tri;
+                                            ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
+                                        } else {
+                                            const DLightTri* lt = S.light_tris + lp.tri;
+                                            ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
+                                        }
+                                        const d3 ln = dot(ldir, ln0) < RL(0.) ? ln0 : -ln0;
+                                        const d3 emission = ld3(MATERIAL(lmat).emission);
+                                        d2 no_uv;
+                                        no_uv.x = no_uv.y = RL(0.0);
+                                        const d3 fr = mat_eval<FEAT>(S, m, ldir, ldir, no_uv, rng); // (directions and uv unread, no draw)
+                                        const real cosT = dot(ldir, fn); // world_to_local(ldir, frame).z
+                                        const real cosTB = -dot(ln, ldir);
+                                        const d3 direct = (emission * fr) * fast_div(cosT * cosTB, (dist * dist) * pdf);
+                                        pending = (PST_LD(S_BETA) * direct) * inv_spp; // what ADD_RADIANCE(direct) adds: the throughput BEFORE Scatter
+                                    }
+                                } else {
+                                    state = ST_SHADOW; // trace the shadow ray, then scatter
+                                    do_scatter = false;
+                                }
                             }
                         }
                     }
+                }
+            } else if (ONE_PASS && state == ST_SHADOW) {
+                // ---- shadow ray returned, vertex already shaded (the lanes the wave loop below did not chain)
+                if (tr.hit.tri < 0) {
+                    PST_ST(S_ACC, PST_LD(S_ACC) + pending);
+                    TRACE_FLAG_AT(nee_v, PRT_TRACE_VISIBLE);
+                }
+                if (cont) {
+                    tr.d = next_d;
+                    state = ST_CLOSEST;
+                } else {
+                    end_sample = true;
                 }
             } else if (state == ST_SHADOW) {
                 // ---- shadow ray returned: visibility = closest hit no nearer than dist - 1e-3 (Camera.cpp:152-155)
@@ -546,7 +611,63 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
             }
 
             PROF_MARK(1); // consume: closest hit (emission, light pick) or shadow ray (light evaluation)
-            if (do_scatter) {
+            if (ONE_PASS && do_scatter) {
+                // ---- the light's contribution (Camera.cpp:157-172, the expressions of the ST_SHADOW block above), Russian
+                // roulette and Scatter (Camera.cpp:176-202, those of the block below) on ONE shading context.  Eval draws
+                // nothing in these permutations, so the roulette number — the next one of the stream either way — is drawn
+                // first: a lane that has no light point and does not survive the roulette needs no context at all.
+                end_sample = true;
+                const bool rr_ok = rng.next() < P.rr;
+                if ((nee && !EVAL_FLAT) || rr_ok) {
+                    const ShadeCtx c = make_ctx<FEAT, PAD>(S, rd, tr.hit.alpha, tr.hit.beta, sh_tri);
+                    const DMaterial& m = MATERIAL(c.material);
+                    if (nee && !EVAL_FLAT) {
+                        d3 ln0;
+                        real pdf;
+                        int32_t lmat;
+                        if (LLDS && P.ltri_lds > 0) {
+                            const DLightTri* lt = lds_ltris + ltri;
+                            ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
+                        } else {
+                            const DLightTri* lt = S.light_tris + ltri;
+                            ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
+                        }
+                        const d3 ln = dot(tr.d, ln0) < RL(0.) ? ln0 : -ln0;
+                        const d3 emission = ld3(MATERIAL(lmat).emission);
+                        const d3 wo = world_to_local(-rd, c.f);
+                        const d3 lwi = world_to_local(tr.d, c.f);
+                        const d3 fr = mat_eval<FEAT>(S, m, lwi, wo, c.uv, rng);
+                        const real cosT = lwi.z;
+                        const real cosTB = -dot(ln, tr.d);
+                        const d3 direct = (emission * fr) * fast_div(cosT * cosTB, (ldist * ldist) * pdf);
+                        pending = (PST_LD(S_BETA) * direct) * inv_spp; // what ADD_RADIANCE(direct) adds: the throughput BEFORE Scatter
+                    }
+                    if (rr_ok) {
+                        d3 att;
+                        TRACE_FLAG(PRT_TRACE_ROULETTE);
+                        if (mat_scatter<FEAT>(S, m, rd, c.f, c.uv, rng, att, next_d)) {
+                            TRACE_FLAG(PRT_TRACE_SCATTER);
+                            depth--;
+                            if (depth >= 0) {
+                                const d3 beta = (PST_LD(S_BETA) * att) * P.inv_rr;
+                                PST_ST(S_BETA, beta);
+                                if (!(beta.x == RL(0.) && beta.y == RL(0.) && beta.z == RL(0.))) {
+                                    prev_skip = m.skip_light_sampling != 0;
+                                    first = false;
+                                    end_sample = false;
+                                }
+                            }
+                        }
+                    }
+                }
+                if (nee) { // the shadow ray first (tr.d points at the light already); what follows it is known
+                    cont = !end_sample;
+                    end_sample = false;
+                    state = ST_SHADOW;
+                } else if (!end_sample) {
+                    tr.d = next_d;
+                }
+            } else if (do_scatter) {
                 // ---- Russian roulette + Scatter, Camera.cpp:176-202
                 end_sample = true;
                 if (rng.next() < P.rr) {
@@ -733,6 +854,40 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
         do {
             // the interval's lower end and the any-hit rule follow from the kind of ray: not kept as traversal state
             tr.template round<COUNT>(S, stk, wc, P.leaf_batch, P.inner_min, state == ST_SHADOW ? RL(0.001) : RL(0.0001), state == ST_SHADOW);
+            if (ONE_PASS) {
+                // Lanes whose shadow ray has returned and whose path goes on need no pass.  With enough of them to be worth the
+                // traversal set-up (executed whole for one lane) they take their light term and start the continuation ray right
+                // here; the others are chained by the next pass.  A finished shadow ray only ever becomes an active closest ray,
+                // so the loop ends as before.  (Measured: the same step as a pass of its own that only these lanes enter — one
+                // set-up site, no second copy of Trav::start in the loop — costs what the chaining gains)
+                const bool fin = !tr.active && state == ST_SHADOW && cont;
+                const int n_fin = wave_count(fin);
+                if (n_fin >= P.chain_min) {
+                    PROF_MARK(0);
+                    if (fin) {
+                        if (tr.hit.tri < 0) {
+                            PST_ST(S_ACC, PST_LD(S_ACC) + pending);
+                            TRACE_FLAG_AT(nee_v, PRT_TRACE_VISIBLE);
+                        }
+                        tr.d = next_d;
+                        state = ST_CLOSEST;
+                        if (COUNT && ctr->ray_dump != nullptr) { // (developer experiment, as at the end of a pass)
+                            const unsigned long long k = atomicAdd(&ctr->ray_dump_n, 1ULL);
+                            if (k < ctr->ray_dump_cap) {
+                                PrtRay r;
+                                r.o[0] = (double)tr.o.x; r.o[1] = (double)tr.o.y; r.o[2] = (double)tr.o.z;
+                                r.d[0] = (double)tr.d.x; r.d[1] = (double)tr.d.y; r.d[2] = (double)tr.d.z;
+                                r.tmin = 0.0001;
+                                r.tmax = __builtin_huge_val();
+                                static_cast<PrtRay*>(ctr->ray_dump)[k] = r;
+                            }
+                        }
+                        tr.start(S, RL(0.0001), PRT_INF);
+                    }
+                    if (lane == 0) atomicAdd(&s_rays[wave], (unsigned long long)n_fin); // closest rays: the low half
+                    PROF_MARK(5); // chain step
+                }
+            }
         } while (wave_count(tr.active) > P.keep);
     }
 
@@ -744,15 +899,16 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
         atomicAdd(&ctr->rays_closest, rays & 0xffffffffULL);
         atomicAdd(&ctr->rays_shadow, rays >> 32);
         if (COUNT) {
-            atomicAdd(&ctr->node_fetches, d);
             atomicAdd(&ctr->tri_full, f);
 #if PRT_K3_PROFILE
+            atomicAdd(&ctr->node_fetches, prof_[5]);
             atomicAdd(&ctr->tri_tests, prof_[0]);
             atomicAdd(&ctr->inner_rounds, prof_[1]);
             atomicAdd(&ctr->leaf_rounds, prof_[2]);
             atomicAdd(&ctr->refills, prof_[3]);
             atomicAdd(&ctr->tri_full, prof_[4]);
 #else
+            atomicAdd(&ctr->node_fetches, d);
             atomicAdd(&ctr->tri_tests, e);
             atomicAdd(&ctr->inner_rounds, (unsigned long long)wc.inner_rounds);
             atomicAdd(&ctr->leaf_rounds, (unsigned long long)wc.leaf_rounds);
