@@ -209,6 +209,9 @@ __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void
 #ifndef PRT_ONE_PASS_VERTEX
 #define PRT_ONE_PASS_VERTEX 1 // the lean and the CookTorrance permutation shade a path vertex in one pass (k_render, ONE_PASS)
 #endif
+#ifndef PRT_SAMPLE_TURNOVER
+#define PRT_SAMPLE_TURNOVER 1 // the one-pass permutations start the next sample in the pass that ends the previous one (k_render, TURN)
+#endif
 enum : int { ST_FETCH = 0, ST_NEW_SAMPLE = 1, ST_CLOSEST = 2, ST_SHADOW = 3, ST_DONE = 4, ST_PRIMARY = 5, ST_CACHED = 6 };
 // The camera ray of a pixel is the same for every sample (Camera.cpp:53-57: GetRay once per pixel, no jitter): K3 traces
 // it ONCE per work item (ST_PRIMARY) and parks the ray's direction and its hit — t, triangle, barycentrics — in LDS,
@@ -411,6 +414,16 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     // those of the two-pass flow bit for bit.  rd, sh_tri, ldist and ltri then live inside one pass only.
     constexpr bool ONE_PASS = PRT_ONE_PASS_VERTEX && !(FEAT & (PRT_FEAT_PHONG | PRT_FEAT_TEX));
     constexpr bool EVAL_FLAT = ONE_PASS && !(FEAT & PRT_FEAT_CT); // Lambertian / mirror / light only: Eval needs no shading frame
+    // TURN (the one-pass permutations): a lane walks a pass in path order.  A returned shadow ray without continuation and a
+    // traced ray that left the scene end their sample at the top of the pass, before anything is shaded; the turnover (next
+    // sample index, stream seed, the parked camera hit) follows at once, and the closest-hit block below consumes the fresh
+    // sample's camera vertex in the SAME pass — as it does for an item whose camera ray has just returned.  Only a sample that
+    // ends inside the shading blocks (emitter, roulette without a light point, a camera vertex that ends its sample) waits, as
+    // ST_CACHED, for the next pass's turnover.  Same draws, same expressions, same order of terms into acc.
+    // Not the fp32 lean kernels: with this order the compiler contracts the multiply-adds of their Scatter (local_to_world,
+    // normalize) differently, and their frames would leave the previous ones by a few fp32 ulps; they
+    // keep the order they had.  fp32 CookTorrance and every fp64 kernel give the same bits either way.
+    constexpr bool TURN = ONE_PASS && PRT_SAMPLE_TURNOVER && !(PRT_F32 && !(FEAT & PRT_FEAT_CT));
     d3 pending = mk3(0, 0, 0);   // ONE_PASS, ST_SHADOW: (throughput * direct light) / spp, added if the shadow ray escapes
     d3 next_d = mk3(0, 0, 1);    // ONE_PASS, ST_SHADOW: the scattered direction (valid if cont)
     bool cont = false;           // ONE_PASS, ST_SHADOW: the path goes on after this vertex
@@ -426,6 +439,64 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
 #if PRT_K3_PROFILE
     unsigned long long prof_[6] = {0, 0, 0, 0, 0, 0}, prof_t_ = __builtin_readcyclecounter();
 #endif
+    // (Two blocks the pass uses at two places, as macros: as lambdas they changed the code of the two-pass permutations.)
+    // A sample has ended: the item's next one is due (`next`: how it is marked), or the item's sum is written and the lane fetches
+#define END_OF_SAMPLE(next) do {                                                                                                                                          \
+        const d3 acc = PST_LD(S_ACC);                                                                                                                                     \
+        s++;                                                                                                                                                              \
+        if (s < s_end) state = (next);                                                                                                                                     \
+        else {                                                                                                                                                            \
+            double* o = cold_args()->partial + (size_t)item * 3;                                                                                                          \
+            o[0] = (double)acc.x; /* the partial sums are fp64 in either mode (K5 adds them in fp64) */                                                                   \
+            o[1] = (double)acc.y;                                                                                                                                         \
+            o[2] = (double)acc.z;                                                                                                                                         \
+            state = ST_FETCH;                                                                                                                                             \
+        }                                                                                                                                                                 \
+    } while (0)
+    // Sample s of the item starts: its stream, its camera ray (P.jitter: to be traced, ST_CLOSEST) or that ray's parked hit
+    // (`parked`: the state of a lane that holds it, with nothing to trace)
+#define NEW_SAMPLE(parked) do {                                                                                                                                           \
+        /* per-sample stream keyed (seed, j*W+i, s) */                                                                                                                    \
+        rng.seed_keyed(P.seed_key, (uint64_t)pixel, (uint64_t)s);                                                                                                         \
+        if (P.jitter) {                                                                                                                                                   \
+            /* the disabled SampleSquare() offset of Camera.cpp:110-111, drawn per sample: y first (g++ argument order); */                                               \
+            /* a camera ray of its own, traced like any other */                                                                                                          \
+            const ColdRenderArgs q = cold_args();                                                                                                                         \
+            const int W = q->C.width;                                                                                                                                     \
+            const int jy = (int)(pixel / (uint32_t)W), jx = (int)(pixel - (uint32_t)jy * (uint32_t)W);                                                                    \
+            const real fy = (real)jy + (rng.next() - RL(0.5));                                                                                                            \
+            const real fx = (real)jx + (rng.next() - RL(0.5));                                                                                                            \
+            const d3 ps = mk3(q->C.pixel00[0], q->C.pixel00[1], q->C.pixel00[2]) + fx * mk3(q->C.du[0], q->C.du[1], q->C.du[2]) +                                         \
+                          fy * mk3(q->C.dv[0], q->C.dv[1], q->C.dv[2]);                                                                                                   \
+            tr.o = mk3(q->C.center[0], q->C.center[1], q->C.center[2]);                                                                                                   \
+            tr.d = ps - tr.o;                                                                                                                                             \
+            state = ST_CLOSEST;                                                                                                                                           \
+        } else {                                                                                                                                                          \
+            /* Camera::GetRay gives every sample of the pixel the same ray (Camera.cpp:53-57, no jitter): the sample starts */                                            \
+            /* from the parked hit of that ray.  Nothing to trace.  Two-pass permutations: the lane waits for the next pass, which */                                     \
+            /* consumes the hit (the LDS reads below have the traversal rounds in between to arrive); TURN: this pass does. */                                            \
+            tr.o = mk3(s_center[0], s_center[1], s_center[2]);                                                                                                            \
+            if (PARK_DIR_GLOBAL(FEAT)) { /* Camera::GetRay again (same expressions as at the fetch: the same bits) */                                                     \
+                const ColdRenderArgs q = cold_args();                                                                                                                     \
+                const d3 ps = mk3(q->C.pixel00[0], q->C.pixel00[1], q->C.pixel00[2]) + (real)px * mk3(q->C.du[0], q->C.du[1], q->C.du[2]) +                               \
+                              (real)py * mk3(q->C.dv[0], q->C.dv[1], q->C.dv[2]);                                                                                         \
+                tr.d = ps - tr.o;                                                                                                                                         \
+            } else {                                                                                                                                                      \
+                tr.d = mk3(unpark_real<NPARK>(park, PARK_DIR), unpark_real<NPARK>(park, PARK_DIR + PRT_RW), unpark_real<NPARK>(park, PARK_DIR + 2 * PRT_RW));             \
+            }                                                                                                                                                             \
+            tr.hit.t = unpark_real<NPARK>(park, PARK_T);                                                                                                                  \
+            tr.hit.tri = (int32_t)park[PARK_TRI * NPARK];                                                                                                                 \
+            if (FEAT & PRT_FEAT_TEX) {                                                                                                                                    \
+                tr.hit.alpha = unpark_real<NPARK>(park, PARK_AB_AT(FEAT));                                                                                                \
+                tr.hit.beta = unpark_real<NPARK>(park, PARK_AB_AT(FEAT) + PRT_RW);                                                                                        \
+            }                                                                                                                                                             \
+            state = (parked);                                                                                                                                             \
+        }                                                                                                                                                                 \
+        PST_ST(S_BETA, mk3(1, 1, 1));                                                                                                                                     \
+        depth = P.max_depth;                                                                                                                                              \
+        first = true;                                                                                                                                                     \
+        prev_skip = false;                                                                                                                                                \
+    } while (0)
     for (;;) {
         if (COUNT) n_refills++;
         PROF_MARK(0); // traversal rounds (and loop control) since the last mark
@@ -482,10 +553,48 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     park_real<NPARK>(park, PARK_AB_AT(FEAT), tr.hit.alpha);
                     park_real<NPARK>(park, PARK_AB_AT(FEAT) + PRT_RW, tr.hit.beta);
                 }
-                state = ST_NEW_SAMPLE; // set up at the bottom of this pass, consumed by the next one
+                state = ST_NEW_SAMPLE; // two-pass: set up at the bottom of this pass, consumed by the next one; TURN: set up right below
             }
-            if (state == ST_CACHED) state = ST_CLOSEST; // a sample set up by the previous pass from the parked hit: nothing to trace
-            if (state == ST_CLOSEST) {
+            bool hit_ready = false; // TURN: the lane holds a closest hit to consume in this pass (else, in ST_CLOSEST, a ray to trace)
+            if (TURN) {
+                // ---- ends that need no shading, then the turnover: a fresh sample's camera hit is consumed below, in this pass
+                bool ended = false;
+                if (state == ST_CACHED) state = ST_NEW_SAMPLE; // its sample ended inside the previous pass's shading blocks
+                else if (state == ST_SHADOW) {
+                    // shadow ray returned, vertex already shaded (the lanes the wave loop below did not chain)
+                    if (tr.hit.tri < 0) {
+                        PST_ST(S_ACC, PST_LD(S_ACC) + pending);
+                        TRACE_FLAG_AT(nee_v, PRT_TRACE_VISIBLE);
+                    }
+                    if (cont) {
+                        tr.d = next_d;
+                        state = ST_CLOSEST;
+                    } else {
+                        ended = true;
+                    }
+                } else if (state == ST_CLOSEST) {
+                    if (tr.hit.tri < 0) {
+                        // a traced ray left the scene: background for the camera ray (Camera.cpp:127); with bSampleLights a bounce miss adds 0 (:187)
+                        if (first || !P.sample_lights) {
+                            const ColdRenderArgs q = cold_args();
+                            ADD_RADIANCE(mk3(q->P.background[0], q->P.background[1], q->P.background[2]));
+                        }
+                        TRACE_VERTEX(-1);
+                        ended = true;
+                    } else {
+                        hit_ready = true;
+                    }
+                }
+                if (ended) END_OF_SAMPLE(ST_NEW_SAMPLE);
+                if (state == ST_NEW_SAMPLE) {
+                    NEW_SAMPLE(ST_CLOSEST);
+                    hit_ready = !P.jitter; // (a jittered sample's camera ray is traced first: the set-up at the bottom starts it)
+                }
+                PROF_MARK(3); // cheap ends + sample turnover: booked with the end of sample / fetch section below
+            } else {
+                if (state == ST_CACHED) state = ST_CLOSEST; // a sample set up by the previous pass from the parked hit: nothing to trace
+            }
+            if (TURN ? hit_ready : state == ST_CLOSEST) {
                 if (tr.hit.tri < 0) {
                     // miss: background for the camera ray (Camera.cpp:127); with bSampleLights a bounce miss adds 0 (:187)
                     if (first || !P.sample_lights) {
@@ -553,7 +662,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                         }
                     }
                 }
-            } else if (ONE_PASS && state == ST_SHADOW) {
+            } else if (ONE_PASS && !TURN && state == ST_SHADOW) {
                 // ---- shadow ray returned, vertex already shaded (the lanes the wave loop below did not chain)
                 if (tr.hit.tri < 0) {
                     PST_ST(S_ACC, PST_LD(S_ACC) + pending);
@@ -565,7 +674,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 } else {
                     end_sample = true;
                 }
-            } else if (state == ST_SHADOW) {
+            } else if (!ONE_PASS && state == ST_SHADOW) {
                 // ---- shadow ray returned: visibility = closest hit no nearer than dist - 1e-3 (Camera.cpp:152-155)
                 const real dist = ldist;
                 // The shadow ray was traced over [0.001, dist - 0.001] only: the reference's test
@@ -693,18 +802,8 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 }
             }
             PROF_MARK(2); // roulette + Scatter
-            if (end_sample) {
-                const d3 acc = PST_LD(S_ACC);
-                s++;
-                if (s < s_end) state = ST_NEW_SAMPLE;
-                else {
-                    double* o = cold_args()->partial + (size_t)item * 3;
-                    o[0] = (double)acc.x; // the partial sums are fp64 in either mode (K5 adds them in fp64)
-                    o[1] = (double)acc.y;
-                    o[2] = (double)acc.z;
-                    state = ST_FETCH;
-                }
-            }
+            // TURN: a sample that ended inside the shading blocks waits for the next pass's turnover (ST_CACHED: nothing in flight)
+            if (end_sample) END_OF_SAMPLE(TURN ? ST_CACHED : ST_NEW_SAMPLE);
 
             // ---------------- give the lane its next piece of work
             if (state == ST_FETCH) {
@@ -755,7 +854,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                             double* o = q->partial + (size_t)item * 3;
                             o[0] = o[1] = o[2] = 0.0;
                         } else if (P.jitter) {
-                            state = ST_NEW_SAMPLE; // a camera ray of its own per sample (below)
+                            state = TURN ? ST_CACHED : ST_NEW_SAMPLE; // a camera ray of its own per sample (below; TURN: the next pass's turnover)
                         } else {
                             // Camera::GetRay (Camera.cpp:108-117), once per work item: the pixel's one camera ray.  Its direction
                             // is parked next to the hit it is about to find.
@@ -773,48 +872,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     }
                 }
             }
-            if (state == ST_NEW_SAMPLE) {
-                // per-sample stream keyed (seed, j*W+i, s)
-                rng.seed_keyed(P.seed_key, (uint64_t)pixel, (uint64_t)s);
-                if (P.jitter) {
-                    // the disabled SampleSquare() offset of Camera.cpp:110-111, drawn per sample: y first (g++ argument order);
-                    // a camera ray of its own, traced like any other
-                    const ColdRenderArgs q = cold_args();
-                    const int W = q->C.width;
-                    const int jy = (int)(pixel / (uint32_t)W), jx = (int)(pixel - (uint32_t)jy * (uint32_t)W);
-                    const real fy = (real)jy + (rng.next() - RL(0.5));
-                    const real fx = (real)jx + (rng.next() - RL(0.5));
-                    const d3 ps = mk3(q->C.pixel00[0], q->C.pixel00[1], q->C.pixel00[2]) + fx * mk3(q->C.du[0], q->C.du[1], q->C.du[2]) +
-                                  fy * mk3(q->C.dv[0], q->C.dv[1], q->C.dv[2]);
-                    tr.o = mk3(q->C.center[0], q->C.center[1], q->C.center[2]);
-                    tr.d = ps - tr.o;
-                    state = ST_CLOSEST;
-                } else {
-                    // Camera::GetRay gives every sample of the pixel the same ray (Camera.cpp:53-57, no jitter): the sample starts
-                    // from the parked hit of that ray.  Nothing to trace: the lane waits for the next pass, which consumes the hit
-                    // (the LDS reads below have the traversal rounds in between to arrive).
-                    tr.o = mk3(s_center[0], s_center[1], s_center[2]);
-                    if (PARK_DIR_GLOBAL(FEAT)) { // Camera::GetRay again (same expressions as at the fetch: the same bits)
-                        const ColdRenderArgs q = cold_args();
-                        const d3 ps = mk3(q->C.pixel00[0], q->C.pixel00[1], q->C.pixel00[2]) + (real)px * mk3(q->C.du[0], q->C.du[1], q->C.du[2]) +
-                                      (real)py * mk3(q->C.dv[0], q->C.dv[1], q->C.dv[2]);
-                        tr.d = ps - tr.o;
-                    } else {
-                        tr.d = mk3(unpark_real<NPARK>(park, PARK_DIR), unpark_real<NPARK>(park, PARK_DIR + PRT_RW), unpark_real<NPARK>(park, PARK_DIR + 2 * PRT_RW));
-                    }
-                    tr.hit.t = unpark_real<NPARK>(park, PARK_T);
-                    tr.hit.tri = (int32_t)park[PARK_TRI * NPARK];
-                    if (FEAT & PRT_FEAT_TEX) {
-                        tr.hit.alpha = unpark_real<NPARK>(park, PARK_AB_AT(FEAT));
-                        tr.hit.beta = unpark_real<NPARK>(park, PARK_AB_AT(FEAT) + PRT_RW);
-                    }
-                    state = ST_CACHED;
-                }
-                PST_ST(S_BETA, mk3(1, 1, 1));
-                depth = P.max_depth;
-                first = true;
-                prev_skip = false;
-            }
+            if (!TURN && state == ST_NEW_SAMPLE) NEW_SAMPLE(ST_CACHED);
             PROF_MARK(3); // end of sample, item fetch, new sample
             // ---------------- start the traversal this lane needs next
             if (state == ST_CLOSEST || state == ST_SHADOW || state == ST_PRIMARY) {
@@ -846,8 +904,9 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
             if (lane == 0) atomicAdd(&s_rays[wave], nc | (ns << 32));
         }
         if (__ballot(state != ST_DONE) == 0ULL) break;
-        // Lanes that started a sample from the parked hit have nothing to trace: with enough of them the next pass comes at
-        // once (it consumes their hits and hands them real rays) instead of after traversal rounds they would sit out.
+        // Lanes that started a sample from the parked hit (TURN: whose sample ended inside the shading blocks, or whose jittered
+        // item has just been fetched) have nothing to trace: with enough of them the next pass comes at once (it starts their
+        // samples and hands them real rays) instead of after traversal rounds they would sit out.
         if (wave_count(state == ST_CACHED) >= P.cached_min) continue;
 
         // ---------------- traversal steps until enough lanes have finished to be worth refilling
