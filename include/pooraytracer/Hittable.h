@@ -3,7 +3,7 @@
 // On the host the scene-graph classes are DESCRIPTORS: they carry the same public data and
 // constructors as the reference's, and Camera::Render flattens them into a PrtSceneDesc for the HIP
 // library (include/prt.h).  Intersection itself never runs on the host: the base Hittable::Hit /
-// Occluded / Sample below forward single queries to the device through the same C ABI (K1 / k_sample_lights).
+// Occluded / Sample below forward queries to the device through the same C ABI (K1 / k_sample_lights).
 #pragma once
 #include <memory>
 #include <vector>
@@ -34,6 +34,10 @@ public:
     virtual ~Hittable();
     // world.Hit(ray, domain, record): one-ray batch through prt_trace_closest (device).
     virtual bool Hit(const Ray& ray, Interval domain, HitRecord& record) const;
+    // The batch form: every ray over the one domain in ONE launch (prt_trace_surface, device).  records is resized to
+    // rays.size(); records[i] is filled from the device's record — position, time, normal, tangent, uv, bFrontFace, and the
+    // hit triangle's material — where the returned [i] is true, and left default-constructed where it is not.  Not virtual.
+    std::vector<bool> Hit(const std::vector<Ray>& rays, Interval domain, std::vector<HitRecord>& records) const;
     // Hit's return value where the record is not wanted (shadow, visibility, line of sight): the any-hit query,
     // prt_trace_occluded (device).  The batch form answers every ray over the one domain in ONE launch: out[i] for rays[i].
     // Not virtual: nothing overrides them, and the vtable layout of existing clients stays as it was.

@@ -348,6 +348,48 @@ int prt_trace_occluded_device(PrtScene* scene, const void* d_rays, size_t n, voi
 int prt_trace_occluded_sorted_device(PrtScene* scene, const void* d_rays, size_t n, void* d_occluded,
                                      int count_work, int precision, void* hip_stream);
 
+/* Surface queries: the whole HitRecord of world.Hit(ray, Interval(tmin, tmax), record) for a batch, plus the response of
+ * the hit's material that prt_render_features defines (albedo, emission).  The surface form of K1: same traversal, same
+ * accept test, and at the point where the closest-hit call writes its PrtHit the lane also reads the triangle's shading
+ * record and material and writes 192 bytes.  192 bytes, the first 32 ARE the ray's PrtHit. */
+typedef struct PrtSurface {
+    double t, alpha, beta;  /* as PrtHit */
+    int32_t prim, front;    /* as PrtHit */
+    double position[3];     /* ray(t) = o + t d  (Ray::operator(), d not normalised) */
+    double normal[3];       /* unit geometric normal on the ray's side (HitRecord::SetFaceNormal): what K3 shades with */
+    double tangent[3];      /* Triangle.cpp:31-46, as stored (not flipped) */
+    double uv[2];           /* (1-alpha-beta) uv0 + alpha uv1 + beta uv2 */
+    double albedo[3];       /* prt_render_features' rule, unaveraged: Lambertian/Debug Kd (texture if any); Phong Kd + Ks (the
+                               texture twice); Mirror, CookTorrance, DiffuseLight, Empty (1,1,1) */
+    double emission[3];     /* Material::GetEmission(): DiffuseLight radiance, Debug albedo, else 0; not face-dependent (as K3) */
+    int32_t material;       /* index into PrtSceneDesc.materials */
+    int32_t material_type;  /* PRT_MAT_* */
+    int32_t reserved[4];    /* written as 0 */
+} PrtSurface;
+/* On a miss: t = +inf, alpha = beta = 0, prim = -1, front = 0 (the miss PrtHit), every other double 0,
+ * material = material_type = -1, reserved 0.
+ * Contract:
+ *  1. For every ray, bytes 0-31 of out[i] equal the PrtHit that prt_trace_closest_device_prec / _sorted_device writes for
+ *     the same ray record and precision, bit for bit (one traversal, one accept test).
+ *  2. The rest is a pure function of that head, the ray and the resident scene tables.  With PRT_PRECISION_F32 it is
+ *     computed from the float tables in float and widened at the boundary (tolerance tier 2).
+ *  3. The records reflect the resident geometry: after prt_scene_refit* they follow the refitted records and tangents, and
+ *     the call orders itself after a refit like every other trace call.
+ *  4. Exactly n records are written; bytes beyond them stay as they are.  n == 0 is PRT_OK.
+ *  5. Arguments, checks and error codes are those of the occlusion calls: PRT_E_NO_DEVICE on a scene that is not uploaded
+ *     (the message names the function), PRT_E_INVALID for a null buffer with n > 0, an unknown precision, n >= 2^32 in the
+ *     sorted call — and for a d_out that is not 32-byte aligned (the kernel stores 32 bytes at a time).
+ *  6. Afterwards prt_get_counters reports rays_closest == n, rays_shadow == 0, samples == 0 and kernel_ms (keys + sort +
+ *     trace for the sorted call); with count_work != 0 node_fetches / tri_tests / tri_full are those of the closest-hit
+ *     call on the same batch. */
+int prt_trace_surface(PrtScene* scene, const PrtRay* rays, size_t n, PrtSurface* out, int count_work); /* host buffers, fp64 */
+/* On device-resident buffers (d_rays: n PrtRay, d_out: n PrtSurface, 32-byte aligned); stream may be NULL. */
+int prt_trace_surface_device(PrtScene* scene, const void* d_rays, size_t n, void* d_out,
+                             int count_work, int precision, void* hip_stream);
+/* K4 first, as prt_trace_closest_sorted_device: same bytes, the batch traced in a locality order. */
+int prt_trace_surface_sorted_device(PrtScene* scene, const void* d_rays, size_t n, void* d_out,
+                                    int count_work, int precision, void* hip_stream);
+
 /* NEE point selection for (pixel, sample) keys 0..n-1 of `seed` from given origins (test hook). */
 int prt_sample_lights(PrtScene* scene, const double* origins, size_t n, uint64_t seed,
                       PrtLightSample* out);

@@ -189,6 +189,25 @@ class PrtHit(C.Structure):
     ]
 
 
+class PrtSurface(C.Structure):
+    _fields_ = [
+        ("t", C.c_double),
+        ("alpha", C.c_double),
+        ("beta", C.c_double),
+        ("prim", C.c_int32),
+        ("front", C.c_int32),
+        ("position", D3),
+        ("normal", D3),
+        ("tangent", D3),
+        ("uv", C.c_double * 2),
+        ("albedo", D3),
+        ("emission", D3),
+        ("material", C.c_int32),
+        ("material_type", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 class PrtLightSample(C.Structure):
     _fields_ = [
         ("position", D3),
@@ -221,11 +240,15 @@ import numpy as np  # noqa: E402
 
 RAY_DTYPE = np.dtype([("o", "<f8", 3), ("tmin", "<f8"), ("d", "<f8", 3), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"), ("front", "<i4")])
+SURFACE_DTYPE = np.dtype(HIT_DTYPE.descr + [
+    ("position", "<f8", 3), ("normal", "<f8", 3), ("tangent", "<f8", 3), ("uv", "<f8", 2), ("albedo", "<f8", 3),
+    ("emission", "<f8", 3), ("material", "<i4"), ("material_type", "<i4"), ("reserved", "<i4", 4)])
 LIGHT_SAMPLE_DTYPE = np.dtype(
     [("position", "<f8", 3), ("normal", "<f8", 3), ("pdf", "<f8"), ("prim", "<i4"), ("front", "<i4")]
 )
 assert RAY_DTYPE.itemsize == C.sizeof(PrtRay) == 64
 assert HIT_DTYPE.itemsize == C.sizeof(PrtHit) == 32
+assert SURFACE_DTYPE.itemsize == C.sizeof(PrtSurface) == 192
 assert LIGHT_SAMPLE_DTYPE.itemsize == C.sizeof(PrtLightSample) == 64
 
 # every symbol include/prt.h declares
@@ -254,6 +277,9 @@ EXPORTS = [
     "prt_trace_occluded",
     "prt_trace_occluded_device",
     "prt_trace_occluded_sorted_device",
+    "prt_trace_surface",
+    "prt_trace_surface_device",
+    "prt_trace_surface_sorted_device",
     "prt_sample_lights",
     "prt_render",
     "prt_render_device",

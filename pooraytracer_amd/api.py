@@ -65,6 +65,9 @@ def load():
     L.prt_trace_occluded.argtypes = [vp, vp, sz, vp, i32]
     L.prt_trace_occluded_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
     L.prt_trace_occluded_sorted_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
+    L.prt_trace_surface.argtypes = [vp, vp, sz, vp, i32]
+    L.prt_trace_surface_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
+    L.prt_trace_surface_sorted_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
     L.prt_sample_lights.argtypes = [vp, vp, sz, u64, vp]
     L.prt_render.argtypes = [vp, vp, vp, vp, vp]
     L.prt_render_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
@@ -296,6 +299,20 @@ class Scene:
         """The any-hit kernel on device buffers: one byte per ray into d_out_ptr; precision and sort as trace_closest_device."""
         fn = self._L.prt_trace_occluded_sorted_device if sort else self._L.prt_trace_occluded_device
         _check(fn(self._h, d_rays_ptr, n, d_out_ptr, int(count_work), int(precision), stream))
+
+    def trace_surface(self, rays, count_work=False):
+        """Surface query: a SURFACE_DTYPE array [n] — trace_closest's hit record followed by position, face-forwarded normal,
+        tangent, uv, the material's albedo and emission and its index and type (all zero / -1 on a miss)."""
+        rays = np.ascontiguousarray(rays, dtype=_abi.RAY_DTYPE)
+        out = np.zeros(rays.shape[0], dtype=_abi.SURFACE_DTYPE)
+        _check(self._L.prt_trace_surface(self._h, rays.ctypes.data, rays.shape[0], out.ctypes.data, int(count_work)), self._L)
+        return out
+
+    def trace_surface_device(self, d_rays_ptr, n, d_out_ptr, count_work=False, stream=None, precision=0, sort=False):
+        """The surface kernel on device buffers: one 192-byte PrtSurface per ray into d_out_ptr (32-byte aligned); precision
+        and sort as trace_closest_device."""
+        fn = self._L.prt_trace_surface_sorted_device if sort else self._L.prt_trace_surface_device
+        _check(fn(self._h, d_rays_ptr, n, d_out_ptr, int(count_work), int(precision), stream), self._L)
 
     def sample_lights(self, origins, seed=1):
         origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

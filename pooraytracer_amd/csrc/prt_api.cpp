@@ -27,7 +27,7 @@ int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_dep
 int render_permutation(int feat);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
+void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
                   int n_cu, hipStream_t st, const uint32_t* d_perm);
 // K4 (ray_sort.hip): a permutation of a ray batch in which consecutive rays start close together
 size_t ray_sort_scratch_bytes(size_t n, std::string* err);
@@ -93,7 +93,7 @@ typedef DSceneT<float> Scene32;
 int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
+void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
                   int n_cu, hipStream_t st, const uint32_t* d_perm);
 void launch_render(const Scene32& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
                    DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st);
@@ -1402,35 +1402,45 @@ int prt_trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_
     return prt_trace_closest_device_prec(s, d_rays, n, d_hits, count_work, PRT_PRECISION_F64, stream);
 }
 
-// One body for the four device batch calls: `occluded` picks the any-hit kernel (d_out = one byte per ray) over the
-// closest-hit one (d_out = one PrtHit per ray); `who` names the public function in error messages.
+// One body for the six device batch calls: `mode` (PRT_TRACE_*) picks what K1 writes per ray — a PrtHit, the any-hit byte
+// (any-hit traversal) or a PrtSurface; `who` names the public function in error messages.
 static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
-                              bool sorted, bool occluded, const char* who);
+                              bool sorted, int mode, const char* who);
 int prt_trace_closest_device_prec(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                   void* stream) {
-    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, false, false, "prt_trace_closest_device");
+    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, false, PRT_TRACE_CLOSEST, "prt_trace_closest_device");
 }
 int prt_trace_closest_sorted_device(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                     void* stream) {
-    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, true, false,
+    return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, true, PRT_TRACE_CLOSEST,
                               "prt_trace_closest_sorted_device");
 }
 int prt_trace_occluded_device(PrtScene* s, const void* d_rays, size_t n, void* d_occluded, int count_work, int precision,
                               void* stream) {
-    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, false, true, "prt_trace_occluded_device");
+    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, false, PRT_TRACE_ANY, "prt_trace_occluded_device");
 }
 int prt_trace_occluded_sorted_device(PrtScene* s, const void* d_rays, size_t n, void* d_occluded, int count_work, int precision,
                                      void* stream) {
-    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, true, true,
+    return trace_batch_device(s, d_rays, n, d_occluded, count_work, precision, stream, true, PRT_TRACE_ANY,
                               "prt_trace_occluded_sorted_device");
 }
+int prt_trace_surface_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream) {
+    return trace_batch_device(s, d_rays, n, d_out, count_work, precision, stream, false, PRT_TRACE_SURFACE, "prt_trace_surface_device");
+}
+int prt_trace_surface_sorted_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision,
+                                    void* stream) {
+    return trace_batch_device(s, d_rays, n, d_out, count_work, precision, stream, true, PRT_TRACE_SURFACE,
+                              "prt_trace_surface_sorted_device");
+}
 static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
-                              bool sorted, bool occluded, const char* who) {
+                              bool sorted, int mode, const char* who) {
     int rc = require_uploaded(s, who);
     if (rc) return rc;
     if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, std::string(who) + ": more than 2^32 - 1 rays in one batch");
     if (n && (!d_rays || !d_out)) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
     if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, std::string(who) + ": unsupported precision");
+    if (mode == PRT_TRACE_SURFACE && (reinterpret_cast<uintptr_t>(d_out) & 31u)) // the kernel stores a record 32 bytes at a time
+        return fail(PRT_E_INVALID, std::string(who) + ": output buffer is not 32-byte aligned");
     if (precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipError_t we;
@@ -1454,9 +1464,9 @@ static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d
     const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
     const bool count = count_work != 0;
     if (precision == PRT_PRECISION_F32)
-        prt32::launch_trace(s->k32.d, rays, n, d_out, q.d_ctr.get(), count, occluded, s->n_cu, st, d_perm);
+        prt32::launch_trace(s->k32.d, rays, n, d_out, q.d_ctr.get(), count, mode, s->n_cu, st, d_perm);
     else
-        prt::launch_trace(s->k64.d, rays, n, d_out, q.d_ctr.get(), count, occluded, s->n_cu, st, d_perm);
+        prt::launch_trace(s->k64.d, rays, n, d_out, q.d_ctr.get(), count, mode, s->n_cu, st, d_perm);
     PRT_HIP(hipGetLastError());
     PRT_HIP(q.stop(st));
     PRT_HIP(q.finish(st, count, 0));
@@ -1464,9 +1474,10 @@ static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d
     return PRT_OK;
 }
 
-// One body for the two host-buffer batch calls (fp64, unsorted): `elem` = bytes per ray of the output (a PrtHit, or the
-// any-hit byte); `who` names the public function in error messages, and its device call (`who`_device) does the work.
-static int trace_batch_host(PrtScene* s, const PrtRay* rays, size_t n, void* out, size_t elem, int count_work, bool occluded,
+// One body for the three host-buffer batch calls (fp64, unsorted): `elem` = bytes per ray of the output (a PrtHit, the
+// any-hit byte, or a PrtSurface); `who` names the public function in error messages, and its device call (`who`_device)
+// does the work.
+static int trace_batch_host(PrtScene* s, const PrtRay* rays, size_t n, void* out, size_t elem, int count_work, int mode,
                             const char* who) {
     int rc = require_uploaded(s, who);
     if (rc) return rc;
@@ -1476,17 +1487,21 @@ static int trace_batch_host(PrtScene* s, const PrtRay* rays, size_t n, void* out
     void* dr = b.in(rays, n * sizeof(PrtRay));
     void* dh = b.out(n * elem);
     const std::string dev = std::string(who) + "_device";
-    if ((rc = b.status(who)) || (rc = trace_batch_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr, false, occluded, dev.c_str())))
+    if ((rc = b.status(who)) || (rc = trace_batch_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr, false, mode, dev.c_str())))
         return rc;
     b.sync();
     b.down(out, dh, n * elem);
     return b.status(who);
 }
 int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, int count_work) {
-    return trace_batch_host(s, rays, n, hits, sizeof(PrtHit), count_work, false, "prt_trace_closest");
+    return trace_batch_host(s, rays, n, hits, sizeof(PrtHit), count_work, PRT_TRACE_CLOSEST, "prt_trace_closest");
 }
 int prt_trace_occluded(PrtScene* s, const PrtRay* rays, size_t n, uint8_t* occluded, int count_work) {
-    return trace_batch_host(s, rays, n, occluded, 1, count_work, true, "prt_trace_occluded");
+    return trace_batch_host(s, rays, n, occluded, 1, count_work, PRT_TRACE_ANY, "prt_trace_occluded");
+}
+int prt_trace_surface(PrtScene* s, const PrtRay* rays, size_t n, PrtSurface* out, int count_work) {
+    static_assert(sizeof(PrtSurface) == 192, "PrtSurface is 192 bytes");
+    return trace_batch_host(s, rays, n, out, sizeof(PrtSurface), count_work, PRT_TRACE_SURFACE, "prt_trace_surface");
 }
 
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {

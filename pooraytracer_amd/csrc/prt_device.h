@@ -458,7 +458,9 @@ PRT_DEV int wave_count(bool p) { return __popcll(__ballot(p)); }
 #define PRT_TEX_QUAD_REALS 16
 // EXTRA (PRT_FEAT_EXTRA kernels): the scene may hold plain texel arrays; kernels for scenes that do not are compiled without that
 // path (its mere presence cost the bathroom2 frame 1.3 % in a same-box A/B: the textured kernel sits at its register limit).
-template <bool EXTRA>
+// NARROW (PRT_FEAT_NARROW callers): the footprint is fetched and blended one row of taps at a time — two thirds of the
+// registers of the twelve-tap fetch, for a caller that has few to spare and one lookup per ray (K1's surface write-out).
+template <bool EXTRA, bool NARROW = false>
 PRT_DEV d3 tex_value(const DScene& S, int ti, real u, real v) {
     const DTexture tx = S.textures[ti];
     if (!tx.has_data) return mk3(RL(0.), RL(1.), RL(1.));
@@ -471,12 +473,26 @@ PRT_DEV d3 tex_value(const DScene& S, int ti, real u, real v) {
     d3 c00, c10, c01, c11;
     if (!EXTRA || !S.tex_compact) { // footprint record of cell (x0, y0): the four taps in one 128-byte line (wave-uniform choice)
         const real4* q = reinterpret_cast<const real4*>(S.texels_lin + tx.offset + (size_t)(y0 * tx.width + x0) * PRT_TEX_QUAD_REALS);
+        if (NARROW) {
+            const real4 r0 = q[0], r1 = q[1];
+            const d3 top = mk3(r0.x, r0.y, r0.z) * (1 - fx) + mk3(r0.w, r1.x, r1.y) * fx;
+            __builtin_amdgcn_sched_barrier(0);
+            const real4 r2 = q[2];
+            const d3 bot = mk3(r1.z, r1.w, r2.x) * (1 - fx) + mk3(r2.y, r2.z, r2.w) * fx;
+            return top * (1 - fy) + bot * fy;
+        }
         const real4 q0 = q[0], q1 = q[1], q2 = q[2];
         c00 = mk3(q0.x, q0.y, q0.z), c10 = mk3(q0.w, q1.x, q1.y);
         c01 = mk3(q1.z, q1.w, q2.x), c11 = mk3(q2.y, q2.z, q2.w);
     } else { // plain texel arrays (a scene beyond its footprint budget): Texture.cpp:35-41's four GetPixel calls
         const int x1 = min(x0 + 1, tx.width - 1), y1 = min(y0 + 1, tx.height - 1);
         const real* base = S.texels_lin + tx.offset;
+        if (NARROW) {
+            const d3 top = ld3(base + ((size_t)y0 * tx.width + x0) * 3) * (1 - fx) + ld3(base + ((size_t)y0 * tx.width + x1) * 3) * fx;
+            __builtin_amdgcn_sched_barrier(0);
+            const d3 bot = ld3(base + ((size_t)y1 * tx.width + x0) * 3) * (1 - fx) + ld3(base + ((size_t)y1 * tx.width + x1) * 3) * fx;
+            return top * (1 - fy) + bot * fy;
+        }
         c00 = ld3(base + ((size_t)y0 * tx.width + x0) * 3), c10 = ld3(base + ((size_t)y0 * tx.width + x1) * 3);
         c01 = ld3(base + ((size_t)y1 * tx.width + x0) * 3), c11 = ld3(base + ((size_t)y1 * tx.width + x1) * 3);
     }
@@ -745,14 +761,15 @@ PRT_DEV d3 ct_sample_wm(const DMaterial& m, d3 w, d2 u) { // Material.h:412-435
 // sample_lights and the plain-texel-array path of tex_value.  A scene that needs neither (no emissive subtree of >= 16
 // triangles, textures within the footprint budget) runs the kernels without them (same-box A/B: cornell +0.9 %, bathroom2 +1.3 %).
 #define PRT_FEAT_EXTRA 8
+#define PRT_FEAT_NARROW 16 // not a material feature either: texture lookups of this caller fetch their footprint a row at a time (tex_value)
 template <int FEAT>
 PRT_DEV d3 mat_kd(const DScene& S, const DMaterial& m, d2 uv) {
-    if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0>(S, m.texture, uv.x, uv.y);
+    if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0, (FEAT & PRT_FEAT_NARROW) != 0>(S, m.texture, uv.x, uv.y);
     return ld3(m.kd);
 }
 template <int FEAT>
 PRT_DEV d3 mat_ks(const DScene& S, const DMaterial& m, d2 uv) { // Phong(mapKd,...) stores the map in Ks too (:178-181)
-    if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0>(S, m.texture, uv.x, uv.y);
+    if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0, (FEAT & PRT_FEAT_NARROW) != 0>(S, m.texture, uv.x, uv.y);
     return ld3(m.ks);
 }
 template <int FEAT>

@@ -1,6 +1,7 @@
 // prt_kernels.hip — gfx950 kernels of the path-tracing hot path and their launchers.
 //
 //   K1 k_trace           closest hit / any hit for a ray batch     (world.Hit, BVH.cpp:51-61)
+//      k_trace_surface   closest hit with the whole HitRecord and the material's response (PrtSurface)
 //   K3 k_render          persistent-wavefront path tracer          (Camera::Render/RayColor, Camera.cpp:21-204)
 //   K5 k_finalize        ordered sum of per-chunk partial sums -> f64 / f32 framebuffer
 //      k_sample_lights   lights.Sample test hook                   (BVH.cpp:62-67,86-100)
@@ -112,6 +113,14 @@ __device__ __forceinline__ T wave_sum(T v) {
 #endif
 #ifndef PRT_K1O_WAVES
 #define PRT_K1O_WAVES PRT_K1_WAVES
+#endif
+// K1s (k_trace_surface, after the shading helpers it shares with K3 and k_features): the closest-hit loop once more, with a
+// third write-out — where K1 writes its PrtHit the lane also reads the hit's shading record and material and writes one
+// PrtSurface.  A sibling kernel, not a third mode of k_trace: as a mode (the loop as a device function under two wrappers)
+// the any-hit instantiations compiled to other multiply-add contractions than before, and their bytes left the closest-hit
+// kernel's on edge-grazing rays (2 of 400,000 on the 2M-triangle soup in fp32).
+#ifndef PRT_K1S_WAVES
+#define PRT_K1S_WAVES PRT_K1_WAVES // the 40 KB of stacks allow four blocks per CU; the surface write-out fits their 128 registers without scratch
 #endif
 template <bool COUNT, bool PAD, bool ANY>
 __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void k_trace(DScene S, const PrtRay* __restrict__ rays, size_t n,
@@ -225,24 +234,162 @@ struct ShadeCtx {
     int32_t material;
 };
 // `rd` = the direction the hit was reached along, (alpha, beta, tri) = the hit (read in place: no HitInfo copy)
+// The three expressions every consumer of a hit shares (K3's make_ctx, k_features, the surface write-out of K1):
+// HitRecord::SetFaceNormal (Hittable.cpp:8-13) on the stored geometric normal, ...
+PRT_DEV d3 face_normal(d3 rd, d3 gn) {
+    const bool front = dot(rd, gn) < RL(0.);
+    return front ? gn : -gn;
+}
+// ... the texture coordinates of Triangle.cpp:111, ...
+PRT_DEV d2 hit_uv(const DTriShade* sh, real alpha, real beta) {
+    const real w0 = RL(1.) - alpha - beta;
+    d2 uv;
+    uv.x = w0 * sh->uv0[0] + alpha * sh->uv1[0] + beta * sh->uv2[0];
+    uv.y = w0 * sh->uv0[1] + alpha * sh->uv1[1] + beta * sh->uv2[1];
+    return uv;
+}
+// ... and the albedo feature of prt_render_features (include/prt.h): what the material multiplies diffuse light by
+template <int F>
+PRT_DEV d3 feature_albedo(const DScene& S, const DMaterial& m, d2 uv) {
+    d3 a = mk3(1, 1, 1);
+    if (m.type == PRT_MAT_LAMBERTIAN || m.type == PRT_MAT_DEBUG) a = mat_kd<F>(S, m, uv);
+    else if (m.type == PRT_MAT_PHONG) a = mat_kd<F>(S, m, uv) + mat_ks<F>(S, m, uv);
+    return a;
+}
 template <int FEAT, bool PAD>
 PRT_DEV ShadeCtx make_ctx(const DScene& S, d3 rd, real alpha, real beta, int32_t tri) {
     ShadeCtx c;
     const DTriShade* sh = S.shade + tri;
     const DTri* T = tri_at<PAD>(S, (uint32_t)tri);
     const d3 gn = mk3(T->n[0], T->n[1], T->n[2]);
-    const bool front = dot(rd, gn) < RL(0.);
-    c.f.n = front ? gn : -gn;
+    c.f.n = face_normal(rd, gn);
     c.f.t = ld3(sh->tangent);
     if (FEAT & PRT_FEAT_TEX) { // texture coordinates are only read by image-textured materials
-        const real w0 = RL(1.) - alpha - beta;
-        c.uv.x = w0 * sh->uv0[0] + alpha * sh->uv1[0] + beta * sh->uv2[0];
-        c.uv.y = w0 * sh->uv0[1] + alpha * sh->uv1[1] + beta * sh->uv2[1];
+        c.uv = hit_uv(sh, alpha, beta);
     } else {
         c.uv.x = c.uv.y = RL(0.0);
     }
     c.material = sh->material;
     return c;
+}
+
+// K1's surface write-out: one PrtSurface from the ray the lane still holds and its finished closest-hit traversal.  The head
+// is the PrtHit k_trace writes (same expressions on the same values); the body is computed in `real` and widened at the
+// store.  Twelve 16-byte stores, each value stored as soon as it is known and the albedo — the only one behind a texture
+// fetch — last: the twelve taps of a footprint then share the registers with the traversal state alone, not with a record
+// waiting to be written (the fp64 kernel: 13 registers spilled when the record was put together first).
+template <bool PAD>
+PRT_DEV void surface_record(const DScene& S, d3 o, d3 d, const HitInfo& hit, PrtSurface* __restrict__ out) {
+    static_assert(sizeof(PrtSurface) == 192 && offsetof(PrtSurface, position) == 32 && offsetof(PrtSurface, material) == 168, "PrtSurface layout");
+    double2* q = reinterpret_cast<double2*>(out); // (the host checks the buffer's alignment)
+    if (hit.tri >= 0) {
+        const DTriShade* sh = S.shade + hit.tri;
+        const d3 gn = ld3(tri_at<PAD>(S, (uint32_t)hit.tri)->n);
+        const int32_t front = dot(d, gn) < RL(0.) ? 1 : 0; // as k_trace's head
+        const unsigned long long pf = (unsigned long long)(uint32_t)sh->prim | ((unsigned long long)(uint32_t)front << 32);
+        q[0] = make_double2((double)hit.t, (double)hit.alpha);
+        q[1] = make_double2((double)hit.beta, __longlong_as_double((long long)pf));
+        const d3 p = o + d * hit.t; // Ray::operator()
+        const d3 fn = face_normal(d, gn);
+        q[2] = make_double2((double)p.x, (double)p.y);
+        q[3] = make_double2((double)p.z, (double)fn.x);
+        q[4] = make_double2((double)fn.y, (double)fn.z);
+        __builtin_amdgcn_sched_barrier(0); // (the shading record is fetched once the head and the normal are on their way, ...
+        const d3 tg = ld3(sh->tangent);
+        const d2 uv = hit_uv(sh, hit.alpha, hit.beta);
+        q[5] = make_double2((double)tg.x, (double)tg.y);
+        q[6] = make_double2((double)tg.z, (double)uv.x);
+        __builtin_amdgcn_sched_barrier(0); // ... and the material after it: fetched all at once they cost the counting kernel two spilled registers)
+        const int32_t mi = sh->material;
+        const DMaterial& m = S.materials[mi];
+        const d3 em = ld3(m.emission);
+        const unsigned long long mt = (unsigned long long)(uint32_t)mi | ((unsigned long long)(uint32_t)m.type << 32);
+        q[9] = make_double2((double)em.x, (double)em.y);
+        q[10] = make_double2((double)em.z, __longlong_as_double((long long)mt));
+        q[11] = make_double2(0.0, 0.0);
+        const d3 a = feature_albedo<PRT_FEAT_ALL | PRT_FEAT_EXTRA | PRT_FEAT_NARROW>(S, m, uv);
+        q[7] = make_double2((double)uv.y, (double)a.x);
+        q[8] = make_double2((double)a.y, (double)a.z);
+    } else {
+        const double2 z = make_double2(0.0, 0.0);
+        q[0] = make_double2((double)PRT_INF, 0.0);
+        q[1] = make_double2(0.0, __longlong_as_double(0x00000000ffffffffLL)); // prim -1, front 0
+        for (int k = 2; k < 12; ++k) q[k] = z;
+        q[10] = make_double2(0.0, __longlong_as_double(-1LL)); // material = material_type = -1
+    }
+}
+
+template <bool COUNT, bool PAD>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_K1S_WAVES) void k_trace_surface(DScene S, const PrtRay* __restrict__ rays, size_t n,
+                                                                            PrtSurface* __restrict__ out, DCounters* ctr,
+                                                                            const uint32_t* __restrict__ perm) { // K4's order (ray_sort.hip) or null
+    __shared__ uint32_t s_stack[PRT_BLOCK / 64][PRT_STACK_DEPTH][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t* stk = &s_stack[wave][0][lane];
+    WorkCount wc{0, 0, 0, 0, 0};
+    uint32_t nrays = 0;
+    Trav<PAD> tr;
+    tr.init(S, mk3(0, 0, 0), mk3(0, 0, 1), RL(0.0), RL(0.0));
+    tr.hit.alpha = tr.hit.beta = RL(0.0);
+    tr.active = false;
+    bool have = false;
+    size_t my = 0;
+    // wave-local ray pool [pool_next, pool_end): refilled PRT_K1_CHUNK rays at a time by ONE atomic per
+    // wave (a single global counter saturates at ~90 dequeues/us on this chip)
+    unsigned long long pool_next = 0, pool_end = 0;
+    bool exhausted = false; // wave-uniform
+    for (;;) {
+        if (!tr.active && have) {
+            surface_record<PAD>(S, tr.o, tr.d, tr.hit, out + my);
+            have = false;
+        }
+        {
+            const unsigned long long need = __ballot(!tr.active);
+            if (need != 0ULL && !exhausted) {
+                if (pool_next >= pool_end) {
+                    unsigned long long base = 0;
+                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
+                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
+                    pool_next = base;
+                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
+                    if (base >= (unsigned long long)n) exhausted = true;
+                }
+                if (!exhausted && !tr.active) {
+                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
+                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
+                    if (idx < pool_end) {
+                        const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
+                        const double4* rp = reinterpret_cast<const double4*>(rays + ri);
+                        const double4 r0 = rp[0], r1 = rp[1];
+                        tr.init(S, mk3((real)r0.x, (real)r0.y, (real)r0.z), mk3((real)r1.x, (real)r1.y, (real)r1.z), (real)r0.w, (real)r1.w); // PrtRay is fp64 at the ABI in either mode
+                        my = ri;
+                        have = true;
+                        nrays++;
+                    }
+                }
+                if (!exhausted) {
+                    const unsigned long long taken = (unsigned long long)__popcll(need);
+                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
+                }
+            }
+        }
+        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
+        do {
+            tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, false);
+        } while (wave_count(tr.active) > PRT_K1_KEEP);
+    }
+    unsigned long long a = wave_sum((unsigned long long)nrays);
+    unsigned long long b = wave_sum((unsigned long long)wc.nodes);
+    unsigned long long c = wave_sum((unsigned long long)wc.tris);
+    unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
+    if (lane == 0) {
+        atomicAdd(&ctr->rays_closest, a);
+        if (COUNT) {
+            atomicAdd(&ctr->node_fetches, b);
+            atomicAdd(&ctr->tri_tests, c);
+            atomicAdd(&ctr->tri_full, f);
+        }
+    }
 }
 
 // A real number parked in / fetched from a lane's LDS column (`base` = the lane's slot of word 0, words PRT_BLOCK apart)
@@ -1299,14 +1446,9 @@ __global__ __launch_bounds__(PRT_BLOCK) void k_features(DScene S, DCamera C, uin
         const DTriShade* sh = S.shade + tr.hit.tri;
         const DMaterial& m = S.materials[sh->material];
         const d3 gn = ld3(tri_at<PAD>(S, (uint32_t)tr.hit.tri)->n);
-        const d3 fn = dot(tr.d, gn) < RL(0.) ? gn : -gn; // SetFaceNormal, as make_ctx
-        const real w0 = RL(1.) - tr.hit.alpha - tr.hit.beta;
-        const d2 uv{w0 * sh->uv0[0] + tr.hit.alpha * sh->uv1[0] + tr.hit.beta * sh->uv2[0],
-                    w0 * sh->uv0[1] + tr.hit.alpha * sh->uv1[1] + tr.hit.beta * sh->uv2[1]};
-        constexpr int F = PRT_FEAT_ALL | PRT_FEAT_EXTRA;
-        d3 a = mk3(1, 1, 1);
-        if (m.type == PRT_MAT_LAMBERTIAN || m.type == PRT_MAT_DEBUG) a = mat_kd<F>(S, m, uv);
-        else if (m.type == PRT_MAT_PHONG) a = mat_kd<F>(S, m, uv) + mat_ks<F>(S, m, uv);
+        const d3 fn = face_normal(tr.d, gn); // SetFaceNormal, as make_ctx
+        const d2 uv = hit_uv(sh, tr.hit.alpha, tr.hit.beta);
+        const d3 a = feature_albedo<PRT_FEAT_ALL | PRT_FEAT_EXTRA>(S, m, uv);
         a_sum = a_sum + a;
         n_sum = n_sum + fn;
         z_sum += (double)tr.hit.t * sqrt((double)dot(tr.d, tr.d)); // world distance: d is not normalised
@@ -1397,19 +1539,29 @@ int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_dep
     return nb;
 }
 
-// One batch of rays through K1: `any_hit` picks the any-hit form (d_out = one byte per ray) over the closest-hit one
-// (d_out = one PrtHit per ray).
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, bool any_hit,
+// One batch of rays through K1: `mode` (PRT_TRACE_*, prt_types.h) picks the closest-hit form (d_out = one PrtHit per ray), the
+// any-hit form (one byte per ray) or the surface form (one PrtSurface per ray, 32-byte aligned).
+void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
                   int n_cu, hipStream_t st, const uint32_t* d_perm) {
     if (n == 0) return;
     size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
     const size_t per_cu = std::max<size_t>(1, (160u * 1024u) / (sizeof(uint32_t) * PRT_STACK_DEPTH * PRT_BLOCK)); // LDS stacks per CU
     unsigned grid = (unsigned)std::min<size_t>(want, (size_t)n_cu * per_cu);
     const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
+    const bool any_hit = mode == PRT_TRACE_ANY;
     const int pick = (count ? 4 : 0) | (pad ? 2 : 0) | (any_hit ? 1 : 0);
     auto go = [&](auto k, auto* out) { hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, out, d_ctr, d_perm); };
     PrtHit* hits = static_cast<PrtHit*>(d_out);
     uint8_t* bytes = static_cast<uint8_t*>(d_out);
+    if (mode == PRT_TRACE_SURFACE) {
+        PrtSurface* recs = static_cast<PrtSurface*>(d_out);
+        switch (pick >> 1) {
+        case 0: return go(k_trace_surface<false, false>, recs);
+        case 1: return go(k_trace_surface<false, true>, recs);
+        case 2: return go(k_trace_surface<true, false>, recs);
+        default: return go(k_trace_surface<true, true>, recs);
+        }
+    }
     switch (pick) {
     case 0: return go(k_trace<false, false, false>, hits);
     case 1: return go(k_trace<false, false, true>, bytes);

@@ -208,6 +208,11 @@ typedef DRenderParamsT<prt_real> DRenderParams;
 #define PRT_QUEUE_STRIDE 32 // in 8-byte words: one counter per 256 bytes (different memory channels)
 #define PRT_ITEMS_FROM_LIST 2 // DRenderParams::scramble: pixels come from DCounters::pixel_list (prt_render_samples, adaptive rounds)
 
+// launch_trace's `mode`: what K1 writes per ray
+#define PRT_TRACE_CLOSEST 0 // one PrtHit
+#define PRT_TRACE_ANY 1     // one byte (any-hit traversal)
+#define PRT_TRACE_SURFACE 2 // one PrtSurface (closest-hit traversal + the hit's shading record and material)
+
 // device-side counters, zeroed before each call
 struct DCounters {
     unsigned long long next_item;

@@ -147,6 +147,35 @@ bool Hittable::Hit(const Ray& ray, Interval domain, HitRecord& record) const {
     return true;
 }
 
+std::vector<bool> Hittable::Hit(const std::vector<Ray>& rays, Interval domain, std::vector<HitRecord>& records) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    std::vector<PrtRay> r(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        r[i].o[0] = rays[i].origin.x; r[i].o[1] = rays[i].origin.y; r[i].o[2] = rays[i].origin.z;
+        r[i].d[0] = rays[i].direction.x; r[i].d[1] = rays[i].direction.y; r[i].d[2] = rays[i].direction.z;
+        r[i].tmin = domain.min;
+        r[i].tmax = domain.max;
+    }
+    std::vector<PrtSurface> s(rays.size());
+    check(prt_trace_surface(dc.scene, r.data(), r.size(), s.data(), 0), "prt_trace_surface");
+    records.assign(rays.size(), HitRecord());
+    std::vector<bool> hit(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        if (s[i].prim < 0) continue;
+        HitRecord& rec = records[i];
+        rec.position = vec3(s[i].position[0], s[i].position[1], s[i].position[2]);
+        rec.time = s[i].t;
+        rec.normal = vec3(s[i].normal[0], s[i].normal[1], s[i].normal[2]);
+        rec.tangent = vec3(s[i].tangent[0], s[i].tangent[1], s[i].tangent[2]);
+        rec.uv = vec2(s[i].uv[0], s[i].uv[1]);
+        rec.material = dc.flat.triangles[(size_t)s[i].prim]->material;
+        rec.bFrontFace = s[i].front != 0;
+        hit[i] = true;
+    }
+    return hit;
+}
+
 std::vector<bool> Hittable::Occluded(const std::vector<Ray>& rays, Interval domain) const {
     DeviceCache& dc = Device();
     dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
