@@ -9,6 +9,7 @@
 
 #include "HittableList.h"
 #include "Math.h"
+#include "Ray.h"
 
 struct PrtCamera;
 struct PrtRenderParams;
@@ -50,6 +51,13 @@ public:
     // of rounds that rendered.  Single device only, like RenderProgressive.  It also fills varianceAttachment (below).
     int RenderAdaptive(Hittable& world, Hittable& lights, double relTol, int minSpp, int maxSpp,
                        std::vector<uint32_t>* counts = nullptr, double absTol = 0.0, int batch = 0, int roundSpp = 0);
+    // Addition (not in the reference): RayColor for rays of the caller's own (prt.h prt_ray_color) — probes, lightmap texels,
+    // camera models this class lacks.  out[i] = the mean over `samples` samples of RayColor(rays[i], maxDepth, world, lights)
+    // (Camera.cpp:119-204) with this camera's maxDepth, russianRoulette, bSampleLights, background, seed and precision; ray
+    // i draws from the streams keyed (seed, i, s).  Directions are not normalised.  The image fields, samplesPerPixel and
+    // bPixelJitter are not used.  Throws std::invalid_argument for a non-finite ray or a zero direction.  Single device
+    // only, like RenderProgressive.
+    void RayColor(const std::vector<Ray>& rays, Hittable& world, Hittable& lights, int samples, std::vector<color>& out);
     // Addition (not in the reference): the edge-aware a-trous denoiser (prt.h prt_denoise) on colorAttachment, guided by the
     // first-hit features of this camera (prt_render_features: albedo, normal, depth).  Runs after Render, RenderProgressive
     // or RenderAdaptive on the same world; params NULL = prt_denoise_defaults.  The result goes to denoisedAttachment;

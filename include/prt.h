@@ -15,6 +15,8 @@
  *                         (Source/HittableList.h:26-39 -> Source/BVH.cpp:51-61)
  *   prt_render            replaces Camera::Render(world, lights)      (Source/Camera.cpp:21-73)
  *   prt_render_device     same, framebuffer left in device memory for an RCCL reduce
+ *   prt_ray_color         replaces RayColor(ray, maxDepth, world, lights) (Source/Camera.cpp:119-204) for a batch of the
+ *                         caller's own rays: probes, lightmap texels, camera models the reference lacks
  *   prt_render_multi      same over several GPUs of this process: tiles + one RCCL reduce of the fp32 framebuffer
  *                         (replaces the std::thread row bands of Source/Camera.cpp:46-71)
  *   prt_sample_lights     replaces lights.Sample(origin, record, pdf) (Source/HittableList.h:44-59,
@@ -423,6 +425,42 @@ int prt_render(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* par
  * issue its calls from one host thread. */
 int prt_render_device(PrtScene* scene, const PrtCamera* cam, const PrtRenderParams* params,
                       void* d_rgb_f64, void* d_rgb_f32, int count_work, void* hip_stream);
+
+/*
+ * Radiance queries: RayColor for caller-supplied rays.  K3 itself, the path tracer of prt_render, with the batch as its ray
+ * source instead of a pinhole camera: one work item per (ray, sample chunk), the primary ray traced once per work item.
+ * Contract:
+ *  1. out[i][0..2] = the mean over samples s in [sample_begin, sample_begin + params->spp) of
+ *     RayColor(Ray(rays[i].o, rays[i].d), max_depth, world, lights) (Source/Camera.cpp:119-204).  Sample s of ray i draws from
+ *     the stream keyed (seed, key_i, s) with key_i = keys ? keys[i] : (uint32_t)i — a frame's keying with "pixel index"
+ *     replaced by "key": a batch of a camera's rays with key = j*W+i is that camera's frame.  Every term is scaled by 1/spp
+ *     as it is added, a work item sums its chunk in sample order and the chunks are added in ascending order: the rules of
+ *     prt_render and its K5.
+ *  2. Rays: d is not normalised (camera directions are not either).  tmin and tmax are NOT read: the primary ray is traced
+ *     over Interval(0.0001, inf) as RayColor traces it.
+ *  3. Parameters: spp, max_depth, russian_roulette, sample_lights, precision, background, seed and sample_chunks mean what
+ *     they mean in prt_render.  tile_size, rank and nranks are ignored (a batch has no tiles; a caller splits a batch
+ *     itself).  pixel_jitter and reserved must be 0: there is no pixel to jitter.
+ *  4. Both precisions.  With PRT_PRECISION_F32 the fp64 ray records are rounded to float on load (tolerance tier 2); partial
+ *     sums and outputs stay fp64.
+ *  5. Either output may be NULL, not both.  Exactly n triples are written; bytes beyond them stay as they are.  n == 0 is
+ *     PRT_OK.  max_depth < 0 gives zeros.
+ *  6. Errors: PRT_E_NO_DEVICE on a scene that is not uploaded (the message names the function); PRT_E_INVALID for a null
+ *     `rays` with n > 0, both outputs null, spp < 1, sample_begin < 0, sample_begin + spp > INT32_MAX, an unknown
+ *     precision, a nonzero pixel_jitter or reserved; PRT_E_LIMIT when n x sample chunks reaches 2^32.  The host-buffer call
+ *     also returns PRT_E_INVALID for a ray whose origin or direction is not finite or whose direction is zero.  The device
+ *     call does not check the rays: the result for such a ray is unspecified.
+ *  7. The call goes through the scene's two call slots like prt_render_device: it orders itself after a refit, and two
+ *     calls may be in flight on two streams.  Afterwards prt_get_counters reports rays_closest, rays_shadow,
+ *     samples == n * spp and K3's kernel_ms.  There is no count_work form and no trace signature.
+ * keys may be NULL.  The ray order is the caller's: neighbouring rays that start and point alike traverse together.
+ */
+int prt_ray_color(PrtScene* scene, const PrtRay* rays, const uint32_t* keys, size_t n, const PrtRenderParams* params,
+                  int32_t sample_begin, double* rgb_f64, float* rgb_f32); /* host buffers, synchronous */
+/* On device-resident buffers (d_rays: n PrtRay, d_keys: n uint32 or NULL, outputs: n triples); asynchronous on hip_stream,
+ * which may be NULL. */
+int prt_ray_color_device(PrtScene* scene, const void* d_rays, const void* d_keys, size_t n, const PrtRenderParams* params,
+                         int32_t sample_begin, void* d_rgb_f64, void* d_rgb_f32, void* hip_stream);
 
 /*
  * Camera::Render over several GPUs of one process — the reference's only parallel split is the thread fan-out over row

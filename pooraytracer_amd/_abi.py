@@ -283,6 +283,8 @@ EXPORTS = [
     "prt_sample_lights",
     "prt_render",
     "prt_render_device",
+    "prt_ray_color",
+    "prt_ray_color_device",
     "prt_get_counters",
     "prt_tonemap_srgb8",
     "prt_material_eval",

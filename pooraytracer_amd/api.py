@@ -71,6 +71,8 @@ def load():
     L.prt_sample_lights.argtypes = [vp, vp, sz, u64, vp]
     L.prt_render.argtypes = [vp, vp, vp, vp, vp]
     L.prt_render_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    L.prt_ray_color.argtypes = [vp, vp, vp, sz, vp, C.c_int32, vp, vp]
+    L.prt_ray_color_device.argtypes = [vp, vp, vp, sz, vp, C.c_int32, vp, vp, vp]
     L.prt_get_counters.argtypes = [vp, vp]
     L.prt_tonemap_srgb8.argtypes = [vp, vp, i32, i32, vp, vp]
     L.prt_material_eval.argtypes = [vp, i32, sz, vp, vp, vp, u64, vp]
@@ -373,6 +375,39 @@ class Scene:
         cam = camera or self.data.camera
         c, p = _abi.make_camera(cam), _abi.make_params(**kw)
         _check(self._L.prt_render_device(self._h, C.byref(c), C.byref(p), d_f64_ptr, d_f32_ptr, int(count_work), stream), self._L)
+
+    @staticmethod
+    def _ray_color_params(kw):
+        """PrtRenderParams of a ray batch: kw as for render(), plus `reserved` (the struct's reserved word, which must be 0)."""
+        reserved = kw.pop("reserved", 0)
+        p = _abi.make_params(**kw)
+        p.reserved = int(reserved)
+        return p
+
+    def ray_color(self, rays, keys=None, sample_begin=0, f32=False, **kw):
+        """RayColor of caller-supplied rays (prt_ray_color): rays a RAY_DTYPE array (o and d are read, d not normalised), keys
+        an optional uint32 array — ray i's random streams are keyed (seed, keys[i] or i, s).  Returns (n, 3) float64, the mean
+        over samples [sample_begin, sample_begin + spp) (and float32 if f32=True).  kw as for render(); tiles and ranks are
+        ignored, pixel_jitter must be off."""
+        rays = np.ascontiguousarray(rays, dtype=_abi.RAY_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+            if keys.shape[0] != n:
+                raise ValueError(f"ray_color: {keys.shape[0]} keys for {n} rays")
+        p = self._ray_color_params(kw)
+        out64 = np.zeros((n, 3), dtype=np.float64)
+        out32 = np.zeros((n, 3), dtype=np.float32) if f32 else None
+        _check(self._L.prt_ray_color(self._h, rays.ctypes.data, None if keys is None else keys.ctypes.data, n, C.byref(p),
+                                     int(sample_begin), out64.ctypes.data, out32.ctypes.data if f32 else None), self._L)
+        return (out64, out32) if f32 else out64
+
+    def ray_color_device(self, d_rays_ptr, n, d_f64_ptr, d_f32_ptr, d_keys_ptr=None, sample_begin=0, stream=None, **kw):
+        """prt_ray_color_device: asynchronous, on device buffers (raw pointers: n PrtRay, optionally n uint32 keys, n triples of
+        float64 and / or float32).  The rays are not checked: a non-finite or zero direction gives an unspecified result."""
+        p = self._ray_color_params(kw)
+        _check(self._L.prt_ray_color_device(self._h, d_rays_ptr, d_keys_ptr, int(n), C.byref(p), int(sample_begin), d_f64_ptr,
+                                            d_f32_ptr, stream), self._L)
 
     def features(self, camera=None, feature_spp=1, **kw):
         """First-hit feature buffers (prt_render_features, include/prt.h): dict of albedo (H, W, 3) float32, normal (H, W, 3)

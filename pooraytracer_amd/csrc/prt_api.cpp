@@ -23,7 +23,7 @@
 #include "prt_host.h"
 
 namespace prt {
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra);
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
 int render_permutation(int feat);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
@@ -34,9 +34,10 @@ size_t ray_sort_scratch_bytes(size_t n, std::string* err);
 const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
                          size_t scratch_bytes, hipStream_t st, std::string* err);
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,
-                   bool count, int feat, unsigned grid, hipStream_t st);
+                   bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
 void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d64, float* d32,
                      hipStream_t st);
+void launch_finalize_rays(const DRenderParams& P, const double* d_partial, double* d64, float* d32, hipStream_t st);
 void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st);
 void launch_resolve(const double* d_sum, size_t n, uint64_t samples, const uint32_t* d_counts, double* d64, float* d32,
                     uint8_t* d8, hipStream_t st);
@@ -90,13 +91,13 @@ void launch_gather_tris(const DTri* tri_in, const DTriShade* shade_in, const uin
 // fp32 fast mode (prt_kernels_f32.hip): K1 and K3 on float records derived from the resident fp64 ones
 namespace prt32 {
 typedef DSceneT<float> Scene32;
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra);
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
 void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
                   int n_cu, hipStream_t st, const uint32_t* d_perm);
 void launch_render(const Scene32& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
-                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st);
+                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
 void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
 void launch_convert_shade(const DTriShadeT<double>* in, uint32_t n, DTriShadeT<float>* out, hipStream_t st);
 void launch_convert_reals(const double* in, size_t n, float* out, hipStream_t st);
@@ -210,6 +211,7 @@ template <typename R>
 struct KernelConfig {
     DSceneT<R> d{};
     int blocks_per_cu[2] = {0, 0};
+    int blocks_per_cu_rays = 0; // ... and of the ray-batch instantiation (prt_ray_color), queried by its first call
     int light_lds = 0, ltri_lds = 0, mat_lds = 0;
     int stack_depth = PRT_STACK_DEPTH;
 };
@@ -311,6 +313,12 @@ struct PrtScene {
             if (!pixel_list && !trace) return hipSuccess; // zeroed already
             const void* ptrs[2] = {pixel_list, trace};
             return hipMemcpyAsync(reinterpret_cast<char*>(d_ctr.get()) + offsetof(DCounters, pixel_list), ptrs, sizeof(ptrs),
+                                  hipMemcpyHostToDevice, st);
+        }
+        // ... and the ray batch of prt_ray_color (DCounters::ray_list / key_list)
+        hipError_t set_rays(hipStream_t st, const void* rays, const void* keys) {
+            const void* ptrs[2] = {rays, keys};
+            return hipMemcpyAsync(reinterpret_cast<char*>(d_ctr.get()) + offsetof(DCounters, ray_list), ptrs, sizeof(ptrs),
                                   hipMemcpyHostToDevice, st);
         }
     };
@@ -454,7 +462,7 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
                 &k.mat_lds, &k.ltri_lds, &k.light_lds);
     const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
     const bool extra = !s->lights.tab.empty() || k.d.tex_compact != 0;
-    auto blocks = [&](bool count, size_t tables) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra); };
+    auto blocks = [&](bool count, size_t tables) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra, false); };
     const size_t tables = table_bytes(k.light_lds, k.mat_lds, k.ltri_lds);
     k.blocks_per_cu[0] = blocks(false, tables);
     const int wanted = drop_tables && tables != 0 ? blocks(false, 0) : k.blocks_per_cu[0];
@@ -472,6 +480,19 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
                          k.blocks_per_cu[0], k.stack_depth, k.mat_lds, k.ltri_lds, k.light_lds);
     }
     return wanted;
+}
+
+// Resident blocks per CU of the ray-batch kernel of a scene (the production kernels' are queried at upload; this one by the
+// first prt_ray_color call of its precision): same tables, stacks and record stride as the production kernel.
+template <typename R>
+static int rays_blocks_per_cu(const PrtScene* s, KernelConfig<R>& k) {
+    if (!k.blocks_per_cu_rays) {
+        constexpr bool f64 = std::is_same<R, double>::value;
+        const size_t tables = (f64 ? prt::render_table_bytes : prt32::render_table_bytes)(k.light_lds, k.mat_lds, k.ltri_lds);
+        const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
+        k.blocks_per_cu_rays = (f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu)(false, s->feat, tables, k.stack_depth, pad, true, true);
+    }
+    return k.blocks_per_cu_rays;
 }
 
 // The PRT_VARIANT_* byte of the production K3 instantiation a render in precision R launches: the choice launch_render makes,
@@ -1582,6 +1603,8 @@ int prt_texture_value(PrtScene* s, int32_t texture, size_t n, const double* uv, 
 // into an accumulator's running sums; the chunks of the launch are sized for `spp` samples either way.
 // prt_accum_render_adaptive sets d_list: K3 renders the list_n listed pixels (j*W+i, device memory) in chunks of
 // exactly `batch` samples (spp / batch <= PRT_MAX_CHUNKS of them), and k_accumulate_list adds sums, moments and counts.
+// prt_ray_color_device sets `rays`: no camera and no tiles — item oi of a chunk is ray d_rays[oi] of the caller's batch, keyed
+// d_keys[oi] (or oi), samples [first, first + spp) scaled by 1/spp, and k_finalize_rays writes one triple per ray.
 struct RenderPass {
     int spp;
     int32_t first = 0;
@@ -1591,10 +1614,63 @@ struct RenderPass {
     int batch = 0;
     double* d_moment = nullptr;
     uint32_t* d_count = nullptr;
+    bool rays = false;
+    const void* d_rays = nullptr;
+    const void* d_keys = nullptr;
+    uint64_t n_rays = 0;
 };
 
 static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const PrtRenderParams* p, const RenderPass& pass,
                        void* d_rgb_f64, void* d_rgb_f32, int count_work, hipStream_t st);
+
+int prt_ray_color_device(PrtScene* s, const void* d_rays, const void* d_keys, size_t n, const PrtRenderParams* p, int32_t sample_begin,
+                         void* d_rgb_f64, void* d_rgb_f32, void* stream) {
+    const char* who = "prt_ray_color_device";
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    const std::string w(who);
+    if (!p) return fail(PRT_E_INVALID, w + ": null argument");
+    if (n && !d_rays) return fail(PRT_E_INVALID, w + ": null ray buffer");
+    if (!d_rgb_f64 && !d_rgb_f32) return fail(PRT_E_INVALID, w + ": both outputs are null");
+    if (p->spp < 1) return fail(PRT_E_INVALID, w + ": spp must be >= 1");
+    if (sample_begin < 0 || (int64_t)sample_begin + p->spp > (int64_t)INT32_MAX) return fail(PRT_E_INVALID, w + ": bad sample range");
+    if (p->pixel_jitter || p->reserved) return fail(PRT_E_INVALID, w + ": pixel_jitter and reserved must be 0 (a ray has no pixel to jitter)");
+    if (n >= 0xffffffffULL) return fail(PRT_E_LIMIT, w + ": more than 2^32 work items (rays x sample chunks) in one launch");
+    RenderPass pass;
+    pass.spp = p->spp;
+    pass.first = sample_begin;
+    pass.rays = true;
+    pass.d_rays = d_rays;
+    pass.d_keys = d_keys;
+    pass.n_rays = n;
+    return render_impl(s, who, nullptr, p, pass, d_rgb_f64, d_rgb_f32, 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int prt_ray_color(PrtScene* s, const PrtRay* rays, const uint32_t* keys, size_t n, const PrtRenderParams* p, int32_t sample_begin,
+                  double* rgb_f64, float* rgb_f32) {
+    const char* who = "prt_ray_color";
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    if (n && !rays) return fail(PRT_E_INVALID, "prt_ray_color: null ray buffer");
+    if (n >= 0xffffffffULL) return fail(PRT_E_LIMIT, "prt_ray_color: more than 2^32 work items (rays x sample chunks) in one launch");
+    for (size_t i = 0; i < n; ++i) {
+        const PrtRay& r = rays[i];
+        bool ok = r.d[0] != 0.0 || r.d[1] != 0.0 || r.d[2] != 0.0;
+        for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(r.o[a]) && std::isfinite(r.d[a]);
+        if (!ok) return fail(PRT_E_INVALID, "prt_ray_color: ray " + std::to_string(i) + " has a non-finite origin or direction, or a zero direction");
+    }
+    Staging b;
+    void* dr = b.in(rays, n * sizeof(PrtRay));
+    void* dk = b.in(keys, n * sizeof(uint32_t));
+    void* d64 = rgb_f64 ? b.out(n * 3 * sizeof(double)) : nullptr;
+    void* d32 = rgb_f32 ? b.out(n * 3 * sizeof(float)) : nullptr;
+    if ((rc = b.status(who)) || (rc = prt_ray_color_device(s, dr, dk, n, p, sample_begin, d64, d32, nullptr)))
+        return rc;
+    b.sync();
+    if (rgb_f64) b.down(rgb_f64, d64, n * 3 * sizeof(double));
+    if (rgb_f32) b.down(rgb_f32, d32, n * 3 * sizeof(float));
+    return b.status(who);
+}
 
 int prt_render_device(PrtScene* s, const PrtCamera* cam, const PrtRenderParams* p, void* d_rgb_f64, void* d_rgb_f32,
                       int count_work, void* stream) {
@@ -1615,10 +1691,11 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     if (p->precision != PRT_PRECISION_F64 && p->precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
     const bool f32 = p->precision == PRT_PRECISION_F32;
     if (f32 && (rc = ensure_f32(s))) return rc;
-    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) return fail(PRT_E_INVALID, w + ": bad rank/nranks");
+    if (!pass.rays && (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks)) return fail(PRT_E_INVALID, w + ": bad rank/nranks");
 
     DCamera C;
-    prt::setup_camera(*cam, C);
+    if (pass.rays) std::memset(&C, 0, sizeof(C)); // (the ray-batch kernels have no camera)
+    else prt::setup_camera(*cam, C);
     DRenderParams P = base_params(s, p);
     P.spp = pass.d_sum ? 1 : pass.spp;
     P.cached_min = 24; // measured: veach-mis -1 %, the others flat
@@ -1629,14 +1706,23 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     if (const char* e = dev_env("PRT_TUNE_LEAF_BATCH")) P.leaf_batch = std::min(64, std::max(1, std::atoi(e))); // (a batch is 1 to 64 lanes of a wave)
     if (const char* e = dev_env("PRT_TUNE_INNER_MIN")) P.inner_min = std::min(64, std::max(0, std::atoi(e))); // (< 0 would never test the leaves of a wave whose lanes are all parked)
     if (const char* e = dev_env("PRT_TUNE_SCRAMBLE")) P.scramble = std::atoi(e) ? 1 : 0; // experiment: incoherent pixel order (PRT_ITEMS_FROM_LIST is set by adaptive rounds below and by prt_render_samples)
-    const TileLayout L(*cam, *p);
-    L.set(P);
+    uint64_t owned_pixels = pass.n_rays;
+    if (pass.rays) { // one "tile" that is never mapped to pixels: the items are the rays
+        P.scramble = 0;
+        P.tile = 8; P.tiles_x = P.tiles_y = P.n_tiles = 1; P.rank = 0; P.nranks = 1; P.owned_tiles = 1;
+        P.items_per_chunk = pass.n_rays;
+    } else {
+        const TileLayout L(*cam, *p);
+        L.set(P);
+        owned_pixels = L.owned_pixels();
+    }
     if (pass.d_list) { // an adaptive round: the listed pixels (all owned by this rank) instead of the owned tiles
         P.scramble = PRT_ITEMS_FROM_LIST;
         P.items_per_chunk = pass.list_n;
     }
     const bool count = count_work != 0;
-    const int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : 0];
+    int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : 0];
+    if (pass.rays) bpc = f32 ? rays_blocks_per_cu(s, s->k32) : rays_blocks_per_cu(s, s->k64);
     const uint64_t lanes = (uint64_t)s->n_cu * bpc * PRT_BLOCK;
     // Work item = (pixel, chunk of samples), dealt chunk-major from PRT_ITEM_QUEUES counters (prt_types.h).
     //  * explicit sample_chunks: that many equal chunks;
@@ -1701,12 +1787,12 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     PRT_HIP(we);
     PRT_HIP(q.partial.reserve(need * sizeof(double), st));
     double* d_partial = q.partial.get<double>();
-    const size_t npx = (size_t)C.width * C.height * 3;
+    const size_t npx = pass.rays ? (size_t)pass.n_rays * 3 : (size_t)C.width * C.height * 3;
     DevBuf<> dump_buf;
     unsigned long long dump_cap = 0;
     std::string dump_path;
-    if (d_rgb_f64) PRT_HIP(hipMemsetAsync(d_rgb_f64, 0, npx * sizeof(double), st));
-    if (d_rgb_f32) PRT_HIP(hipMemsetAsync(d_rgb_f32, 0, npx * sizeof(float), st));
+    if (d_rgb_f64 && npx) PRT_HIP(hipMemsetAsync(d_rgb_f64, 0, npx * sizeof(double), st));
+    if (d_rgb_f32 && npx) PRT_HIP(hipMemsetAsync(d_rgb_f32, 0, npx * sizeof(float), st));
     PRT_HIP(q.start(st));
     // maxDepth < 0: RayColor returns 0 before it traces anything (Camera.cpp:121) — the cleared framebuffer is the frame
     if (P.max_depth < 0) P.n_items = 0;
@@ -1714,6 +1800,7 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
         const uint64_t want = (P.n_items + PRT_BLOCK - 1) / PRT_BLOCK;
         const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s->n_cu * bpc));
         PRT_HIP(q.set_pointers(st, pass.d_list, nullptr));
+        if (pass.rays) PRT_HIP(q.set_rays(st, pass.d_rays, pass.d_keys));
         if (const char* e = dev_env("PRT_TUNE_DUMP_RAYS")) { // "<max rays>,<file>" (counting launches only)
             const std::string v(e);
             const size_t comma = v.find(',');
@@ -1726,8 +1813,8 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
             }
         }
         // fp32: the same camera and parameters rounded to float (K5 below works from the fp64 originals: it only maps pixels)
-        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st);
-        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st);
+        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays);
+        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays);
         PRT_HIP(hipGetLastError());
     }
     PRT_HIP(q.stop(st));
@@ -1752,11 +1839,12 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
                                     pass.d_count, st);
         PRT_HIP(hipGetLastError());
     } else if (P.n_items) {
-        if (pass.d_sum) prt::launch_accumulate(C, P, d_partial, pass.d_sum, st);
+        if (pass.rays) prt::launch_finalize_rays(P, d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
+        else if (pass.d_sum) prt::launch_accumulate(C, P, d_partial, pass.d_sum, st);
         else prt::launch_finalize(C, P, d_partial, static_cast<double*>(d_rgb_f64), static_cast<float*>(d_rgb_f32), st);
         PRT_HIP(hipGetLastError());
     }
-    const uint64_t samples = !P.n_items ? 0 : pass.d_list ? (uint64_t)pass.list_n * (uint64_t)spp : L.owned_pixels() * (uint64_t)spp;
+    const uint64_t samples = !P.n_items ? 0 : pass.d_list ? (uint64_t)pass.list_n * (uint64_t)spp : owned_pixels * (uint64_t)spp;
     PRT_HIP(q.finish(st, count, samples));
     return PRT_OK;
 }

@@ -4,6 +4,7 @@
 //      k_trace_surface   closest hit with the whole HitRecord and the material's response (PrtSurface)
 //   K3 k_render          persistent-wavefront path tracer          (Camera::Render/RayColor, Camera.cpp:21-204)
 //   K5 k_finalize        ordered sum of per-chunk partial sums -> f64 / f32 framebuffer
+//      k_finalize_rays   the same sum per ray of a batch           (prt_ray_color)
 //      k_sample_lights   lights.Sample test hook                   (BVH.cpp:62-67,86-100)
 //      k_tonemap         NaN scrub + sRGB + clamp -> u8            (Camera.cpp:206-221,279-301)
 //
@@ -60,7 +61,7 @@
 #define PRT_F32_WAVES 3 // fp32 fast mode: resident waves per SIMD of every K3 permutation
 #endif
 constexpr int render_waves(int feat_with_extra) {
-    const int feat = feat_with_extra & PRT_FEAT_ALL; // (PRT_FEAT_EXTRA is not a material feature)
+    const int feat = feat_with_extra & PRT_FEAT_ALL; // (PRT_FEAT_EXTRA and PRT_FEAT_RAYS are not material features)
     if (PRT_F32_TU) return PRT_F32_WAVES;
     return feat == 0 ? PRT_RENDER_WAVES_LEAN
          : feat == PRT_FEAT_TEX ? PRT_RENDER_WAVES_TEX
@@ -420,6 +421,14 @@ PRT_DEV real unpark_real(const uint32_t* base, int word) {
 #define PARK_AB_AT(feat) (PARK_DIR_GLOBAL(feat) ? PRT_RW + 1 : 4 * PRT_RW + 1)
 #define PARK_WORDS(feat) (((feat) & PRT_FEAT_TEX) ? 3 * PRT_RW + 1 : 4 * PRT_RW + 1)
 
+// prt_ray_color (PRT_FEAT_RAYS kernels): ray i of the caller's batch, fp64 records rounded to the kernel's real on load.  tmin and
+// tmax are not read: a primary ray is traced over Interval(0.0001, inf) like a camera ray (Camera.cpp:125).
+PRT_DEV void load_ray(const void* ray_list, uint32_t i, d3& o, d3& d) {
+    const PrtRay* r = static_cast<const PrtRay*>(ray_list) + i;
+    o = mk3((real)r->o[0], (real)r->o[1], (real)r->o[2]);
+    d = mk3((real)r->d[0], (real)r->d[1], (real)r->d[2]);
+}
+
 // K3's arguments are ONE struct, so that the kernel can also reach them through the kernarg segment pointer: what the
 // hot loop needs (scene tables, thresholds, roulette, seed) is used as plain arguments — the compiler loads those into
 // scalar registers once — while everything only a work-item fetch or a miss needs (the camera, tile geometry, the chunk
@@ -447,6 +456,12 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     const DScene& S = A.S;
     const DRenderParams& P = A.P; // hot fields only: see RenderArgs
     DCounters* const ctr = A.ctr;
+    // RAYS (prt_ray_color): the work item's primary ray is ray_list[oi] of the caller's batch instead of a camera ray, and the
+    // key of its random streams is key_list[oi] (or oi) instead of the pixel index.  The ray is traced once per work item
+    // and its hit parked like a camera ray's; a sample re-reads the ray itself (64 bytes, L2) instead of unparking a
+    // direction and taking the block's one camera centre, so the park layout and the LDS budget are the frame kernels'.
+    // `px` carries oi across the item; no pixel, no jitter.
+    constexpr bool RAYS = (FEAT & PRT_FEAT_RAYS) != 0;
     __shared__ uint32_t s_qoff[PRT_BLOCK / 64];
     __shared__ unsigned long long s_rays[PRT_BLOCK / 64];
     __shared__ real s_center[4]; // Camera::center, the origin of every camera ray
@@ -605,7 +620,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
 #define NEW_SAMPLE(parked) do {                                                                                                                                           \
         /* per-sample stream keyed (seed, j*W+i, s) */                                                                                                                    \
         rng.seed_keyed(P.seed_key, (uint64_t)pixel, (uint64_t)s);                                                                                                         \
-        if (P.jitter) {                                                                                                                                                   \
+        if (!RAYS && P.jitter) {                                                                                                                                          \
             /* the disabled SampleSquare() offset of Camera.cpp:110-111, drawn per sample: y first (g++ argument order); */                                               \
             /* a camera ray of its own, traced like any other */                                                                                                          \
             const ColdRenderArgs q = cold_args();                                                                                                                         \
@@ -622,13 +637,16 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
             /* Camera::GetRay gives every sample of the pixel the same ray (Camera.cpp:53-57, no jitter): the sample starts */                                            \
             /* from the parked hit of that ray.  Nothing to trace.  Two-pass permutations: the lane waits for the next pass, which */                                     \
             /* consumes the hit (the LDS reads below have the traversal rounds in between to arrive); TURN: this pass does. */                                            \
-            tr.o = mk3(s_center[0], s_center[1], s_center[2]);                                                                                                            \
-            if (PARK_DIR_GLOBAL(FEAT)) { /* Camera::GetRay again (same expressions as at the fetch: the same bits) */                                                     \
+            if (RAYS) { /* the lane's own ray, read again (the parked words hold its hit only) */                                                                         \
+                load_ray(ctr->ray_list, (uint32_t)px, tr.o, tr.d);                                                                                                        \
+            } else if (PARK_DIR_GLOBAL(FEAT)) { /* Camera::GetRay again (same expressions as at the fetch: the same bits) */                                              \
+                tr.o = mk3(s_center[0], s_center[1], s_center[2]);                                                                                                        \
                 const ColdRenderArgs q = cold_args();                                                                                                                     \
                 const d3 ps = mk3(q->C.pixel00[0], q->C.pixel00[1], q->C.pixel00[2]) + (real)px * mk3(q->C.du[0], q->C.du[1], q->C.du[2]) +                               \
                               (real)py * mk3(q->C.dv[0], q->C.dv[1], q->C.dv[2]);                                                                                         \
                 tr.d = ps - tr.o;                                                                                                                                         \
             } else {                                                                                                                                                      \
+                tr.o = mk3(s_center[0], s_center[1], s_center[2]);                                                                                                        \
                 tr.d = mk3(unpark_real<NPARK>(park, PARK_DIR), unpark_real<NPARK>(park, PARK_DIR + PRT_RW), unpark_real<NPARK>(park, PARK_DIR + 2 * PRT_RW));             \
             }                                                                                                                                                             \
             tr.hit.t = unpark_real<NPARK>(park, PARK_T);                                                                                                                  \
@@ -735,7 +753,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 if (ended) END_OF_SAMPLE(ST_NEW_SAMPLE);
                 if (state == ST_NEW_SAMPLE) {
                     NEW_SAMPLE(ST_CLOSEST);
-                    hit_ready = !P.jitter; // (a jittered sample's camera ray is traced first: the set-up at the bottom starts it)
+                    hit_ready = RAYS || !P.jitter; // (a jittered sample's camera ray is traced first: the set-up at the bottom starts it)
                 }
                 PROF_MARK(3); // cheap ends + sample turnover: booked with the end of sample / fetch section below
             } else {
@@ -983,7 +1001,10 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     const uint32_t oi = item - chunk * ipc;
                     const int W = q->C.width;
                     bool valid;
-                    if (P.scramble == PRT_ITEMS_FROM_LIST) { // prt_render_samples: the pixels of a list
+                    if (RAYS) { // prt_ray_color: item oi of a chunk is ray oi of the batch
+                        px = (int)oi;
+                        valid = true;
+                    } else if (P.scramble == PRT_ITEMS_FROM_LIST) { // prt_render_samples: the pixels of a list
                         const int32_t pix = ctr->pixel_list[oi];
                         py = pix / W;
                         px = pix - py * W;
@@ -995,11 +1016,19 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     if (valid) {
                         s = q->P.chunk_begin[chunk];
                         s_end = q->P.chunk_begin[chunk + 1];
-                        pixel = (uint32_t)(py * W + px);
+                        if (RAYS) {
+                            const uint32_t* keys = ctr->key_list;
+                            pixel = keys ? keys[oi] : oi;
+                        } else {
+                            pixel = (uint32_t)(py * W + px);
+                        }
                         PST_ST(S_ACC, mk3(0, 0, 0));
                         if (s >= s_end) {
                             double* o = q->partial + (size_t)item * 3;
                             o[0] = o[1] = o[2] = 0.0;
+                        } else if (RAYS) {
+                            load_ray(ctr->ray_list, oi, tr.o, tr.d);
+                            state = ST_PRIMARY;
                         } else if (P.jitter) {
                             state = TURN ? ST_CACHED : ST_NEW_SAMPLE; // a camera ray of its own per sample (below; TURN: the next pass's turnover)
                         } else {
@@ -1157,6 +1186,24 @@ __global__ void k_finalize(DCamera C, DRenderParams P, const double* __restrict_
         out32[m] = (float)r;
         out32[m + 1] = (float)g;
         out32[m + 2] = (float)b;
+    }
+}
+
+// prt_ray_color: out[i] = the same sum for ray i of a batch (item c * n + i of chunk c); no pixel mapping, no other ranks.
+__global__ void k_finalize_rays(DRenderParams P, const double* __restrict__ partial, double* __restrict__ out64, float* __restrict__ out32) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.items_per_chunk) return;
+    double r, g, b;
+    chunk_sum(P, partial, i, r, g, b);
+    if (out64) {
+        out64[i * 3] = r;
+        out64[i * 3 + 1] = g;
+        out64[i * 3 + 2] = b;
+    }
+    if (out32) {
+        out32[i * 3] = (float)r;
+        out32[i * 3 + 1] = (float)g;
+        out32[i * 3 + 2] = (float)b;
     }
 }
 
@@ -1486,6 +1533,7 @@ namespace PRT_NS {
 // The compiled permutations: lean, textures only, Phong only, CookTorrance only, everything.  A scene gets the smallest one
 // that covers its materials.
 int render_permutation(int feat) {
+    feat &= ~PRT_FEAT_RAYS; // (not a material feature: the ray source of prt_ray_color)
     if (feat == 0 || feat == PRT_FEAT_TEX || feat == PRT_FEAT_PHONG || feat == PRT_FEAT_CT) return feat;
     return PRT_FEAT_ALL;
 }
@@ -1503,26 +1551,29 @@ size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds) {
 }
 
 typedef void (*RenderKernel)(RenderArgs);
-// COUNT instantiations exist only with PRT_FEAT_EXTRA (statistics runs: speed is not what they are for)
+// COUNT instantiations exist only with PRT_FEAT_EXTRA (statistics runs: speed is not what they are for); so do the
+// PRT_FEAT_RAYS ones (prt_ray_color: one kernel per permutation and layout, no counting form)
 template <int FEAT, bool PAD>
-static RenderKernel render_kernel_feat(bool count, bool llds, bool extra) {
+static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool rays) {
     constexpr int X = FEAT | PRT_FEAT_EXTRA;
+    if (rays) return llds ? k_render<false, X | PRT_FEAT_RAYS, true, PAD> : k_render<false, X | PRT_FEAT_RAYS, false, PAD>;
     if (count) return llds ? k_render<true, X, true, PAD> : k_render<true, X, false, PAD>;
     if (extra) return llds ? k_render<false, X, true, PAD> : k_render<false, X, false, PAD>;
     return llds ? k_render<false, FEAT, true, PAD> : k_render<false, FEAT, false, PAD>;
 }
 template <bool PAD>
 static RenderKernel render_kernel_pad(bool count, int feat, bool llds, bool extra) {
+    const bool rays = (feat & PRT_FEAT_RAYS) != 0;
     switch (render_permutation(feat)) {
-    case 0: return render_kernel_feat<0, PAD>(count, llds, extra);
-    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra);
-    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra);
-    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra);
-    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra);
+    case 0: return render_kernel_feat<0, PAD>(count, llds, extra, rays);
+    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra, rays);
+    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra, rays);
+    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra, rays);
+    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra, rays);
     }
 }
 // `pad`: the scene's intersection records sit 128 bytes apart (DScene::tri_stride); `extra`: the scene has light tables or
-// plain texel arrays (PRT_FEAT_EXTRA kernels)
+// plain texel arrays (PRT_FEAT_EXTRA kernels); `feat` with PRT_FEAT_RAYS: the kernel of prt_ray_color
 static RenderKernel render_kernel(bool count, int feat, bool llds, bool pad, bool extra) {
     return pad ? render_kernel_pad<true>(count, feat, llds, extra) : render_kernel_pad<false>(count, feat, llds, extra);
 }
@@ -1531,8 +1582,9 @@ static size_t stack_bytes(int stack_depth) { return PRT_DYN_STACK ? (size_t)PRT_
 
 // Resident blocks per CU of the instantiation a launch will use (`pad`: the scene's records sit at the padded stride —
 // a different function with its own register count).
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra) {
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays) {
     int nb = 0;
+    if (rays) feat |= PRT_FEAT_RAYS;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel(count, feat, table_bytes != 0, pad, extra), PRT_BLOCK,
                                                                 table_bytes + stack_bytes(stack_depth));
     if (e != hipSuccess || nb < 1) nb = 1;
@@ -1574,8 +1626,9 @@ void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, 
     }
 }
 
+// `rays`: the ray-batch kernels (prt_ray_color; DCounters::ray_list / key_list are set, C is not read)
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,
-                   bool count, int feat, unsigned grid, hipStream_t st) {
+                   bool count, int feat, unsigned grid, hipStream_t st, bool rays) {
     static_assert(sizeof(DMaterial) % 16 == 0, "materials are staged in 16-byte pieces");
     const size_t tables = render_table_bytes(P.light_lds, P.mat_lds, P.ltri_lds);
     const size_t dyn_lds = tables + stack_bytes(P.stack_depth);
@@ -1586,6 +1639,7 @@ void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, do
     A.P = P;
     A.partial = d_partial;
     A.ctr = d_ctr;
+    if (rays) feat |= PRT_FEAT_RAYS;
     hipLaunchKernelGGL(render_kernel(count, feat, tables != 0, pad, S.light_tab != nullptr || S.tex_compact != 0), dim3(grid), dim3(PRT_BLOCK), dyn_lds, st, A);
 }
 
@@ -1641,6 +1695,11 @@ void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_p
     unsigned grid = (unsigned)((P.items_per_chunk + 255) / 256);
     if (grid == 0) return;
     hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, C, P, d_partial, d64, d32);
+}
+void launch_finalize_rays(const DRenderParams& P, const double* d_partial, double* d64, float* d32, hipStream_t st) {
+    unsigned grid = (unsigned)((P.items_per_chunk + 255) / 256);
+    if (grid == 0) return;
+    hipLaunchKernelGGL(k_finalize_rays, dim3(grid), dim3(256), 0, st, P, d_partial, d64, d32);
 }
 void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st) {
     unsigned grid = (unsigned)((P.items_per_chunk + 255) / 256);

@@ -15,6 +15,7 @@
 // device.  A translation unit sees the un-suffixed names (DTri, DScene, ...) instantiated for PRT_REAL (default
 // double); prt_kernels_f32.hip compiles the same kernels with PRT_REAL = float.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef PRT_REAL
@@ -226,9 +227,15 @@ struct DCounters {
     // developer experiment (PRT_TUNE_DUMP_RAYS, counting instantiation): every traversal K3 starts is appended here as a PrtRay
     void* ray_dump;
     unsigned long long ray_dump_cap, ray_dump_n;
-    unsigned long long pad_[PRT_QUEUE_STRIDE - 15];
+    // prt_ray_color (k_render with PRT_FEAT_RAYS): work item oi traces ray_list[oi] (a PrtRay, 64 bytes) and keys its random
+    // streams with key_list[oi], or with oi itself when key_list is null
+    const void* ray_list;
+    const uint32_t* key_list;
+    unsigned long long pad_[PRT_QUEUE_STRIDE - 17];
     unsigned long long queue[PRT_ITEM_QUEUES * PRT_QUEUE_STRIDE]; // queue[q * PRT_QUEUE_STRIDE] = next 64-item-block-local index of queue q
 };
+
+static_assert(offsetof(DCounters, queue) == PRT_QUEUE_STRIDE * 8, "the item queues start one queue stride into DCounters");
 
 // Adaptive sampling (prt_accum_render_adaptive, include/prt.h): the activity rule of one round.  n = the accumulator's
 // global sample count; every count is a multiple of batch.

@@ -9,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -466,6 +467,36 @@ void Camera::Render(Hittable& world, Hittable& lights) {
             lastRays += cnt.rays_closest + cnt.rays_shadow;
             lastKernelMs = std::max(lastKernelMs, cnt.kernel_ms); // the devices run concurrently
         }
+}
+
+void Camera::RayColor(const std::vector<Ray>& rays, Hittable& world, Hittable& lights, int samples, std::vector<color>& out) {
+    if (devices.size() > 1) throw std::invalid_argument("Camera::RayColor: one device only (`devices` lists several)");
+    if (samples < 1) throw std::invalid_argument("Camera::RayColor: samples must be >= 1");
+    const std::vector<int> devs = devices.empty() ? std::vector<int>{device} : devices;
+    PrtCamera c;
+    PrtRenderParams p;
+    Hittable::DeviceCache& dc = PrepareScene(world, lights, devs, c, p);
+    p.spp = samples;
+    p.pixel_jitter = 0; // (a ray has no pixel)
+    std::vector<PrtRay> batch(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        PrtRay& r = batch[i];
+        r.o[0] = rays[i].origin.x; r.o[1] = rays[i].origin.y; r.o[2] = rays[i].origin.z;
+        r.d[0] = rays[i].direction.x; r.d[1] = rays[i].direction.y; r.d[2] = rays[i].direction.z;
+        r.tmin = 0.0001; // (not read: RayColor traces Interval(0.0001, inf), Camera.cpp:125)
+        r.tmax = std::numeric_limits<double>::infinity();
+    }
+    std::vector<double> rgb(rays.size() * 3);
+    const int rc = prt_ray_color(dc.scene, batch.data(), nullptr, batch.size(), &p, 0, rgb.data(), nullptr);
+    if (rc == PRT_E_INVALID) throw std::invalid_argument(std::string("Camera::RayColor: ") + prt_last_error());
+    check(rc, "prt_ray_color");
+    out.resize(rays.size());
+    for (size_t i = 0; i < out.size(); ++i) out[i] = color(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
+    PrtCounters cnt;
+    if (prt_get_counters(dc.scene, &cnt) == PRT_OK) {
+        lastRays = cnt.rays_closest + cnt.rays_shadow;
+        lastKernelMs = cnt.kernel_ms;
+    }
 }
 
 void Camera::RenderProgressive(Hittable& world, Hittable& lights, const std::vector<int>& sppLadder,
