@@ -7,6 +7,8 @@ Every source is compiled to its own object (in parallel, only when it or a heade
                      PRT_TEST_DUMP_BVH=<file> writes each scene's traversal tree (header, nodes, leaf order) when it is
                      built: host trees at create and on a host rebuild, device trees at upload, either after a refit
                      (tests/bvh_model.py reads it).
+build_probe() builds tests/probe/libprt_probe.so, the test-only wrappers of prt_device.h's primitives — a library of its
+own, linked into neither of the two above.
 """
 import concurrent.futures
 import hashlib
@@ -82,6 +84,25 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     _link(objs[:len(SOURCES)], LIB, verbose)
     _link([objs[-1]] + objs[1:len(SOURCES)], DEV_LIB, verbose)
     return LIB
+
+
+PROBE_DIR = os.path.join(os.path.dirname(HERE), "tests", "probe")
+PROBE_LIB = os.path.join(PROBE_DIR, "libprt_probe.so")
+PROBE_SOURCES = ["prt_probe.hip", "prt_probe_f32.hip"]
+
+
+def build_probe(force=False, verbose=False):
+    """tests/probe/libprt_probe.so: the TEST-ONLY element-wise wrappers of prt_device.h's primitives (fp64 + fp32 twin).
+    Same flags as the product, same freshness rule on the headers; linked on its own, never into the product libraries."""
+    lib = PROBE_LIB
+    deps = [os.path.join(PROBE_DIR, s) for s in PROBE_SOURCES] + [os.path.join(CSRC, h) for h in HEADERS[:3]] + [os.path.abspath(__file__)]
+    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(d) for d in deps):
+        return lib
+    cmd = [HIPCC, "-shared"] + CFLAGS + ["-o", lib] + [os.path.join(PROBE_DIR, s) for s in PROBE_SOURCES]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return lib
 
 
 HOST_LIB = os.path.join(HERE, "libpooraytracer_host.so")

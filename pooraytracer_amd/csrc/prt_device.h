@@ -56,7 +56,14 @@ PRT_DEV d3 cross(d3 x, d3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * 
 // (v_rsq_f64 / v_rcp_f64, ~2^-23 relative) plus one coupled Newton step and one residual correction — within an ulp
 // or two of the IEEE result (the parity tolerance is 1e-9) in 7-8 instructions instead of the 14-17 of the
 // correctly rounded, range-scaled library sequences.  Arguments are positive normal numbers wherever these are
-// used (squared lengths, pdfs, |direction components|); zero is handled, NaN propagates.
+// used (squared lengths, pdfs, |direction components|): for those — every binade, results down into the subnormals —
+// all four are within 2 ulp (measured <= 1.5; tests/test_gpu_device_math.py).  fast_sqrt(+-0) is +0 and NaN propagates.
+// NOT like IEEE outside that domain, because the Newton step multiplies the estimate by its argument (0 * inf, inf * 0):
+//   fast_rsqrt(0), fast_rcp(+-0), fast_div(a, 0)            NaN, not +-inf   (callers guard: tri_test's |denom| >= 1e-8,
+//                                                            mat_scatter's pdf > 0, normalize of a non-zero vector)
+//   fast_sqrt(inf), fast_rsqrt(inf), fast_rcp(+-inf)        NaN, not inf / 0 (no caller passes an infinity)
+//   fast_rcp / fast_div by a subnormal                      NaN, not a huge finite value or inf
+//   negative arguments: sqrt / rsqrt NaN as in IEEE, rcp / div the ordinary result; subnormal sqrt / rsqrt within 2 ulp.
 PRT_DEV double fast_rsqrt(double x) { // 1 / sqrt(x), x > 0
     const double y = __builtin_amdgcn_rsq(x);
     const double g = x * y, h = 0.5 * y;
@@ -85,7 +92,11 @@ PRT_DEV double fast_div(double a, double b) { // a / b, b != 0
     const double q = a * r;
     return fma(fma(-b, q, a), r, q);
 }
-// fp32 fast mode: the hardware instructions themselves (v_rsq_f32 / v_sqrt_f32 / v_rcp_f32, 1 ulp) — one instruction each
+// fp32 fast mode: the hardware instructions themselves (v_rsq_f32 / v_sqrt_f32 / v_rcp_f32) — one instruction each, within
+// 1 ulp of the correctly rounded result for EVERY normal float (checked exhaustively on the GPU,
+// tests/test_gpu_device_math.py; the slab test's pad below rests on it).  v_rcp_f32 flushes a subnormal RESULT to zero
+// (|b| > 2^126), so fast_div / ieee_div (two roundings: within 2 ulp) return 0 there; subnormal arguments give a correctly
+// signed finite or infinite value, never NaN.
 PRT_DEV float fast_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
 PRT_DEV float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 PRT_DEV float fast_rcp(float b) { return __builtin_amdgcn_rcpf(b); }
@@ -570,7 +581,10 @@ PRT_DEV void sincos_turns(real u, real& sn, real& cs) {
     cs = (q == 0) ? c : (q == 1) ? -s : (q == 2) ? -c : s;
 }
 // sin / cos of theta = 2 pi u: the library call the reference makes in fp64; in fp32 the hardware instructions, which
-// take their argument in turns (v_sin_f32 / v_cos_f32)
+// take their argument in turns (v_sin_f32 / v_cos_f32).  No accuracy of those two is documented that this code could
+// cite; what the fp32 mode NEEDS of them is an absolute error <= 16 * 2^-24 on u = k / 2^24 — a BUDGET, the size of the
+// 16-ulp perturbation the mode is validated against, not an accuracy claim.
+// tests/test_gpu_device_math.py checks it on all 2^24 points (measured 2.1 * 2^-24).
 PRT_DEV void sincos_any(double theta, double, double& sn, double& cs) { sincos(theta, &sn, &cs); }
 PRT_DEV void sincos_any(float, float u, float& sn, float& cs) {
     sn = __builtin_amdgcn_sinf(u);
@@ -640,8 +654,12 @@ PRT_DEV real clampd(real v, real lo, real hi) { return v < lo ? lo : (v > hi ? h
 PRT_DEV real sqr(real v) { return v * v; }
 // x^y for the Phong lobe (Material.h:205,223,247,260) as exp(y*log(x)): |y*log x| <= ~50 here, so the
 // result is within ~1e-14 relative of pow() — far inside the 1e-9 parity tolerance — at a third of the
-// instructions and registers of the fp64 library pow.  x = 0 -> 0, x < 0 -> NaN (every caller then
-// takes its 'pdf <= 0 / lobe <= 0' branch exactly as with pow's negative/NaN result).
+// instructions and registers of the fp64 library pow (measured: 9.4e-15 over |y log x| <= 50, 1.9e-15 below 10).
+// pow_pos(1, y) = 1 exactly; x = 0 -> 0 for every y > 0 (and for y = 0 in fp64; NaN in fp32, 0 * -inf); y log x < -1000
+// -> 0.  OUT OF DOMAIN the two precisions differ: for x < 0 or NaN the fp64 body returns 0 (its last line is
+// `x > 0 ? e : 0`), the fp32 one NaN (v_log_f32 of a negative number).  No caller can tell: mat_eval forms
+// ca = fmax(0, dot) and returns on `ca <= 0` before the call (a NaN dot becomes 0 there too), mat_scatter passes a
+// lattice draw u1 in [0, 1) and uses the result only under `u1 > 0`.  Pinned in tests/test_gpu_device_math.py.
 PRT_DEV float pow_pos(float x, float y) { // fp32 fast mode: v_exp_f32(y * v_log_f32(x)) (base 2); x = 0 -> exp2(-inf) = 0
     return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
 }
@@ -739,10 +757,19 @@ PRT_DEV d3 ct_sample_wm(const DMaterial& m, d3 w, d2 u) { // Material.h:412-435
     real sn, cs;
     sincos_any(theta, u.y, sn, cs);
     d2 p = {r * cs, r * sn};
-    real h = ieee_sqrt(1 - sqr(p.x));
+    // h = sqrt(1 - p.x^2) and pz = sqrt(1 - p.x^2 - p.y'^2) of the reference, without its cancellations: on the disk's rim
+    // (u.x = 1 - 2^-31 is drawn in every frame) 1 - p.x^2 squares sqrt(u.x) back and keeps 2^-22 relative, which the
+    // stretch back to the ellipsoid divides by alpha.  With om = 1 - u.x (exact on the lattice): 1 - p.x^2 = om + u.x sin^2,
+    // (h - p.y)(h + p.y) = om, and pz^2 = h^2 - p.y'^2 = (h - p.y')(h + p.y') = lx (h - p.y) (2 (1 - lx) h + lx (h + p.y)) —
+    // sums of non-negative terms only.  Same values as the reference's expressions up to their rounding.
+    const real om = 1 - u.x;
+    real h = ieee_sqrt(om + u.x * sqr(sn));
     real lx = (1 + wh.z) / 2;
+    real hp = h + p.y, hm = h - p.y;
+    if (p.y >= 0) hm = fast_div(om, hp);
+    else hp = fast_div(om, hm);
+    real pz = ieee_sqrt(fmax(RL(0.), lx * hm * (2 * (1 - lx) * h + lx * hp)));
     p.y = (1 - lx) * h + lx * p.y; // Lerp
-    real pz = ieee_sqrt(fmax(RL(0.), RL(1.) - (sqr(p.x) + sqr(p.y))));
     d3 nh = p.x * T1 + p.y * T2 + pz * wh;
     return normalize(mk3(m.alpha_x * nh.x, m.alpha_y * nh.y, fmax(RL(1e-6), nh.z)));
 }

@@ -8,6 +8,10 @@ the order of blocks inside a pass changed — draws, expressions and the order o
     by commit e1bdde2, "Shade a K3 path vertex in one pass and chain its rays in the wave loop"; the "_items" entries are the
     spp 7 frames dealt as one work item per pixel, sample_chunks=1 — a frame this small is otherwise dealt sample by sample
     and no sample would turn over inside an item).
+    The CookTorrance entries were rendered again when ct_sample_wm stopped forming sqrt(1 - p.x^2) and pz by cancellation
+    (tests/test_gpu_device_math.py holds its error below 1e-11): same ray counters, the same draws and paths, and of the
+    3,840 values per frame 227 .. 435 moved by at most 2.3e-14 relative in fp64, 391 .. 1,330 by at most 2.6e-5 in fp32
+    (rounding of the new expressions); the lean entries are still e1bdde2's, bit for bit.
     The fp32 lean kernels keep the old order of the pass (with the new one the compiler contracts their Scatter arithmetic
     differently and 133 / 228 / 539 of the 3,840 values left the fixture by up to 5.4e-7 relative), so
     for them this is a regression check of an unchanged kernel;

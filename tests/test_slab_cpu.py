@@ -10,6 +10,9 @@ import numpy as np
 
 f32 = np.float32
 PAD = f32(9.5367432e-7)  # 2^-20
+# The pad as the derivation writes it, |id| * (|r| + E) * 2^-20, and as the device computes it, fma(E, |id|, |c|) * 2^-20
+# with c = r * id already rounded.  Every property below holds for both.
+PAD_VARIANTS = ("derivation", "device")
 
 
 def fma32(a, b, c):
@@ -17,24 +20,29 @@ def fma32(a, b, c):
     return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f32)
 
 
-def slab_axis(o, d, E, g0, gs):
+def slab_axis(o, d, E, g0, gs, variant="derivation"):
     """prt_device.h slab_axis (fp64 origin): returns idq, c_lo (entry), c_hi (exit), rot."""
     df = d.astype(f32)
     with np.errstate(divide="ignore"):
-        idv = (f32(1.0) / df).astype(f32)  # v_rcp_f32 is within 1 ulp of this
+        # the correctly rounded reciprocal; the device's v_rcp_f32 is within 1 ulp of it for every normal float:
+        # tests/test_gpu_device_math.py::test_f32_hardware_ops_exhaustive proves that on the GPU
+        idv = (f32(1.0) / df).astype(f32)
     idv = np.where(np.abs(idv) <= f32(1e28), idv, np.copysign(f32(1e28), df)).astype(f32)
     r = (np.float64(g0) - o).astype(f32)
     c = (r * idv).astype(f32)
-    pad = ((np.abs(idv) * (np.abs(r) + f32(E)).astype(f32)).astype(f32) * PAD).astype(f32)
+    if variant == "device":
+        pad = (fma32(np.full_like(idv, E), np.abs(idv), np.abs(c)) * PAD).astype(f32)
+    else:
+        pad = ((np.abs(idv) * (np.abs(r) + f32(E)).astype(f32)).astype(f32) * PAD).astype(f32)
     return (f32(gs) * idv).astype(f32), (c - pad).astype(f32), (c + pad).astype(f32), idv < 0
 
 
-def box_test(o, d, lo_q, hi_q, E, g0, gs, tmin=f32(1e-4), tmax=f32(np.inf)):
+def box_test(o, d, lo_q, hi_q, E, g0, gs, tmin=f32(1e-4), tmax=f32(np.inf), variant="derivation"):
     """Trav::box4 with PRT_BOX_ROTATE: entry / exit per axis from the rotated range, n <= f accepts."""
     n = np.full(o.shape[0], tmin, dtype=f32)
     f = np.full(o.shape[0], tmax, dtype=f32)
     for a in range(3):
-        idq, c_lo, c_hi, neg = slab_axis(o[:, a], d[:, a], E, g0[a], gs[a])
+        idq, c_lo, c_hi, neg = slab_axis(o[:, a], d[:, a], E, g0[a], gs[a], variant)
         ent = np.where(neg, hi_q[:, a], lo_q[:, a]).astype(f32)
         ext = np.where(neg, lo_q[:, a], hi_q[:, a]).astype(f32)
         n = np.maximum(n, fma32(ent, idq, c_lo))
@@ -89,11 +97,12 @@ def test_fp32_slab_test_is_conservative_near_far_and_translated():
                 lo = g0.astype(np.float64) + lo_q * gs.astype(np.float64)
                 hi = g0.astype(np.float64) + hi_q * gs.astype(np.float64)
                 ex = exact_test(o, d, lo, hi)
-                got = box_test(o, d, lo_q, hi_q, E, g0, gs)
-                assert not (ex & ~got).any(), (center, extent, dist, int((ex & ~got).sum()))
-                if dist <= 10 * extent and np.abs(center).max() <= 1e6 * extent:
-                    # ... and still culls: relative to the grid origin a far-away scene is tested like one at the origin
-                    assert got.mean() < ex.mean() + 0.05, (center, extent, dist, got.mean(), ex.mean())
+                for variant in PAD_VARIANTS:
+                    got = box_test(o, d, lo_q, hi_q, E, g0, gs, variant=variant)
+                    assert not (ex & ~got).any(), (variant, center, extent, dist, int((ex & ~got).sum()))
+                    if dist <= 10 * extent and np.abs(center).max() <= 1e6 * extent:
+                        # ... and still culls: relative to the grid origin a far-away scene is tested like one at the origin
+                        assert got.mean() < ex.mean() + 0.05, (variant, center, extent, dist, got.mean(), ex.mean())
 
 
 def test_unused_slot_range_is_rejected_near_the_scene_and_not_beyond():
@@ -106,10 +115,12 @@ def test_unused_slot_range_is_rejected_near_the_scene_and_not_beyond():
     hi_q = np.zeros((n, 3), dtype=np.int64)
     for dist in (0.0, 100.0, 2.0 ** 17 * extent):
         o, d = rays_towards(rng, n, center, extent, dist)
-        assert not box_test(o, d, lo_q, hi_q, E, g0, gs).any(), dist
+        for variant in PAD_VARIANTS:
+            assert not box_test(o, d, lo_q, hi_q, E, g0, gs, variant=variant).any(), (variant, dist)
     # from 2^21 extents away the pad exceeds the whole grid on every axis: the range alone no longer rejects the slot
     o, d = rays_towards(rng, n, center, extent, 2.0 ** 21 * extent)
-    assert box_test(o, d, lo_q, hi_q, E, g0, gs).any()
+    for variant in PAD_VARIANTS:
+        assert box_test(o, d, lo_q, hi_q, E, g0, gs, variant=variant).any(), variant
     # the formula this replaces padded by the WORLD coordinate: a unit scene at 1e6 accepted the empty slot for rays inside it
     o, d = rays_towards(rng, n, center, extent, 0.0)
     B = f32(np.abs(center).max() + extent)
