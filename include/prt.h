@@ -23,6 +23,8 @@
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
  *   prt_scene_refit       new vertex positions for a resident scene: records and BVH boxes follow on the GPU, the tree's
  *                         topology stays (the reference rebuilds its BVHNode graph instead, Source/BVH.cpp:7-48)
+ *   prt_scene_rebuild     new vertex positions and a NEW tree of them from the device builder; textures, materials and
+ *                         light tables stay resident
  *   prt_get_counters      rays / node fetches / triangle tests / kernel ms of the last call
  *   prt_accum_*           progressive, resumable rendering: the same frame built up over several calls
  *                         (replaces a ladder of separate Camera::Render calls at rising samplesPerPixel);
@@ -245,7 +247,11 @@ int prt_scene_upload(PrtScene* scene, int device);
  * path: 4 ms per 126k triangles, 17 ms per 8M).  Limitation: there is no topology-preserving refit (the
  * reference has none either — it rebuilds, Source/BVH.cpp:7-48); a caller that moves geometry every frame pays
  * the rebuild plus a re-upload of the triangle records each time.  (prt_scene_refit below is the in-place alternative for
- * an uploaded scene whose emitters stay put.)  Replaces every host position: clears the stale mark prt_scene_refit_device sets. */
+ * an uploaded scene whose emitters stay put.)  Replaces every host position: clears the stale mark prt_scene_refit_device sets.
+ * This call takes HOST positions and goes through prt_scene_upload, which frees and re-sends every table (materials,
+ * light tables, textures) and drops the fp32 tables.  A caller whose positions are on the device and whose emitters stay
+ * put refits every frame and, when PrtRefitInfo.sah_ratio says so, rebuilds on the device with prt_scene_rebuild_device
+ * (below): a new tree while everything else stays resident. */
 int prt_scene_update_vertices(PrtScene* scene, const double* vertices, const double* normals);
 
 /*
@@ -285,7 +291,8 @@ int prt_scene_update_vertices(PrtScene* scene, const double* vertices, const dou
  * marks the host geometry stale: while it is, prt_scene_upload is refused with PRT_E_INVALID; prt_scene_update_vertices
  * and prt_scene_refit replace every host position and clear the mark.
  * Quality.  A refit keeps the tree's topology, so the tree decays as the geometry deforms; PrtRefitInfo.sah_ratio is the
- * caller's signal that prt_scene_update_vertices (a rebuild) is due.  The library never rebuilds on its own.
+ * caller's signal that a rebuild is due: prt_scene_rebuild* below (a new tree, nothing re-uploaded) or
+ * prt_scene_update_vertices.  The library never rebuilds on its own.
  * With PRT_TEST_DUMP_BVH (dev-hooks build) the refitted tree is dumped after every successful refit (synchronous).
  */
 typedef struct PrtRefitInfo {
@@ -303,6 +310,43 @@ int prt_scene_refit(PrtScene* scene, const double* vertices, const double* norma
 int prt_scene_refit_device(PrtScene* scene, const void* d_vertices, const void* d_normals, void* hip_stream);
 /* Synchronous: waits for the last refit's end (the times and the SAH ratio come from the device). */
 int prt_scene_refit_info(const PrtScene* scene, PrtRefitInfo* out);
+
+/*
+ * Device-side REBUILD of the acceleration structure of an UPLOADED scene from new positions: the inputs and the read-only
+ * first phase are those of prt_scene_refit* (same layouts, same PRT_E_NO_DEVICE, same refusals: a coordinate that is not
+ * finite or beyond 1e18, a moved emitter vertex - PRT_E_INVALID, use prt_scene_update_vertices), but the result is a NEW
+ * topology from the device builder, while everything that does not depend on the positions stays resident.  The
+ * pattern: prt_scene_refit_device every frame, prt_scene_rebuild_device when PrtRefitInfo.sah_ratio says the tree has
+ * decayed; the library does not decide that for the caller.
+ *
+ * What is replaced.  The device builder (PRT_SCENE_DEVICE_BVH's) runs on the fp32 boxes of the new positions, computed
+ * on the device by the rule of the builders relative to the new grid origin.  The node array (n_nodes may change) and the
+ * leaf order are replaced; the shading records (uv, material, prim) are permuted on the device from the old leaf
+ * position of each triangle to its new one; the intersection records and the tangents are rewritten from the new
+ * vertices through the new order; the quantisation grid and the slab test's scale are the builder's.  Textures,
+ * materials, light tables, the record stride and the call slots are untouched: nothing is re-uploaded.
+ * Derived state.  stack_need is recomputed as at upload and the render kernels are sized again (the fp32 ones too if
+ * the fp32 tables exist: their records are re-converted, their tree is the new one).  The 32-entry collapse of a deep
+ * host-built tree is dropped: a device-built tree has none.  PrtBvhInfo afterwards reports built_on_device = 1, the new
+ * n_nodes, depth, stack_need and render_variant, and the builder's build_ms / sort_ms / tree_ms / split_ms.  The refit
+ * state follows the new topology: sah_ratio is 1.0 again and is measured against the new tree; refits keeps counting.
+ * Generation and host geometry: as for the refit.  The generation is bumped (accumulators: PRT_E_INVALID until
+ * prt_accum_reset); prt_scene_rebuild updates the host triangles, prt_scene_rebuild_device marks them stale.
+ * Ordering.  The call waits for the last refit; its writing phase waits, on hip_stream, for the work in flight on both
+ * call slots and for the last prt_render_features* call.  Unlike the refit it is SYNCHRONOUS: it returns when the new tree
+ * is resident (the builder reads counts back, and the old node array is freed).  The kernels of the device form run on
+ * hip_stream, and every later call orders itself after it.
+ * All or nothing.  The new tree, the new order and every new allocation are made BEFORE anything resident is written: a
+ * refusal, an allocation failure or a HIP error up to that point frees what the call made and leaves the scene, its
+ * generation, its frames and prt_scene_refit_info exactly as they were.  Afterwards the refit's wording applies: the
+ * generation and the grid are already the new ones.
+ * Small scenes.  The builder needs two triangles: with fewer the call behaves as prt_scene_refit* does (no triangles:
+ * PRT_OK).
+ * With PRT_TEST_DUMP_BVH (dev-hooks build) the rebuilt tree is dumped; PRT_TEST_FAIL_REBUILD=k (dev-hooks build) makes
+ * the k-th allocation of a rebuild (from 0; the builder's run counts as one) report PRT_E_OOM.
+ */
+int prt_scene_rebuild(PrtScene* scene, const double* vertices, const double* normals); /* host pointers */
+int prt_scene_rebuild_device(PrtScene* scene, const void* d_vertices, const void* d_normals, void* hip_stream);
 
 /* Number of light triangles and their order in the reference's area-CDF descent (BVH.cpp:86-100). */
 int prt_scene_bvh_info(const PrtScene* scene, PrtBvhInfo* out);

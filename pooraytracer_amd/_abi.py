@@ -267,6 +267,8 @@ EXPORTS = [
     "prt_scene_refit",
     "prt_scene_refit_device",
     "prt_scene_refit_info",
+    "prt_scene_rebuild",
+    "prt_scene_rebuild_device",
     "prt_scene_bvh_info",
     "prt_scene_light_count",
     "prt_scene_light_order",

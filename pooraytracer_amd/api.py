@@ -56,6 +56,8 @@ def load():
     L.prt_scene_refit.argtypes = [vp, vp, vp]
     L.prt_scene_refit_device.argtypes = [vp, vp, vp, vp]
     L.prt_scene_refit_info.argtypes = [vp, vp]
+    L.prt_scene_rebuild.argtypes = [vp, vp, vp]
+    L.prt_scene_rebuild_device.argtypes = [vp, vp, vp, vp]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
     L.prt_trace_closest.argtypes = [vp, vp, sz, vp, i32]
@@ -227,36 +229,52 @@ class Scene:
         _check(self._L.prt_scene_update_vertices(self._h, v.ctypes.data, None if n is None else n.ctypes.data), self._L)
         return self
 
-    def _refit_array(self, a, what):
+    def _refit_array(self, a, what, who="refit"):
         """A caller's positions (or normals) as the C call wants them; shape and dtype errors are raised here, before any call."""
         if not isinstance(a, np.ndarray):
-            raise TypeError(f"refit: {what} must be a numpy array, not {type(a).__name__}")
+            raise TypeError(f"{who}: {what} must be a numpy array, not {type(a).__name__}")
         if a.dtype != np.float64:
-            raise TypeError(f"refit: {what} must be float64, not {a.dtype}")
+            raise TypeError(f"{who}: {what} must be float64, not {a.dtype}")
         if a.shape != self.data.vertices.shape:
-            raise ValueError(f"refit: {what} must have shape {self.data.vertices.shape}, not {a.shape}")
+            raise ValueError(f"{who}: {what} must have shape {self.data.vertices.shape}, not {a.shape}")
         return np.ascontiguousarray(a)
+
+    def _positions_call(self, fn, who, vertices, normals):
+        v = self._refit_array(vertices, "vertices", who)
+        n = None if normals is None else self._refit_array(normals, "normals", who)
+        _check(fn(self._h, v.ctypes.data, None if n is None else n.ctypes.data), self._L)
+        return self
+
+    def _positions_call_device(self, fn, who, d_vertices_ptr, d_normals_ptr, stream):
+        for name, p in (("d_vertices_ptr", d_vertices_ptr), ("d_normals_ptr", d_normals_ptr), ("stream", stream)):
+            if isinstance(p, bool) or not (p is None or isinstance(p, (int, np.integer))):
+                raise TypeError(f"{who}: {name} must be an integer address or None, not {type(p).__name__}")
+        if not d_vertices_ptr and self.data.vertices.shape[0]:
+            raise ValueError(f"{who}: d_vertices_ptr is null")
+        _check(fn(self._h, int(d_vertices_ptr or 0) or None, int(d_normals_ptr or 0) or None, int(stream or 0) or None), self._L)
+        return self
 
     def refit(self, vertices, normals=None):
         """New positions for the same triangles of an uploaded scene, in place: the records and the BVH's boxes follow on the
         GPU, the tree keeps its topology and nothing is reloaded (prt_scene_refit).  Emitters must stay where they are."""
-        v = self._refit_array(vertices, "vertices")
-        n = None if normals is None else self._refit_array(normals, "normals")
-        _check(self._L.prt_scene_refit(self._h, v.ctypes.data, None if n is None else n.ctypes.data), self._L)
-        return self
+        return self._positions_call(self._L.prt_scene_refit, "refit", vertices, normals)
 
     def refit_device(self, d_vertices_ptr, d_normals_ptr=None, stream=None):
         """The same from device memory: raw pointers to [n_tris][3][3] float64 arrays on the scene's device (e.g.
         tensor.data_ptr() of a contiguous float64 tensor), asynchronous on `stream` after one small read-back.  The host
         copy of the geometry goes stale: upload() is refused until update_vertices() or refit() has replaced every position."""
-        for name, p in (("d_vertices_ptr", d_vertices_ptr), ("d_normals_ptr", d_normals_ptr), ("stream", stream)):
-            if isinstance(p, bool) or not (p is None or isinstance(p, (int, np.integer))):
-                raise TypeError(f"refit_device: {name} must be an integer address or None, not {type(p).__name__}")
-        if not d_vertices_ptr and self.data.vertices.shape[0]:
-            raise ValueError("refit_device: d_vertices_ptr is null")
-        _check(self._L.prt_scene_refit_device(self._h, int(d_vertices_ptr or 0) or None, int(d_normals_ptr or 0) or None,
-                                              int(stream or 0) or None), self._L)
-        return self
+        return self._positions_call_device(self._L.prt_scene_refit_device, "refit_device", d_vertices_ptr, d_normals_ptr, stream)
+
+    def rebuild(self, vertices, normals=None):
+        """New positions as for refit(), and a NEW tree of them from the device builder (prt_scene_rebuild): what a refitted
+        tree has lost (refit_info()["sah_ratio"]) comes back, while textures, materials and light tables stay resident.
+        Synchronous.  Emitters must stay where they are."""
+        return self._positions_call(self._L.prt_scene_rebuild, "rebuild", vertices, normals)
+
+    def rebuild_device(self, d_vertices_ptr, d_normals_ptr=None, stream=None):
+        """The same from device memory (the arguments of refit_device): the kernels run on `stream`, the call returns when the
+        new tree is resident.  The host copy of the geometry goes stale as after refit_device."""
+        return self._positions_call_device(self._L.prt_scene_rebuild_device, "rebuild_device", d_vertices_ptr, d_normals_ptr, stream)
 
     def refit_info(self):
         """PrtRefitInfo as a dict: refits since the upload, the last one's hipEvent times, the grid, sah_ratio (synchronous)."""

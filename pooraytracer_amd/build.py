@@ -6,7 +6,7 @@ Every source is compiled to its own object (in parallel, only when it or a heade
                      / PRT_VALIDATE_BVH hooks exist only there (failure-injection tests, sweep tools: api.dev_hooks()).
                      PRT_TEST_DUMP_BVH=<file> writes each scene's traversal tree (header, nodes, leaf order) when it is
                      built: host trees at create and on a host rebuild, device trees at upload, either after a refit
-                     (tests/bvh_model.py reads it).
+                     or a device rebuild of the resident scene (tests/bvh_model.py reads it).
 build_probe() builds tests/probe/libprt_probe.so, the test-only wrappers of prt_device.h's primitives — a library of its
 own, linked into neither of the two above.
 """

@@ -455,26 +455,29 @@ void launch_gather_tris(const DTri* tri_in, const DTriShade* shade_in, const uin
         }                                                                               \
     } while (0)
 
-bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t n_, DeviceBVH& out, std::string* err) {
+// The builder proper, on boxes that are in device memory already (written on `st`, or before the call): every kernel and
+// copy of the build runs on `st`, and the call returns when the tree is resident (the stream has been waited for).
+bool build_bvh_device_boxes(const PrimBox* d_boxes_in, const float box_origin[3], size_t n_, DeviceBVH& out, std::string* err,
+                            hipStream_t st) {
     static_assert(sizeof(PrimBox) == sizeof(FBox), "box layouts must agree");
     if (n_ < 2 || n_ >= ((size_t)1 << 28)) {
         if (err) *err = "device BVH build needs 2 <= triangles < 2^28";
         return false;
     }
     const uint32_t n = (uint32_t)n_;
+    const FBox* d_boxes = reinterpret_cast<const FBox*>(d_boxes_in);
     uint32_t M = 1;
     while (M < n) M <<= 1;
     const unsigned B = 256;
     auto blocks = [&](uint64_t items) { return (unsigned)std::max<uint64_t>(1, (items + B - 1) / B); };
 
     Scratch tmp;
-    FBox *d_boxes = nullptr, *d_tree = nullptr, *d_root = nullptr;
+    FBox *d_tree = nullptr, *d_root = nullptr;
     uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
     uint32_t *d_vals = nullptr, *d_order = nullptr;
     BuildState* d_state = nullptr;
     Item *d_q0 = nullptr, *d_q1 = nullptr;
     FNodeD* d_fn = nullptr;
-    BVH_HIP(tmp.alloc(&d_boxes, n));
     BVH_HIP(tmp.alloc(&d_tree, (size_t)2 * M));
     BVH_HIP(tmp.alloc(&d_root, 1));
     BVH_HIP(tmp.alloc(&d_keys, n));
@@ -505,8 +508,6 @@ bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t 
         }
     } ev_guard{ev};
 
-    BVH_HIP(hipMemcpy(d_boxes, h_boxes, (size_t)n * sizeof(FBox), hipMemcpyHostToDevice));
-    hipStream_t st = nullptr;
     BVH_HIP(hipEventRecord(ev[0], st));
     k_init_state<<<1, 1, 0, st>>>(d_state);
     k_centroid_bounds<<<std::min(blocks(n), 2048u), B, 0, st>>>(d_boxes, n, d_state);
@@ -529,11 +530,9 @@ bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t 
     // level-synchronous splits; level L holds at most min(2^L, n) open nodes
     const Item root{0, n, kNoParent, 0};
     BVH_HIP(hipMemcpyAsync(d_q0, &root, sizeof(Item), hipMemcpyHostToDevice, st));
-    {
-        const uint32_t one = 1;
-        BVH_HIP(hipMemcpyAsync(reinterpret_cast<char*>(d_state) + offsetof(BuildState, counts), &one, sizeof(one),
-                               hipMemcpyHostToDevice, st));
-    }
+    const uint32_t one = 1; // (lives until the stream has been waited for, like `root`)
+    BVH_HIP(hipMemcpyAsync(reinterpret_cast<char*>(d_state) + offsetof(BuildState, counts), &one, sizeof(one),
+                           hipMemcpyHostToDevice, st));
     Item *qin = d_q0, *qout = d_q1;
     for (int level = 0; level <= kMaxLevels; ++level) {
         const uint64_t cap = level >= 31 ? (uint64_t)n : std::min<uint64_t>((uint64_t)1 << level, n);
@@ -545,7 +544,8 @@ bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t 
 
     BuildState hs;
     FBox root_box;
-    BVH_HIP(hipMemcpy(&hs, d_state, sizeof(hs), hipMemcpyDeviceToHost)); // synchronises with the stream
+    BVH_HIP(hipStreamSynchronize(st)); // (a non-blocking stream: the copies below do not wait for it by themselves)
+    BVH_HIP(hipMemcpy(&hs, d_state, sizeof(hs), hipMemcpyDeviceToHost));
     BVH_HIP(hipMemcpy(&root_box, d_root, sizeof(root_box), hipMemcpyDeviceToHost));
     if (hs.n_nodes == 0 || hs.n_nodes >= n || hs.counts[kMaxLevels + 1] != 0) {
         if (err) *err = "device BVH build: inconsistent node count";
@@ -599,6 +599,7 @@ bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t 
         }
         BVH_HIP(hipGetLastError());
         WideState hw;
+        BVH_HIP(hipStreamSynchronize(st));
         BVH_HIP(hipMemcpy(&hw, d_ws, sizeof(hw), hipMemcpyDeviceToHost));
         if (hw.n_wide == 0 || hw.n_wide > hs.n_nodes || hw.counts[kMaxLevels + 1] != 0) {
             if (err) *err = "device BVH build: inconsistent wide node count";
@@ -642,6 +643,19 @@ bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t 
     cs = std::nextafter(std::max(cs, gm), std::numeric_limits<float>::infinity());
     out.coord_scale = cs;
     return true;
+}
+
+// From host boxes (prt_scene_upload): they are copied to the device, the build runs on the null stream.
+bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t n, DeviceBVH& out, std::string* err) {
+    if (n < 2 || n >= ((size_t)1 << 28)) {
+        if (err) *err = "device BVH build needs 2 <= triangles < 2^28";
+        return false;
+    }
+    Scratch tmp;
+    PrimBox* d_boxes = nullptr;
+    BVH_HIP(tmp.alloc(&d_boxes, n));
+    BVH_HIP(hipMemcpy(d_boxes, h_boxes, n * sizeof(PrimBox), hipMemcpyHostToDevice));
+    return build_bvh_device_boxes(d_boxes, box_origin, n, out, err, nullptr);
 }
 
 } // namespace prt

@@ -6,6 +6,8 @@
 //   k_refit_tris     one thread per leaf position: the Triangle constructor precompute (scene_setup.cpp,
 //                    setup_triangle_geometry) and the DTri / DTriShade derivation of prt_scene_upload on the new vertices,
 //                    written straight into the resident records, plus the triangle's fp32 box by the rule of prim_boxes
+//   k_prim_boxes     prt_scene_rebuild: the same box rule for every triangle in description order, the device builder's input
+//   k_permute_shade  prt_scene_rebuild: the shading records from the old leaf order into the new one (k_invert_order first)
 //   k_refit_parents  once per topology: the parent of every node
 //   k_refit_boxes    bottom-up over the 64-byte nodes: every thread fills the leaf slots of its own node, then arrives at
 //                    the node's counter; the last arriver of a node (its own thread and one per inner child) fills the
@@ -203,6 +205,17 @@ struct RefitFrame { // prim_boxes' numbers for this refit, computed on the host 
     double delta;     // 1e-9 extent + 256 eps scale
 };
 
+// the triangle's fp32 box relative to the grid origin (bvh_build.cpp, prim_boxes): b[0..2] lo, b[3..5] hi
+__device__ inline void tri_box(V p0, V p1, V p2, const RefitFrame& F, float* __restrict__ b) {
+    const double c[3][3] = {{p0.x, p1.x, p2.x}, {p0.y, p1.y, p2.y}, {p0.z, p1.z, p2.z}};
+    for (int a = 0; a < 3; ++a) {
+        double lo, hi;
+        tri_interval(c[a][0], c[a][1], c[a][2], lo, hi);
+        b[a] = round_down((lo - F.delta) - F.origin[a]);
+        b[3 + a] = round_up((hi + F.delta) - F.origin[a]);
+    }
+}
+
 __global__ void __launch_bounds__(kBlock) k_refit_tris(const double* __restrict__ verts, const double* __restrict__ normals,
                                                        const uint32_t* __restrict__ order, uint32_t n, char* __restrict__ tris,
                                                        uint32_t tri_stride, DTriShadeT<double>* __restrict__ shade,
@@ -257,15 +270,39 @@ __global__ void __launch_bounds__(kBlock) k_refit_tris(const double* __restrict_
     S.tangent[0] = tg.x;
     S.tangent[1] = tg.y;
     S.tangent[2] = tg.z;
-    // the triangle's fp32 box relative to the grid origin (bvh_build.cpp, prim_boxes)
-    const double c[3][3] = {{p0.x, p1.x, p2.x}, {p0.y, p1.y, p2.y}, {p0.z, p1.z, p2.z}};
-    float* b = tbox + (size_t)i * 6;
-    for (int a = 0; a < 3; ++a) {
-        double lo, hi;
-        tri_interval(c[a][0], c[a][1], c[a][2], lo, hi);
-        b[a] = round_down((lo - F.delta) - F.origin[a]);
-        b[3 + a] = round_up((hi + F.delta) - F.origin[a]);
-    }
+    tri_box(p0, p1, p2, F, tbox + (size_t)i * 6);
+}
+
+// The builder's input: the PrimBox of every triangle in DESCRIPTION order (prt_scene_rebuild).
+__global__ void __launch_bounds__(kBlock) k_prim_boxes(const double* __restrict__ verts, uint32_t n, float* __restrict__ boxes,
+                                                       RefitFrame F) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const double* pv = verts + (size_t)t * 9;
+    tri_box(load3(pv), load3(pv + 3), load3(pv + 6), F, boxes + (size_t)t * 6);
+}
+
+// inv[order[i]] = i: where the triangle of description index t sits in a leaf order
+__global__ void __launch_bounds__(kBlock) k_invert_order(const uint32_t* __restrict__ order, uint32_t n, uint32_t* __restrict__ inv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = order[i];
+    if (t < n) inv[t] = i;
+}
+
+// shade_new[j] = shade_old[inv_old[new_order[j]]], out of place, 16 bytes per lane (bvh_build_gpu.hip, k_gather_tris)
+__global__ void __launch_bounds__(kBlock) k_permute_shade(const uint4* __restrict__ shade_old, const uint32_t* __restrict__ inv_old,
+                                                          const uint32_t* __restrict__ new_order, uint32_t n,
+                                                          uint4* __restrict__ shade_new) {
+    constexpr uint32_t SP = sizeof(DTriShadeT<double>) / 16;
+    const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = (uint32_t)(x / SP), c = (uint32_t)(x % SP);
+    if (j >= n) return;
+    const uint32_t t = new_order[j];
+    if (t >= n) return; // (permutations by construction; never index out of a buffer)
+    const uint32_t src = inv_old[t];
+    if (src >= n) return;
+    shade_new[(uint64_t)j * SP + c] = shade_old[(uint64_t)src * SP + c];
 }
 
 __global__ void __launch_bounds__(kBlock) k_refit_parents(const DNode* __restrict__ nodes, uint32_t n_nodes,
@@ -452,6 +489,25 @@ void launch_refit_tris(const double* d_verts, const double* d_normals, const uin
     F.delta = delta;
     k_refit_tris<<<blocks_for(n), kBlock, 0, st>>>(d_verts, d_normals, d_order, n, static_cast<char*>(d_tris), tri_stride, d_shade,
                                                    d_tbox, F);
+}
+
+// d_boxes: n PrimBox (prt_host.h: float lo[3], hi[3]) in description order
+void launch_prim_boxes(const double* d_verts, uint32_t n, float* d_boxes, const double origin[3], double delta, hipStream_t st) {
+    if (!n) return;
+    RefitFrame F;
+    for (int a = 0; a < 3; ++a) F.origin[a] = origin[a];
+    F.delta = delta;
+    k_prim_boxes<<<blocks_for(n), kBlock, 0, st>>>(d_verts, n, d_boxes, F);
+}
+
+// The shading records from the leaf order `d_old_order` into the leaf order `d_new_order`; d_inv: n entries of scratch.
+void launch_permute_shade(const DTriShadeT<double>* d_shade_old, const uint32_t* d_old_order, const uint32_t* d_new_order,
+                          uint32_t n, uint32_t* d_inv, DTriShadeT<double>* d_shade_new, hipStream_t st) {
+    static_assert(sizeof(DTriShadeT<double>) % 16 == 0, "records are moved in 16-byte pieces");
+    if (!n) return;
+    k_invert_order<<<blocks_for(n), kBlock, 0, st>>>(d_old_order, n, d_inv);
+    k_permute_shade<<<blocks_for((uint64_t)n * (sizeof(DTriShadeT<double>) / 16)), kBlock, 0, st>>>(
+        reinterpret_cast<const uint4*>(d_shade_old), d_inv, d_new_order, n, reinterpret_cast<uint4*>(d_shade_new));
 }
 
 void launch_refit_parents(const DNode* d_nodes, uint32_t n_nodes, uint32_t* d_parent, hipStream_t st) {

@@ -80,6 +80,12 @@ void launch_refit_tris(const double* d_verts, const double* d_normals, const uin
                        uint32_t tri_stride, DTriShadeT<double>* d_shade, float* d_tbox, const double origin[3], double delta,
                        hipStream_t st);
 void launch_refit_parents(const DNode* d_nodes, uint32_t n_nodes, uint32_t* d_parent, hipStream_t st);
+void launch_prim_boxes(const double* d_verts, uint32_t n, float* d_boxes, const double origin[3], double delta, hipStream_t st);
+void launch_permute_shade(const DTriShadeT<double>* d_shade_old, const uint32_t* d_old_order, const uint32_t* d_new_order,
+                          uint32_t n, uint32_t* d_inv, DTriShadeT<double>* d_shade_new, hipStream_t st);
+// bvh_build_gpu.hip: the device builder on boxes that are on the device already, on a stream (build_bvh_device: prt_host.h)
+bool build_bvh_device_boxes(const PrimBox* d_boxes, const float box_origin[3], size_t n, DeviceBVH& out, std::string* err,
+                            hipStream_t st);
 hipError_t launch_refit_boxes(DNode* d_nodes, uint32_t n_nodes, const uint32_t* d_parent, uint32_t* d_cnt, const float* d_tbox,
                               uint32_t n_tris, const float step[3], hipStream_t st);
 void launch_refit_sah(const DNode* d_nodes, uint32_t n_nodes, const float origin[3], const float step[3], void* d_scratch,
@@ -366,6 +372,17 @@ struct PrtScene {
         *out = p.get();
         allocs.push_back(std::move(p));
         return PRT_OK;
+    }
+    // The owner of a resident array, out of `allocs` (null, or not there: an empty owner).
+    DevBuf<> take(const void* p) {
+        DevBuf<> out;
+        for (auto it = allocs.begin(); p && it != allocs.end(); ++it)
+            if (it->get() == p) {
+                out = std::move(*it);
+                allocs.erase(it);
+                break;
+            }
+        return out;
     }
     void release() {
         if (device >= 0) (void)hipSetDevice(device);
@@ -1065,6 +1082,12 @@ int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double*
 // (synchronous; the scene then holds both).  Triangle and shading records and texels are converted on the device —
 // they already are in BVH leaf order there, whichever builder made the tree — the small tables on the host.
 static int ensure_f32_impl(PrtScene* s);
+// Stack entries per lane of the fp32 kernels for a tree that needs `need`.
+static int f32_stack_depth(int need) {
+    int depth = need <= PRT_STACK_SHALLOW ? PRT_STACK_SHALLOW : PRT_STACK_DEPTH;
+    if (const char* e = dev_env("PRT_TUNE_STACK32")) depth = std::max(need, std::min(PRT_STACK_DEPTH, std::atoi(e))); // developer: smaller stacks when the tree allows
+    return depth;
+}
 // All or nothing, like the upload: a failure frees what this call allocated and leaves the scene without fp32 tables.
 static int ensure_f32(PrtScene* s) {
     if (s->f32_ready) return PRT_OK;
@@ -1161,8 +1184,7 @@ static int ensure_f32_impl(PrtScene* s) {
             f.n_nodes = s->n_nodes_shallow;
             need = std::min(need, PRT_STACK_SHALLOW);
         }
-        k.stack_depth = need <= PRT_STACK_SHALLOW ? PRT_STACK_SHALLOW : PRT_STACK_DEPTH;
-        if (const char* e = dev_env("PRT_TUNE_STACK32")) k.stack_depth = std::max(need, std::min(PRT_STACK_DEPTH, std::atoi(e))); // developer: smaller stacks when the tree allows
+        k.stack_depth = f32_stack_depth(need);
         if (dev_env("PRT_TUNE_VERBOSE")) std::fprintf(stderr, "[prt] fp32 tables: tree needs %d stack entries, using %d\n", need, k.stack_depth);
     }
     size_kernels(s, k, false); // the fp32 kernels keep their LDS tables whatever they cost in occupancy
@@ -1237,12 +1259,17 @@ static int refit_prepare(PrtScene* s, hipStream_t st) {
     return PRT_OK;
 }
 
-// d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
-static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
+// The numbers of prim_boxes and quant_grid for a set of new positions, from the bounds of the first phase.
+struct RefitGridHost {
+    float origin[3], step[3], root_hi[3]; // the fp32 grid origin; the grid's steps and the root box's upper corner relative to it
+    double origin_d[3], delta;            // the origin widened; prim_boxes' margin
+};
+
+// What a refit and a rebuild share up to the decision.  after_refit, the working arrays (refit_prepare; a failure frees what
+// this call made), then phase 1, read-only: vertex range, scene bounds, emitters in place; the one read-back; the grid.
+static int refit_begin(PrtScene* s, const std::string& who, const double* d_verts, hipStream_t st, RefitGridHost& g) {
     DScene& d = s->k64.d;
     const uint32_t n = d.n_tris;
-    if (n == 0) return PRT_OK; // nothing to move (the empty scene's root is never traversed)
-    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
     PrtScene::Refit& R = s->refit;
     PRT_HIP_AS(who, s->after_refit(st)); // one refit at a time: they share the working arrays
     {
@@ -1264,7 +1291,6 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
             return rc;
         }
     }
-    // phase 1, read-only: vertex range, scene bounds, emitters in place; then the one read-back of the call
     prt::launch_refit_check(d_verts, n, d.light_tris, (uint32_t)d.n_lights, R.d_scratch, R.d_check, st);
     PRT_HIP_AS(who, hipGetLastError());
     prt::RefitCheck c;
@@ -1280,43 +1306,73 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     // builders is the union of the triangles' fp32 boxes; rounding and the subtraction are monotone, so its upper corner
     // is the box rule applied to the upper corner of the bounds.
     const double extent = std::max(1.0, std::max(c.hi[0] - c.lo[0], std::max(c.hi[1] - c.lo[1], c.hi[2] - c.lo[2])));
-    const double delta = 1e-9 * extent + 256.0 * std::numeric_limits<double>::epsilon() * c.scale;
-    float origin[3], step[3], root_hi[3], rel0[3];
-    double origin_d[3];
+    g.delta = 1e-9 * extent + 256.0 * std::numeric_limits<double>::epsilon() * c.scale;
     for (int a = 0; a < 3; ++a) {
-        origin[a] = f32_round_down(c.lo[a] - 2.0 * delta);
-        origin_d[a] = (double)origin[a];
-        root_hi[a] = f32_round_up((c.hi[a] + delta) - origin_d[a]);
+        g.origin[a] = f32_round_down(c.lo[a] - 2.0 * g.delta);
+        g.origin_d[a] = (double)g.origin[a];
+        g.root_hi[a] = f32_round_up((c.hi[a] + g.delta) - g.origin_d[a]);
     }
-    {
-        const float zero[3] = {0.f, 0.f, 0.f};
-        prt::quant_grid(zero, root_hi, false, rel0, step);
-    }
-    // phase 2 writes what calls in flight read: wait for both call slots and the last features call first
+    const float zero[3] = {0.f, 0.f, 0.f};
+    float rel0[3];
+    prt::quant_grid(zero, g.root_hi, false, rel0, g.step);
+    return PRT_OK;
+}
+
+// The writing phase changes what calls in flight read: `st` waits for both call slots and the last features call first.
+static int refit_wait_readers(PrtScene* s, const std::string& who, hipStream_t st) {
     for (PrtScene::CallSlot& q : s->slots)
         if (q.timed) PRT_HIP_AS(who, hipStreamWaitEvent(st, q.done.get(), 0));
     if (s->feat_pending) PRT_HIP_AS(who, hipStreamWaitEvent(st, s->feat_done.get(), 0));
-    // The geometry changes from here on, even if a launch below fails half way (as in prt_scene_update_vertices): the
-    // generation and the grid, in every copy (the host tree's, both DScenes), go first, so that a scene whose records were
-    // partly rewritten never passes for the old one.
+    return PRT_OK;
+}
+
+// The geometry changes from here on, even if a launch afterwards fails half way (as in prt_scene_update_vertices): the
+// generation and the grid, in every copy (the host tree's, both DScenes), go first, so that a scene whose records were
+// partly rewritten never passes for the old one.
+static void refit_commit_grid(PrtScene* s, const float origin[3], const float step[3], float coord_scale) {
+    DScene& d = s->k64.d;
+    double e = 0.0;
+    for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)step[a]);
+    s->bvh.coord_scale = coord_scale;
+    for (int a = 0; a < 3; ++a) {
+        s->bvh.grid_origin[a] = d.grid_origin[a] = s->k32.d.grid_origin[a] = origin[a];
+        s->bvh.grid_step[a] = d.grid_step[a] = s->k32.d.grid_step[a] = step[a];
+    }
+    d.slab_scale = s->k32.d.slab_scale = std::nextafter((float)e, std::numeric_limits<float>::infinity());
+    ++s->generation;
+}
+
+// PRT_TEST_DUMP_BVH: the resident tree, as the kernels now get it (synchronous)
+static int dump_resident_bvh(PrtScene* s, const std::string& who, const char* path, hipStream_t st) {
+    const DScene& d = s->k64.d;
+    std::vector<DNode> hn(d.n_nodes);
+    std::vector<uint32_t> ho(d.n_tris);
+    PRT_HIP_AS(who, hipStreamSynchronize(st));
+    PRT_HIP_AS(who, hipMemcpy(hn.data(), d.nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+    PRT_HIP_AS(who, hipMemcpy(ho.data(), s->d_order, ho.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return dump_bvh(path, s, hn.data(), hn.size(), ho.data(), s->stack_need);
+}
+
+// d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
+static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
+    DScene& d = s->k64.d;
+    const uint32_t n = d.n_tris;
+    if (n == 0) return PRT_OK; // nothing to move (the empty scene's root is never traversed)
+    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
+    PrtScene::Refit& R = s->refit;
+    RefitGridHost g;
+    if (const int rc = refit_begin(s, who, d_verts, st, g)) return rc;
+    const float *origin = g.origin, *step = g.step;
+    if (const int rc = refit_wait_readers(s, who, st)) return rc;
     {
-        double e = 0.0;
-        for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)step[a]);
-        const float slab = std::nextafter((float)e, std::numeric_limits<float>::infinity());
-        float cs = std::max(root_hi[0], std::max(root_hi[1], root_hi[2]));
+        float cs = std::max(g.root_hi[0], std::max(g.root_hi[1], g.root_hi[2]));
         if (s->bvh_info.built_on_device) // (the device builder also covers the grid's far corner)
             for (int a = 0; a < 3; ++a) cs = std::max(cs, (float)(65535.0 * (double)step[a]));
-        s->bvh.coord_scale = std::nextafter(cs, std::numeric_limits<float>::infinity());
-        for (int a = 0; a < 3; ++a) {
-            s->bvh.grid_origin[a] = d.grid_origin[a] = s->k32.d.grid_origin[a] = origin[a];
-            s->bvh.grid_step[a] = d.grid_step[a] = s->k32.d.grid_step[a] = step[a];
-        }
-        d.slab_scale = s->k32.d.slab_scale = slab;
-        ++s->generation;
+        refit_commit_grid(s, origin, step, std::nextafter(cs, std::numeric_limits<float>::infinity()));
     }
     PRT_HIP_AS(who, hipEventRecord(R.ev0.get(), st));
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
-                           R.d_tbox, origin_d, delta, st);
+                           R.d_tbox, g.origin_d, g.delta, st);
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
         const DSceneT<float>& f = s->k32.d;
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
@@ -1333,14 +1389,8 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     PRT_HIP_AS(who, hipEventRecord(R.ev2.get(), st));
     PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
     ++R.count;
-    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) { // the refitted tree, as the kernels now get it (synchronous)
-        std::vector<DNode> hn(d.n_nodes);
-        std::vector<uint32_t> ho(n);
-        PRT_HIP_AS(who, hipStreamSynchronize(st));
-        PRT_HIP_AS(who, hipMemcpy(hn.data(), d.nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
-        PRT_HIP_AS(who, hipMemcpy(ho.data(), s->d_order, ho.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (const int rc = dump_bvh(path, s, hn.data(), hn.size(), ho.data(), s->stack_need)) return rc;
-    }
+    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) // the refitted tree
+        if (const int rc = dump_resident_bvh(s, who, path, st)) return rc;
     return PRT_OK;
 }
 
@@ -1353,28 +1403,138 @@ int prt_scene_refit_device(PrtScene* s, const void* d_vertices, const void* d_no
     return rc;
 }
 
-int prt_scene_refit(PrtScene* s, const double* vertices, const double* normals) {
-    int rc = require_uploaded(s, "prt_scene_refit");
+// ---- prt_scene_rebuild: new positions for a resident scene and a NEW tree of them from the device builder; textures,
+// materials and light tables stay resident (kernels in bvh_refit.hip, the builder in bvh_build_gpu.hip)
+static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
+    DScene& d = s->k64.d;
+    const uint32_t n = d.n_tris;
+    if (n < 2) return refit_impl(s, who, d_verts, d_normals, st); // the builder needs two triangles: one triangle's tree has one shape
+    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
+    PrtScene::Refit& R = s->refit;
+    RefitGridHost g;
+    if (const int rc = refit_begin(s, who, d_verts, st, g)) return rc;
+    // Everything the new tree needs is made before anything resident is written: a failure up to the commit below frees
+    // what this call made (the owners are locals) and leaves the scene as it was.
+    // test hook (PRT_TEST_FAIL_REBUILD=k): the k-th allocation of the rebuild, the builder run counting as one, reports out-of-memory
+    const int fail_at = dev_env("PRT_TEST_FAIL_REBUILD") ? std::atoi(dev_env("PRT_TEST_FAIL_REBUILD")) : -1;
+    int n_allocs = 0;
+    auto injected = [&]() { return n_allocs++ == fail_at; };
+    auto alloc = [&](size_t bytes, DevBuf<>& out) -> int {
+        if (injected()) return fail(PRT_E_OOM, who + ": injected allocation failure (PRT_TEST_FAIL_REBUILD)");
+        PRT_HIP_AS(who, dev_alloc(out, std::max<size_t>(bytes, 256)));
+        return PRT_OK;
+    };
+    DevBuf<> boxes, nodes, order, shade, inv, parent, cnt;
+    int rc;
+    if ((rc = alloc((size_t)n * sizeof(prt::PrimBox), boxes))) return rc;
+    prt::launch_prim_boxes(d_verts, n, static_cast<float*>(boxes.get()), g.origin_d, g.delta, st);
+    PRT_HIP_AS(who, hipGetLastError());
+    prt::DeviceBVH db;
+    {
+        if (injected()) return fail(PRT_E_OOM, who + ": injected allocation failure (PRT_TEST_FAIL_REBUILD)");
+        std::string err;
+        if (!prt::build_bvh_device_boxes(static_cast<const prt::PrimBox*>(boxes.get()), g.origin, n, db, &err, st))
+            return fail(PRT_E_HIP, who + ": " + err);
+        nodes.reset(db.d_nodes);
+        order.reset(db.d_order);
+    }
+    if ((rc = alloc((size_t)n * sizeof(DTriShade), shade)) || (rc = alloc((size_t)n * sizeof(uint32_t), inv)) ||
+        (rc = alloc((size_t)db.n_nodes * sizeof(uint32_t), parent)) || (rc = alloc(round16((size_t)db.n_nodes * sizeof(uint32_t)), cnt)))
+        return rc;
+    int need = PRT_STACK_DEPTH; // as at upload: the nodes come back once for the count (larger trees keep the bound)
+    if (db.n_nodes <= (1u << 21)) {
+        try {
+            std::vector<DNode> hn(db.n_nodes);
+            PRT_HIP_AS(who, hipMemcpy(hn.data(), db.d_nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+            need = prt::tree_stack_need(hn.data(), hn.size());
+        } catch (const std::bad_alloc&) {
+            return fail(PRT_E_OOM, who + ": out of host memory");
+        }
+    }
+    if ((rc = refit_wait_readers(s, who, st))) return rc;
+
+    // Commit.  From here on the refit's wording applies: the generation and the grid are the new ones.  The scene takes
+    // the new arrays at once; the ones they replace stay alive in `old` until this call returns (freeing waits for the device).
+    refit_commit_grid(s, db.grid_origin, db.grid_step, db.coord_scale);
+    const DTriShade* const shade_old = d.shade;
+    const uint32_t* const order_old = s->d_order;
+    DevBuf<> old[8] = {s->take(d.nodes),  s->take(s->d_order),        s->take(d.shade),      s->take(R.d_parent),
+                       s->take(R.d_cnt),  s->take(s->d_nodes_shallow), s->take(R.d_parent_sh), s->take(R.d_cnt_sh)};
+    d.nodes = static_cast<const DNode*>(nodes.get());
+    d.n_nodes = db.n_nodes;
+    d.shade = static_cast<const DTriShade*>(shade.get());
+    s->d_order = static_cast<const uint32_t*>(order.get());
+    R.d_parent = static_cast<uint32_t*>(parent.get());
+    R.d_cnt = static_cast<uint32_t*>(cnt.get());
+    R.d_parent_sh = R.d_cnt_sh = nullptr; // a device-built tree has no 32-entry collapse
+    s->d_nodes_shallow = nullptr;
+    s->n_nodes_shallow = 0;
+    for (DevBuf<>* b : {&nodes, &order, &shade, &parent, &cnt}) s->allocs.push_back(std::move(*b)); // (room for more than `old` took out)
+    s->device_bvh = true; // a later upload builds on the device as well: the host tree is not this one
+    s->bvh.depth = db.depth;
+    s->last.bvh_nodes = s->bvh_info.n_nodes = db.n_nodes;
+    s->last.bvh_depth = s->bvh_info.depth = db.depth;
+    s->bvh_info.built_on_device = 1;
+    s->bvh_info.build_ms = db.ms_total;
+    s->bvh_info.sort_ms = db.ms_sort;
+    s->bvh_info.tree_ms = db.ms_tree;
+    s->bvh_info.split_ms = db.ms_split;
+    s->stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH);
+    s->k64.blocks_per_cu_rays = 0;
+    s->blocks_wanted = size_kernels(s, s->k64, true);
+    if (s->f32_ready) {
+        KernelConfig<float>& k = s->k32;
+        k.d.nodes = d.nodes;
+        k.d.n_nodes = d.n_nodes;
+        k.stack_depth = f32_stack_depth(s->stack_need);
+        k.blocks_per_cu_rays = 0;
+        size_kernels(s, k, false);
+    }
+    prt::launch_permute_shade(shade_old, order_old, s->d_order, n, static_cast<uint32_t*>(inv.get()), const_cast<DTriShade*>(d.shade), st);
+    prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
+                           R.d_tbox, g.origin_d, g.delta, st);
+    if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
+        const DSceneT<float>& f = s->k32.d;
+        prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
+        prt32::launch_convert_shade(d.shade, n, const_cast<DTriShadeT<float>*>(f.shade), st);
+    }
+    // the refit state of the new topology: parents, and the SAH cost that sah_ratio is measured against from now on
+    prt::launch_refit_parents(d.nodes, d.n_nodes, R.d_parent, st);
+    prt::launch_refit_sah(d.nodes, d.n_nodes, d.grid_origin, d.grid_step, R.d_scratch, R.d_sah, st);
+    PRT_HIP_AS(who, hipGetLastError());
+    PRT_HIP_AS(who, hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st));
+    PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
+    PRT_HIP_AS(who, hipStreamSynchronize(st)); // synchronous: the new tree is resident, what it replaced can go
+    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) // the rebuilt tree
+        if ((rc = dump_resident_bvh(s, who, path, st))) return rc;
+    return PRT_OK;
+}
+
+// The host-pointer forms of the refit and the rebuild: the caller's arrays go to the device, the host triangles follow.
+static int host_positions(PrtScene* s, const char* name, const double* vertices, const double* normals, bool rebuild) {
+    const std::string who = name;
+    int rc = require_uploaded(s, name);
     if (rc) return rc;
     const size_t n = s->tris.size(), bytes = n * 9 * sizeof(double);
     if (n == 0) return PRT_OK;
-    if (!vertices) return fail(PRT_E_INVALID, "prt_scene_refit: null vertices");
+    if (!vertices) return fail(PRT_E_INVALID, who + ": null vertices");
     // device copies of the caller's arrays, in a buffer the scene keeps (a previous refit may still be reading it)
-    PRT_HIP_AS("prt_scene_refit", s->refit_in.reserve(bytes * (normals ? 2 : 1), nullptr));
+    PRT_HIP_AS(who, s->refit_in.reserve(bytes * (normals ? 2 : 1), nullptr));
     double* dv = s->refit_in.get<double>();
     double* dn = normals ? dv + n * 9 : nullptr;
     PRT_HIP(hipMemcpyAsync(dv, vertices, bytes, hipMemcpyHostToDevice, nullptr));
     if (normals) PRT_HIP(hipMemcpyAsync(dn, normals, bytes, hipMemcpyHostToDevice, nullptr));
-    rc = refit_impl(s, "prt_scene_refit", dv, dn, nullptr);
-    PRT_HIP_AS("prt_scene_refit", s->refit_in.used(nullptr));
+    rc = (rebuild ? rebuild_impl : refit_impl)(s, who, dv, dn, nullptr);
+    PRT_HIP_AS(who, s->refit_in.used(nullptr));
     if (rc != PRT_OK) {
         const std::string keep = g_err;
         (void)hipStreamSynchronize(nullptr); // the caller's arrays are free again on every way out
         g_err = keep;
         return rc;
     }
-    // the host triangles follow, so that a later upload or update sees this geometry; the host tree's boxes do not (they
-    // were refitted on the device only): that upload builds a fresh tree, on the GPU where there are two triangles to split
+    // the host triangles follow, so that a later upload or update sees this geometry; the host tree does not (the boxes
+    // were refitted, or the tree rebuilt, on the device only): that upload builds a fresh tree, on the GPU where there are
+    // two triangles to split
     try {
         prt::update_triangles(vertices, normals, s->tris);
         s->host_stale = false;
@@ -1382,14 +1542,31 @@ int prt_scene_refit(PrtScene* s, const double* vertices, const double* normals) 
             if (n >= 2) s->device_bvh = true;
             else {
                 std::string err;
-                if (!prt::build_bvh(s->tris, s->bvh, &err)) return fail(PRT_E_LIMIT, "prt_scene_refit: " + err);
+                if (!prt::build_bvh(s->tris, s->bvh, &err)) return fail(PRT_E_LIMIT, who + ": " + err);
             }
         }
     } catch (const std::bad_alloc&) {
         s->host_stale = true; // the device holds the new geometry, the host triangles may not
-        return fail(PRT_E_OOM, "prt_scene_refit: out of host memory (the resident scene was refitted)");
+        return fail(PRT_E_OOM, who + ": out of host memory (the resident scene holds the new geometry)");
     }
     return PRT_OK;
+}
+
+int prt_scene_refit(PrtScene* s, const double* vertices, const double* normals) {
+    return host_positions(s, "prt_scene_refit", vertices, normals, false);
+}
+
+int prt_scene_rebuild(PrtScene* s, const double* vertices, const double* normals) {
+    return host_positions(s, "prt_scene_rebuild", vertices, normals, true);
+}
+
+int prt_scene_rebuild_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
+    int rc = require_uploaded(s, "prt_scene_rebuild_device");
+    if (rc) return rc;
+    rc = rebuild_impl(s, "prt_scene_rebuild_device", static_cast<const double*>(d_vertices), static_cast<const double*>(d_normals),
+                      reinterpret_cast<hipStream_t>(stream));
+    if (rc == PRT_OK && !s->tris.empty()) s->host_stale = true; // the host triangles still hold the old positions
+    return rc;
 }
 
 int prt_scene_refit_info(const PrtScene* s, PrtRefitInfo* out) {
