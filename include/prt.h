@@ -270,8 +270,10 @@ int prt_scene_update_vertices(PrtScene* scene, const double* vertices, const dou
  * Grid.  The quantisation grid of the 16-bit boxes (origin, step, the slab test's scale) is recomputed from the new scene
  * bounds on every refit by the builders' rule, so a scene that grows, shrinks or moves far away keeps tight,
  * conservative boxes.
- * Emitters do not move in this version: if a vertex of any triangle of a light mesh differs bitwise from the resident
- * light triangle, the call fails with PRT_E_INVALID (use prt_scene_update_vertices, which rebuilds the light tree).
+ * Emitters stay in place by default: if a vertex of any triangle of a light mesh differs bitwise from the resident
+ * light triangle, the call fails with PRT_E_INVALID (use prt_scene_update_vertices, which rebuilds the light tree) -
+ * unless the scene allows it with prt_scene_set_dynamic_lights (below): then the light tree, its records and its O(1)
+ * tables follow on the device, and the call has a second host synchronisation.
  * A vertex coordinate that is not finite or beyond 1e18 is PRT_E_INVALID, as in prt_scene_update_vertices; the check
  * runs on the device, where the coordinates are.
  * All or nothing.  Both checks run in a read-only first phase over the new vertices, which also reduces the scene
@@ -314,7 +316,8 @@ int prt_scene_refit_info(const PrtScene* scene, PrtRefitInfo* out);
 /*
  * Device-side REBUILD of the acceleration structure of an UPLOADED scene from new positions: the inputs and the read-only
  * first phase are those of prt_scene_refit* (same layouts, same PRT_E_NO_DEVICE, same refusals: a coordinate that is not
- * finite or beyond 1e18, a moved emitter vertex - PRT_E_INVALID, use prt_scene_update_vertices), but the result is a NEW
+ * finite or beyond 1e18, a moved emitter vertex - PRT_E_INVALID, use prt_scene_update_vertices or allow it with
+ * prt_scene_set_dynamic_lights), but the result is a NEW
  * topology from the device builder, while everything that does not depend on the positions stays resident.  The
  * pattern: prt_scene_refit_device every frame, prt_scene_rebuild_device when PrtRefitInfo.sah_ratio says the tree has
  * decayed; the library does not decide that for the caller.
@@ -347,6 +350,60 @@ int prt_scene_refit_info(const PrtScene* scene, PrtRefitInfo* out);
  */
 int prt_scene_rebuild(PrtScene* scene, const double* vertices, const double* normals); /* host pointers */
 int prt_scene_rebuild_device(PrtScene* scene, const void* d_vertices, const void* d_normals, void* hip_stream);
+
+/*
+ * Moving emitters.  Off by default: prt_scene_refit* / prt_scene_rebuild* refuse a moved emitter vertex as described above,
+ * with the same code, message and single host synchronisation.  On: they accept it, and after a successful call the light
+ * state of the scene is what a fresh scene created from the new vertices has - the CDF order (prt_scene_light_order), every
+ * light record (vertices, normal, area, pdf), the total area, the tree and the O(1) table words, bit for bit - so
+ * prt_sample_lights, frames, prt_ray_color and accumulators follow.  Which meshes are lights does not change.
+ * Why it is cheap: the SHAPE of a mesh's light subtree depends only on its triangle count (every span is split at its
+ * middle), so a motion changes which triangle sits at which leaf and the areas; with one or two light meshes every
+ * resident light array keeps its size and layout (with three or more, the order of the meshes in the top of the tree
+ * follows the motion, and the tables' places with it: see "Layout exceptions").  The host does what defines the order - the Triangle precompute of the emitter triangles, the
+ * reference's two std::sort passes, areas and pdfs (a sort per tree level: n log^2 n on the emitter triangles) - and plans the tables; the device
+ * fills the thresholds and buckets and verifies them (the host's verification points; its random draws are replaced by a
+ * sub-stream per lane).
+ * Phases of a call.  No emitter vertex differs bitwise: the call is the one described above (one host synchronisation),
+ * except that its read-back also carries the emitters' new vertices: 72 bytes per EMITTER triangle (144 with normals) - it
+ * scales with the emitter triangles, not with the scene's.  One differs: at most TWO host synchronisations, that read-back
+ * and the verification flag (which brings the filled table words, 4 bytes each, for the host's copy); a scene whose
+ * lights have no table (no clean subtree of 16 or more light triangles) has only the first.  The refit's ordering rules apply to the
+ * light writes unchanged.
+ * All or nothing.  The scene keeps two device copies of the light arrays: the new nodes, records and tables are built
+ * and verified in the spare one while calls in flight read the resident one, and the two are exchanged in the call's
+ * writing phase.  A refusal (a non-finite coordinate anywhere, an allocation failure) leaves lights, frames and
+ * prt_scene_refit_info exactly as they were.
+ * Layout exceptions (PrtLightUpdateInfo.relaid = 1).  The plan of the new geometry differs from the resident layout - the
+ * meshes of a list of three or more changed places, or a subtree whose area gives no finite positive bucket width gets
+ * no table and its children are tried - or the device verification fails: then the scene keeps the full tree and no tables (tables_dropped = 1), as the host builder
+ * decides.  Either way larger arrays are made before anything is written and the render kernels are sized again
+ * (PrtBvhInfo.lds_light_nodes / lds_light_tris / render_variant may change).
+ * fp32 tables, if they exist, are re-derived (the small light tables on the host).  The host triangles of the EMITTERS are
+ * always updated (their vertices are on the host anyway); PrtRefitInfo.host_stale keeps its meaning for the rest.  The
+ * generation is bumped as for any refit.
+ * PRT_TEST_FAIL_LIGHT_VERIFY=1 (dev-hooks build) makes the device verification report a failure;
+ * PRT_TEST_FAIL_LIGHT_STAGE=k makes the k-th allocation (from 0) of a light update's spare arrays report PRT_E_OOM.
+ */
+int prt_scene_set_dynamic_lights(PrtScene* scene, int on); /* any time; survives prt_scene_upload / prt_scene_update_vertices */
+int prt_scene_get_dynamic_lights(const PrtScene* scene, int* on);
+
+typedef struct PrtLightUpdateInfo {
+    uint64_t updates;        /* light updates since the last upload (calls in which an emitter vertex differed) */
+    double gather_ms;        /* hipEvent: the first phase that gathers the emitters' new vertices, with its read-back */
+    double host_tree_ms;     /* wall: Triangle precompute of the emitter triangles + the sort replay + the plan, on the host */
+    double tables_ms;        /* hipEvent: thresholds + buckets + verification on the device, with the read-back of the words */
+    uint32_t n_tables, table_words; /* of the resident light state */
+    uint32_t tables_dropped; /* 1 if the last update's verification failed and the scene now descends the full tree */
+    uint32_t relaid;         /* 1 if the last update changed the layout */
+} PrtLightUpdateInfo;
+/* Synchronous, like prt_scene_refit_info (the times are of the last light update). */
+int prt_scene_light_update_info(const PrtScene* scene, PrtLightUpdateInfo* out);
+
+/* Test hook, beside prt_scene_light_order: the resident O(1) table words (DLightTable headers, thresholds, buckets), read
+ * back from the device (synchronous).  *n = word count (0: no tables); copies min(*n, cap) words.  PRT_E_NO_DEVICE unless
+ * the scene is uploaded. */
+int prt_scene_light_table_words(PrtScene* scene, uint32_t* words, uint64_t cap, uint64_t* n);
 
 /* Number of light triangles and their order in the reference's area-CDF descent (BVH.cpp:86-100). */
 int prt_scene_bvh_info(const PrtScene* scene, PrtBvhInfo* out);

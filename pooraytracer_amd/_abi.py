@@ -115,6 +115,19 @@ class PrtRefitInfo(C.Structure):
     ]
 
 
+class PrtLightUpdateInfo(C.Structure):
+    _fields_ = [
+        ("updates", C.c_uint64),
+        ("gather_ms", C.c_double),
+        ("host_tree_ms", C.c_double),
+        ("tables_ms", C.c_double),
+        ("n_tables", C.c_uint32),
+        ("table_words", C.c_uint32),
+        ("tables_dropped", C.c_uint32),
+        ("relaid", C.c_uint32),
+    ]
+
+
 # PrtBvhInfo.render_variant, per precision byte (prt.h PRT_VARIANT_*)
 VARIANT_PERM_MASK, VARIANT_LLDS, VARIANT_PAD, VARIANT_EXTRA, VARIANT_VALID = 0x07, 0x08, 0x10, 0x20, 0x80
 
@@ -269,6 +282,10 @@ EXPORTS = [
     "prt_scene_refit_info",
     "prt_scene_rebuild",
     "prt_scene_rebuild_device",
+    "prt_scene_set_dynamic_lights",
+    "prt_scene_get_dynamic_lights",
+    "prt_scene_light_update_info",
+    "prt_scene_light_table_words",
     "prt_scene_bvh_info",
     "prt_scene_light_count",
     "prt_scene_light_order",

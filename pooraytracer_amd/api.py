@@ -58,6 +58,10 @@ def load():
     L.prt_scene_refit_info.argtypes = [vp, vp]
     L.prt_scene_rebuild.argtypes = [vp, vp, vp]
     L.prt_scene_rebuild_device.argtypes = [vp, vp, vp, vp]
+    L.prt_scene_set_dynamic_lights.argtypes = [vp, i32]
+    L.prt_scene_get_dynamic_lights.argtypes = [vp, C.POINTER(C.c_int)]
+    L.prt_scene_light_update_info.argtypes = [vp, vp]
+    L.prt_scene_light_table_words.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
     L.prt_trace_closest.argtypes = [vp, vp, sz, vp, i32]
@@ -256,7 +260,8 @@ class Scene:
 
     def refit(self, vertices, normals=None):
         """New positions for the same triangles of an uploaded scene, in place: the records and the BVH's boxes follow on the
-        GPU, the tree keeps its topology and nothing is reloaded (prt_scene_refit).  Emitters must stay where they are."""
+        GPU, the tree keeps its topology and nothing is reloaded (prt_scene_refit).  Emitters must stay where they are unless
+        `dynamic_lights` is on."""
         return self._positions_call(self._L.prt_scene_refit, "refit", vertices, normals)
 
     def refit_device(self, d_vertices_ptr, d_normals_ptr=None, stream=None):
@@ -268,7 +273,7 @@ class Scene:
     def rebuild(self, vertices, normals=None):
         """New positions as for refit(), and a NEW tree of them from the device builder (prt_scene_rebuild): what a refitted
         tree has lost (refit_info()["sah_ratio"]) comes back, while textures, materials and light tables stay resident.
-        Synchronous.  Emitters must stay where they are."""
+        Synchronous.  Emitters must stay where they are unless `dynamic_lights` is on."""
         return self._positions_call(self._L.prt_scene_rebuild, "rebuild", vertices, normals)
 
     def rebuild_device(self, d_vertices_ptr, d_normals_ptr=None, stream=None):
@@ -294,6 +299,33 @@ class Scene:
         _check(self._L.prt_scene_light_count(self._h, C.byref(n)), self._L)
         out = np.zeros(n.value, dtype=np.int32)
         _check(self._L.prt_scene_light_order(self._h, out.ctypes.data, n.value), self._L)
+        return out
+
+    @property
+    def dynamic_lights(self):
+        """Whether refit* / rebuild* accept a moved emitter (prt_scene_set_dynamic_lights): off by default; on, the light
+        tree, its records and its O(1) tables follow the new positions on the device."""
+        on = C.c_int(0)
+        _check(self._L.prt_scene_get_dynamic_lights(self._h, C.byref(on)), self._L)
+        return bool(on.value)
+
+    @dynamic_lights.setter
+    def dynamic_lights(self, on):
+        _check(self._L.prt_scene_set_dynamic_lights(self._h, int(bool(on))), self._L)
+
+    def light_update_info(self):
+        """PrtLightUpdateInfo as a dict: light updates since the upload, the last one's times and outcome (synchronous)."""
+        b = _abi.PrtLightUpdateInfo()
+        _check(self._L.prt_scene_light_update_info(self._h, C.byref(b)), self._L)
+        return {f: getattr(b, f) for f, _ in _abi.PrtLightUpdateInfo._fields_}
+
+    def light_table_words(self):
+        """The resident O(1) light-table words as a uint32 array, read back from the device (empty: no tables)."""
+        n = C.c_uint64(0)
+        _check(self._L.prt_scene_light_table_words(self._h, None, 0, C.byref(n)), self._L)
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            _check(self._L.prt_scene_light_table_words(self._h, out.ctypes.data, n.value, C.byref(n)), self._L)
         return out
 
     def trace_closest(self, rays, count_work=False):

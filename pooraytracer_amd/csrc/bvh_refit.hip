@@ -116,7 +116,8 @@ __device__ inline void block_bounds(double r[7]) {
 
 __global__ void __launch_bounds__(kBlock) k_refit_check(const double* __restrict__ verts, uint32_t n,
                                                         const DLightTriT<double>* __restrict__ ltris, uint32_t n_lights,
-                                                        RefitCheck* __restrict__ partial) {
+                                                        RefitCheck* __restrict__ partial, const double* __restrict__ normals,
+                                                        double* __restrict__ gather_v, double* __restrict__ gather_n) {
     const double inf = INFINITY;
     double r[7] = {inf, inf, inf, -inf, -inf, -inf, 1.0};
     uint32_t flags = 0;
@@ -136,7 +137,10 @@ __global__ void __launch_bounds__(kBlock) k_refit_check(const double* __restrict
             r[6] = fmax(r[6], fmax(fabs(lo), fabs(hi)));
         }
     }
-    // emitters stay where they are: every light triangle still has the vertices it was uploaded with, bit for bit
+    // emitters in place: does every light triangle still have the vertices it was uploaded with, bit for bit?  (Without
+    // prt_scene_set_dynamic_lights a moved one refuses the call; with it, the new vertices - and vertex normals - of every
+    // light triangle are gathered here, in resident CDF order, for the host's light tree: k_light_gather, folded into this
+    // loop, which reads these 72 bytes anyway.)
     for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n_lights; l += stride) {
         const DLightTriT<double>& L = ltris[l];
         const uint32_t prim = (uint32_t)L.prim;
@@ -145,6 +149,10 @@ __global__ void __launch_bounds__(kBlock) k_refit_check(const double* __restrict
             continue;
         }
         const unsigned long long* nv = reinterpret_cast<const unsigned long long*>(verts + (size_t)prim * 9);
+        if (gather_v)
+            for (int k = 0; k < 9; ++k) gather_v[(size_t)l * 9 + k] = verts[(size_t)prim * 9 + k];
+        if (gather_n)
+            for (int k = 0; k < 9; ++k) gather_n[(size_t)l * 9 + k] = normals[(size_t)prim * 9 + k];
         for (int k = 0; k < 3; ++k)
             if (nv[k] != (unsigned long long)__double_as_longlong(L.v0[k]) || nv[3 + k] != (unsigned long long)__double_as_longlong(L.v1[k]) ||
                 nv[6 + k] != (unsigned long long)__double_as_longlong(L.v2[k]))
@@ -473,10 +481,13 @@ inline unsigned blocks_for(uint64_t items) { return (unsigned)std::max<uint64_t>
 // bytes of the reductions' partials (one buffer serves both)
 size_t refit_scratch_bytes() { return (size_t)kMaxBlocks * sizeof(RefitCheck); }
 
+// d_gather_v / d_gather_n: null, or room for 9 doubles per light triangle (the new vertices; the new vertex normals, only
+// with d_normals): filled in the order of d_ltris
 void launch_refit_check(const double* d_verts, uint32_t n, const DLightTriT<double>* d_ltris, uint32_t n_lights, void* d_scratch,
-                        RefitCheck* d_out, hipStream_t st) {
+                        RefitCheck* d_out, hipStream_t st, const double* d_normals, double* d_gather_v, double* d_gather_n) {
     const unsigned nb = std::min(kMaxBlocks, blocks_for(std::max(n, n_lights)));
-    k_refit_check<<<nb, kBlock, 0, st>>>(d_verts, n, d_ltris, n_lights, static_cast<RefitCheck*>(d_scratch));
+    k_refit_check<<<nb, kBlock, 0, st>>>(d_verts, n, d_ltris, n_lights, static_cast<RefitCheck*>(d_scratch), d_normals, d_gather_v,
+                                         d_normals ? d_gather_n : nullptr);
     k_refit_check_final<<<1, kBlock, 0, st>>>(static_cast<const RefitCheck*>(d_scratch), nb, d_out);
 }
 

@@ -74,8 +74,10 @@ struct RefitCheck {
     uint32_t flags, pad_;
 };
 size_t refit_scratch_bytes();
+// light_tables.hip: thresholds, buckets and verification of the planned tables of a light update
+hipError_t launch_light_tables(const DLightTableBuild& A, hipStream_t st);
 void launch_refit_check(const double* d_verts, uint32_t n, const DLightTriT<double>* d_ltris, uint32_t n_lights, void* d_scratch,
-                        RefitCheck* d_out, hipStream_t st);
+                        RefitCheck* d_out, hipStream_t st, const double* d_normals, double* d_gather_v, double* d_gather_n);
 void launch_refit_tris(const double* d_verts, const double* d_normals, const uint32_t* d_order, uint32_t n, void* d_tris,
                        uint32_t tri_stride, DTriShadeT<double>* d_shade, float* d_tbox, const double origin[3], double delta,
                        hipStream_t st);
@@ -282,6 +284,39 @@ struct PrtScene {
     bool host_stale = false; // prt_scene_refit_device moved the geometry past the host triangles
     Event feat_done;         // behind the last prt_render_features* kernel (it uses no call slot): a refit waits for it
     bool feat_pending = false;
+    // prt_scene_set_dynamic_lights: an emitter may move under a refit or a rebuild, and the light tree, its records and its
+    // O(1) tables follow.  The scene then keeps TWO device copies of the light arrays: the resident one (what k64.d / k32.d
+    // point to) and a spare one, which a light update fills and verifies while calls in flight still read the resident
+    // one; the writing phase swaps them.  (The spare's last readers were issued before the previous swap, and that update's
+    // writing phase waited for them: a new update, which waits for the previous one, finds the spare free.)
+    bool dynamic_lights = false; // survives upload / update_vertices
+    struct LightArrays {         // capacities in elements (words for tab); every array is owned by `allocs`
+        void *nodes = nullptr, *tris = nullptr, *tab = nullptr, *nodes32 = nullptr, *tris32 = nullptr;
+        size_t cap_nodes = 0, cap_tris = 0, cap_tab = 0, cap_nodes32 = 0, cap_tris32 = 0;
+    };
+    LightArrays light_res, light_spare;
+    struct LightUpdate {
+        double* d_gather = nullptr;    // per light triangle, resident CDF order: 9 doubles of new vertices, then (second half) of vertex normals
+        std::vector<double> h_gather;  // ... read back with the refit's decision
+        Scratch tmp;                   // flag word, the full tree, per-table subtree roots and areas: inputs of the device fill
+        prt::LightTree next;           // the tree of the new positions, resident after the swap
+        prt::LightTablePlan plan;
+        std::vector<uint32_t> words;   // the filled tables, read back with the verification flag
+        uint32_t flag = 0;
+        std::vector<DLightNodeT<float>> ln32;
+        std::vector<DLightTriT<float>> lt32;
+        std::vector<int32_t> prims;        // the emitter triangles and their host records before the update (a refusal or a
+        std::vector<prt::HostTri> saved;   // failure before the swap puts them back)
+        bool staged = false;               // the spare holds a verified copy for `next`, waiting for the swap
+        bool staged_relaid = false, staged_dropped = false, staged_tables = false;
+        Event g0, g1, t0, t1;              // timed: the gather (the refit's first phase), the table fill + verification
+        bool tables_timed = false;
+        uint64_t count = 0;                // light updates since the upload
+        double host_tree_ms = 0.0, gather_ms = 0.0;            // of the last light update (taken over at the swap)
+        double staged_host_tree_ms = 0.0, staged_gather_ms = 0.0; // of the update being staged
+        int fail_alloc_at = -1, n_allocs = 0; // test hook (PRT_TEST_FAIL_LIGHT_STAGE=k): the k-th allocation of a staging reports out-of-memory
+        uint32_t tables_dropped = 0, relaid = 0;
+    } lu;
     // Every call that reads the geometry first waits, on its stream, for the last refit's end.
     hipError_t after_refit(hipStream_t st) const {
         return refit.pending ? hipStreamWaitEvent(st, refit.done.get(), 0) : hipSuccess;
@@ -389,6 +424,8 @@ struct PrtScene {
         allocs.clear();
         d_order = nullptr;
         refit = Refit();
+        light_res = light_spare = LightArrays();
+        lu = LightUpdate();
         refit_in = Scratch();
         multi_fb = Scratch();
         sort = Scratch();
@@ -976,6 +1013,12 @@ static int upload_impl(PrtScene* s, int device) {
     d.light_tab = nullptr;
     if (!s->lights.tab.empty() && (rc = s->up(s->lights.tab, &d.light_tab))) return rc;
     if ((rc = s->up(s->lights.tris, &d.light_tris))) return rc;
+    s->light_res.nodes = const_cast<DLightNode*>(d.light_nodes);
+    s->light_res.tris = const_cast<DLightTri*>(d.light_tris);
+    s->light_res.tab = const_cast<uint32_t*>(d.light_tab);
+    s->light_res.cap_nodes = s->lights.nodes.size();
+    s->light_res.cap_tris = s->lights.tris.size();
+    s->light_res.cap_tab = s->lights.tab.size();
     d.light_root = s->lights.root;
     d.n_lights = (int32_t)s->lights.tris.size();
     d.light_area = s->lights.area;
@@ -1037,6 +1080,18 @@ static int upload_impl(PrtScene* s, int device) {
     return PRT_OK;
 }
 
+// The part of a scene description build_light_tree reads, from what the scene kept of it.
+static void light_desc(const PrtScene* s, PrtSceneDesc& d) {
+    std::memset(&d, 0, sizeof(d));
+    d.n_tris = s->tris.size();
+    d.n_meshes = (uint32_t)s->mesh_mat.size();
+    d.mesh_first_tri = s->mesh_first.data();
+    d.mesh_material = s->mesh_mat.data();
+    static const int32_t none = 0;
+    d.light_meshes = s->explicit_lights ? (s->light_meshes.empty() ? &none : s->light_meshes.data()) : nullptr;
+    d.n_light_meshes = (uint32_t)s->light_meshes.size();
+}
+
 int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double* normals) {
     if (!s || (!vertices && !s->tris.empty())) return fail(PRT_E_INVALID, "prt_scene_update_vertices: null argument");
     for (size_t i = 0; i < s->tris.size() * 9; ++i)
@@ -1046,14 +1101,7 @@ int prt_scene_update_vertices(PrtScene* s, const double* vertices, const double*
         prt::update_triangles(vertices, normals, s->tris);
         s->host_stale = false; // every host position has been replaced
         PrtSceneDesc d;
-        std::memset(&d, 0, sizeof(d));
-        d.n_tris = s->tris.size();
-        d.n_meshes = (uint32_t)s->mesh_mat.size();
-        d.mesh_first_tri = s->mesh_first.data();
-        d.mesh_material = s->mesh_mat.data();
-        static const int32_t none = 0;
-        d.light_meshes = s->explicit_lights ? (s->light_meshes.empty() ? &none : s->light_meshes.data()) : nullptr;
-        d.n_light_meshes = (uint32_t)s->light_meshes.size();
+        light_desc(s, d);
         s->lights = prt::LightTree();
         prt::build_light_tree(d, s->tris, s->mats, s->lights); // light areas and the CDF order follow the geometry
         if (s->device >= 0 && s->tris.size() >= 2) {
@@ -1088,6 +1136,24 @@ static int f32_stack_depth(int need) {
     if (const char* e = dev_env("PRT_TUNE_STACK32")) depth = std::max(need, std::min(PRT_STACK_DEPTH, std::atoi(e))); // developer: smaller stacks when the tree allows
     return depth;
 }
+// The float copies of the light tree's nodes and of the light triangles (the small light tables are converted on the host).
+static void light_tables_f32(const prt::LightTree& lights, std::vector<DLightNodeT<float>>& ln, std::vector<DLightTriT<float>>& lt) {
+    ln.resize(lights.nodes.size());
+    for (size_t i = 0; i < ln.size(); ++i) {
+        std::memset(&ln[i], 0, sizeof(ln[i]));
+        ln[i].left_area = (float)lights.nodes[i].left_area;
+        ln[i].left = lights.nodes[i].left;
+        ln[i].right = lights.nodes[i].right;
+    }
+    lt.resize(lights.tris.size());
+    for (size_t i = 0; i < lt.size(); ++i) {
+        const DLightTri& a = lights.tris[i];
+        DLightTriT<float>& o = lt[i];
+        std::memset(&o, 0, sizeof(o));
+        conv_arr(o.v0, a.v0, 3); conv_arr(o.v1, a.v1, 3); conv_arr(o.v2, a.v2, 3); conv_arr(o.n, a.n, 3);
+        o.area = (float)a.area; o.material = a.material; o.prim = a.prim; o.pdf = (float)a.pdf;
+    }
+}
 // All or nothing, like the upload: a failure frees what this call allocated and leaves the scene without fp32 tables.
 static int ensure_f32(PrtScene* s) {
     if (s->f32_ready) return PRT_OK;
@@ -1097,6 +1163,8 @@ static int ensure_f32(PrtScene* s) {
         const std::string keep = g_err;
         s->allocs.resize(mark);
         s->k32 = KernelConfig<float>();
+        s->light_res.nodes32 = s->light_res.tris32 = nullptr;
+        s->light_res.cap_nodes32 = s->light_res.cap_tris32 = 0;
         g_err = keep;
     }
     return rc;
@@ -1131,24 +1199,16 @@ static int ensure_f32_impl(PrtScene* s) {
         o.has_emission = a.has_emission; o.skip_light_sampling = a.skip_light_sampling;
         o.inv_ns1 = (float)a.inv_ns1; o.spec_scale = (float)a.spec_scale;
     }
-    std::vector<DLightNodeT<float>> ln(s->lights.nodes.size());
-    for (size_t i = 0; i < ln.size(); ++i) {
-        std::memset(&ln[i], 0, sizeof(ln[i]));
-        ln[i].left_area = (float)s->lights.nodes[i].left_area;
-        ln[i].left = s->lights.nodes[i].left;
-        ln[i].right = s->lights.nodes[i].right;
-    }
-    std::vector<DLightTriT<float>> lt(s->lights.tris.size());
-    for (size_t i = 0; i < lt.size(); ++i) {
-        const DLightTri& a = s->lights.tris[i];
-        DLightTriT<float>& o = lt[i];
-        std::memset(&o, 0, sizeof(o));
-        conv_arr(o.v0, a.v0, 3); conv_arr(o.v1, a.v1, 3); conv_arr(o.v2, a.v2, 3); conv_arr(o.n, a.n, 3);
-        o.area = (float)a.area; o.material = a.material; o.prim = a.prim; o.pdf = (float)a.pdf;
-    }
+    std::vector<DLightNodeT<float>> ln;
+    std::vector<DLightTriT<float>> lt;
+    light_tables_f32(s->lights, ln, lt);
     // (these uploads do not count for PRT_TEST_FAIL_UPLOAD, which injects failures into prt_scene_upload)
     if ((rc = s->up(mats, &f.materials, false)) || (rc = s->up(ln, &f.light_nodes, false)) || (rc = s->up(lt, &f.light_tris, false)))
         return rc;
+    s->light_res.nodes32 = const_cast<DLightNodeT<float>*>(f.light_nodes);
+    s->light_res.tris32 = const_cast<DLightTriT<float>*>(f.light_tris);
+    s->light_res.cap_nodes32 = ln.size();
+    s->light_res.cap_tris32 = lt.size();
     PRT_HIP(hipDeviceSynchronize());
     f.nodes = d.nodes;
     f.tris = static_cast<const DTriT<float>*>(t);
@@ -1267,7 +1327,10 @@ struct RefitGridHost {
 
 // What a refit and a rebuild share up to the decision.  after_refit, the working arrays (refit_prepare; a failure frees what
 // this call made), then phase 1, read-only: vertex range, scene bounds, emitters in place; the one read-back; the grid.
-static int refit_begin(PrtScene* s, const std::string& who, const double* d_verts, hipStream_t st, RefitGridHost& g) {
+// *lights_moved: an emitter vertex differs and the scene accepts that (prt_scene_set_dynamic_lights): the gathered new
+// vertices (and vertex normals, with d_normals) of the light triangles are in s->lu.h_gather.
+static int refit_begin(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st,
+                       RefitGridHost& g, bool* lights_moved) {
     DScene& d = s->k64.d;
     const uint32_t n = d.n_tris;
     PrtScene::Refit& R = s->refit;
@@ -1291,17 +1354,44 @@ static int refit_begin(PrtScene* s, const std::string& who, const double* d_vert
             return rc;
         }
     }
-    prt::launch_refit_check(d_verts, n, d.light_tris, (uint32_t)d.n_lights, R.d_scratch, R.d_check, st);
+    *lights_moved = false;
+    PrtScene::LightUpdate& U = s->lu;
+    const size_t nl = (size_t)d.n_lights;
+    const bool gather = s->dynamic_lights && nl > 0;
+    if (gather && !U.d_gather) { // (72 bytes per light triangle for the vertices and as much for the normals, kept for the upload's life)
+        PRT_HIP_AS(who, make_event(U.g0, hipEventDefault));
+        PRT_HIP_AS(who, make_event(U.g1, hipEventDefault));
+        PRT_HIP_AS(who, make_event(U.t0, hipEventDefault));
+        PRT_HIP_AS(who, make_event(U.t1, hipEventDefault));
+        void* p = nullptr;
+        if (const int rc = s->alloc(nl * 18 * sizeof(double), &p)) return rc;
+        U.d_gather = static_cast<double*>(p);
+    }
+    if (gather) {
+        try {
+            U.h_gather.resize(nl * 18);
+        } catch (const std::bad_alloc&) {
+            return fail(PRT_E_OOM, who + ": out of host memory");
+        }
+        PRT_HIP_AS(who, hipEventRecord(U.g0.get(), st));
+    }
+    prt::launch_refit_check(d_verts, n, d.light_tris, (uint32_t)d.n_lights, R.d_scratch, R.d_check, st, d_normals,
+                            gather ? U.d_gather : nullptr, gather ? U.d_gather + nl * 9 : nullptr);
     PRT_HIP_AS(who, hipGetLastError());
     prt::RefitCheck c;
     PRT_HIP_AS(who, hipMemcpyAsync(&c, R.d_check, sizeof(c), hipMemcpyDeviceToHost, st));
+    if (gather) { // the same read-back brings the emitters' new vertices: it scales with the emitter triangles, not the scene's
+        PRT_HIP_AS(who, hipMemcpyAsync(U.h_gather.data(), U.d_gather, nl * (d_normals ? 18 : 9) * sizeof(double), hipMemcpyDeviceToHost, st));
+        PRT_HIP_AS(who, hipEventRecord(U.g1.get(), st));
+    }
     PRT_HIP_AS(who, hipEventRecord(R.done.get(), st)); // (the working arrays are in use until here, whatever the verdict)
     R.pending = true;
     PRT_HIP_AS(who, hipStreamSynchronize(st));
     if (c.flags & 1u) return fail(PRT_E_INVALID, who + ": vertex coordinate is not finite (or beyond 1e18)");
-    if (c.flags & 2u)
+    if ((c.flags & 2u) && !s->dynamic_lights)
         return fail(PRT_E_INVALID, who + ": a vertex of a light mesh moved; emitters stay in place under a refit (the light tree is not "
                                          "rebuilt) - use prt_scene_update_vertices");
+    *lights_moved = (c.flags & 2u) != 0;
     // the quantisation grid of the new bounds: prim_boxes' origin and margin, quant_grid's steps.  The root box of the
     // builders is the union of the triangles' fp32 boxes; rounding and the subtraction are monotone, so its upper corner
     // is the box rule applied to the upper corner of the bounds.
@@ -1316,6 +1406,192 @@ static int refit_begin(PrtScene* s, const std::string& who, const double* d_vert
     float rel0[3];
     prt::quant_grid(zero, g.root_hi, false, rel0, g.step);
     return PRT_OK;
+}
+
+// ---- a moved emitter (prt_scene_set_dynamic_lights): the light tree of the new positions, built into the spare arrays
+// One array of the spare copy with room for `need` elements (a larger one replaces it: hipFree waits for the device).
+static int light_grow(PrtScene* s, void*& p, size_t& cap, size_t need, size_t elem) {
+    if (p && cap >= need) return PRT_OK;
+    if (s->lu.n_allocs++ == s->lu.fail_alloc_at) return fail(PRT_E_OOM, "light update: injected allocation failure (PRT_TEST_FAIL_LIGHT_STAGE)");
+    (void)s->take(p); // (freed here)
+    p = nullptr;
+    cap = 0;
+    if (const int rc = s->alloc(need * elem, &p)) return rc;
+    cap = need;
+    return PRT_OK;
+}
+
+// Puts the emitter triangles' host records back (a refusal or a failure between light_stage and light_commit).
+static void light_unstage(PrtScene* s) {
+    PrtScene::LightUpdate& U = s->lu;
+    if (!U.staged) return;
+    for (size_t l = U.prims.size(); l-- > 0;) s->tris[(size_t)U.prims[l]] = U.saved[l];
+    U.staged = false;
+}
+
+// Between the decision and the writing phase.  Host: the Triangle precompute of the emitter triangles from the gathered
+// vertices, the reference's sort replay and flattening (build_light_tree), the plan of the tables.  Device, on `st`: the
+// new nodes, records and table headers go into the SPARE arrays, light_tables.hip fills and verifies the tables there, and
+// the flag comes back with the filled words (the call's second and last host synchronisation; none without tables).
+// Nothing resident is written: a failure leaves the scene as it was.  On success the spare holds what a fresh scene of
+// the new vertices has, and light_commit swaps it in.
+static int light_stage(PrtScene* s, const std::string& who, bool normals, hipStream_t st) {
+    PrtScene::LightUpdate& U = s->lu;
+    const size_t nl = s->lights.tris.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    bool tables = false;
+    try {
+        U.prims.resize(nl);
+        U.saved.resize(nl);
+        for (size_t l = 0; l < nl; ++l) {
+            U.prims[l] = s->lights.tris[l].prim;
+            U.saved[l] = s->tris[(size_t)U.prims[l]];
+        }
+        U.staged = true; // (from here on a failure puts the host records back)
+        prt::update_triangles_listed(U.prims.data(), nl, U.h_gather.data(), normals ? U.h_gather.data() + nl * 9 : nullptr, s->tris);
+        PrtSceneDesc ld;
+        light_desc(s, ld);
+        U.next = prt::LightTree();
+        prt::build_light_tree(ld, s->tris, s->mats, U.next, false);
+        tables = prt::plan_light_tables(U.next, U.plan);
+        if (tables) U.words.assign(U.plan.tab.size(), 0u);
+    } catch (const std::bad_alloc&) {
+        light_unstage(s);
+        return fail(PRT_E_OOM, who + ": out of host memory");
+    }
+    U.staged_host_tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    U.n_allocs = 0;
+    U.fail_alloc_at = dev_env("PRT_TEST_FAIL_LIGHT_STAGE") ? std::atoi(dev_env("PRT_TEST_FAIL_LIGHT_STAGE")) : -1;
+    {
+        float ms = 0.f; // (the first phase has completed: the decision's read-back waited for it)
+        U.staged_gather_ms = hipEventElapsedTime(&ms, U.g0.get(), U.g1.get()) == hipSuccess ? ms : 0.0;
+    }
+    auto failed = [&](int rc) {
+        const std::string keep = g_err;
+        light_unstage(s);
+        g_err = keep;
+        return rc;
+    };
+    if (U.next.tris.size() != nl) return failed(fail(PRT_E_INVALID, who + ": the set of light triangles changed"));
+    PrtScene::LightArrays& A = s->light_spare;
+    const size_t n_full = U.next.full_nodes.size(), n_words = tables ? U.plan.tab.size() : 0, n_tab = tables ? U.plan.node.size() : 0;
+    int rc;
+    // (the node array has room for the full tree: what the scene descends if the verification fails)
+    if ((rc = light_grow(s, A.nodes, A.cap_nodes, n_full, sizeof(DLightNode))) || (rc = light_grow(s, A.tris, A.cap_tris, nl, sizeof(DLightTri))) ||
+        (n_words && (rc = light_grow(s, A.tab, A.cap_tab, n_words, sizeof(uint32_t)))))
+        return failed(rc);
+    if (s->f32_ready && ((rc = light_grow(s, A.nodes32, A.cap_nodes32, n_full, sizeof(DLightNodeT<float>))) ||
+                         (rc = light_grow(s, A.tris32, A.cap_tris32, nl, sizeof(DLightTriT<float>)))))
+        return failed(rc);
+    const size_t off_full = 16, off_area = off_full + n_full * sizeof(DLightNode), off_node = off_area + n_tab * sizeof(double);
+    auto hip = [&](hipError_t e) { return e == hipSuccess ? PRT_OK : failed(hip_fail(who, e)); };
+    if ((rc = hip(U.tmp.reserve(off_node + n_tab * sizeof(int32_t), st)))) return rc;
+    char* const tmp = U.tmp.get<char>();
+    auto put = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+    const std::vector<DLightNode>& top = tables ? U.plan.top : U.next.full_nodes;
+    if ((rc = hip(put(A.nodes, top.data(), top.size() * sizeof(DLightNode)))) || (rc = hip(put(A.tris, U.next.tris.data(), nl * sizeof(DLightTri)))))
+        return rc;
+    bool dropped = false;
+    U.tables_timed = false;
+    if (tables) {
+        if ((rc = hip(put(tmp + off_full, U.next.full_nodes.data(), n_full * sizeof(DLightNode)))) ||
+            (rc = hip(put(tmp + off_area, U.plan.area.data(), n_tab * sizeof(double)))) ||
+            (rc = hip(put(tmp + off_node, U.plan.node.data(), n_tab * sizeof(int32_t)))) ||
+            (rc = hip(put(A.tab, U.plan.tab.data(), n_words * sizeof(uint32_t)))))
+            return rc;
+        DLightTableBuild B;
+        B.full = reinterpret_cast<const DLightNode*>(tmp + off_full);
+        B.top = static_cast<const DLightNode*>(A.nodes);
+        B.table_node = reinterpret_cast<const int32_t*>(tmp + off_node);
+        B.table_area = reinterpret_cast<const double*>(tmp + off_area);
+        B.tab = static_cast<uint32_t*>(A.tab);
+        B.flag = reinterpret_cast<uint32_t*>(tmp);
+        B.n_full = (uint32_t)n_full;
+        B.n_top = (uint32_t)top.size();
+        B.n_tables = (uint32_t)n_tab;
+        B.n_words = (uint32_t)n_words;
+        B.full_root = U.next.full_root;
+        B.root = U.plan.root;
+        B.total = (float)U.next.area;
+        if ((rc = hip(hipEventRecord(U.t0.get(), st))) || (rc = hip(prt::launch_light_tables(B, st))) ||
+            (rc = hip(hipMemcpyAsync(&U.flag, B.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st))) ||
+            (rc = hip(hipMemcpyAsync(U.words.data(), A.tab, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st))) ||
+            (rc = hip(hipEventRecord(U.t1.get(), st))) || (rc = hip(U.tmp.used(st))) || (rc = hip(hipStreamSynchronize(st))))
+            return rc;
+        U.tables_timed = true;
+        // test hook (PRT_TEST_FAIL_LIGHT_VERIFY=1, dev-hooks build): the device verification reports a failure
+        dropped = U.flag != 0 || (dev_env("PRT_TEST_FAIL_LIGHT_VERIFY") && std::atoi(dev_env("PRT_TEST_FAIL_LIGHT_VERIFY")));
+        if (dropped) { // the scene keeps the full tree and no tables, as the host builder decides
+            if ((rc = hip(put(A.nodes, U.next.full_nodes.data(), n_full * sizeof(DLightNode))))) return rc;
+        } else {
+            try {
+                prt::apply_light_tables(U.next, U.plan, U.words);
+            } catch (const std::bad_alloc&) {
+                return failed(fail(PRT_E_OOM, who + ": out of host memory"));
+            }
+        }
+    }
+    if (s->f32_ready) {
+        try {
+            light_tables_f32(U.next, U.ln32, U.lt32);
+        } catch (const std::bad_alloc&) {
+            return failed(fail(PRT_E_OOM, who + ": out of host memory"));
+        }
+        if ((rc = hip(put(A.nodes32, U.ln32.data(), U.ln32.size() * sizeof(DLightNodeT<float>)))) ||
+            (rc = hip(put(A.tris32, U.lt32.data(), U.lt32.size() * sizeof(DLightTriT<float>)))))
+            return rc;
+    }
+    // did the layout change?  (array sizes, the root, or any table's place: then the kernels are sized again)
+    const prt::LightTree& old = s->lights;
+    bool relaid = old.nodes.size() != U.next.nodes.size() || old.tab.size() != U.next.tab.size() || old.root != U.next.root ||
+                  old.n_tables != U.next.n_tables;
+    for (size_t t = 0; !relaid && t < U.next.n_tables; ++t)
+        relaid = std::memcmp(old.tab.data() + 8 * t, U.next.tab.data() + 8 * t, 5 * sizeof(uint32_t)) != 0; // first, n, thr_off, bkt_off, n_bkt
+    U.staged_relaid = relaid;
+    U.staged_dropped = dropped;
+    U.staged_tables = tables;
+    return PRT_OK;
+}
+
+// In the writing phase (the readers in flight have been waited for on the call's stream, the grid is committed): the
+// spare copy becomes the resident one, on the device by exchanging pointers and on the host by taking the new tree.
+static void light_commit(PrtScene* s) {
+    PrtScene::LightUpdate& U = s->lu;
+    if (!U.staged) return;
+    U.staged = false;
+    std::swap(s->light_res, s->light_spare);
+    const PrtScene::LightArrays& A = s->light_res;
+    s->lights = std::move(U.next);
+    U.next = prt::LightTree();
+    DScene& d = s->k64.d;
+    d.light_nodes = static_cast<const DLightNode*>(A.nodes);
+    d.light_tris = static_cast<const DLightTri*>(A.tris);
+    d.light_tab = s->lights.tab.empty() ? nullptr : static_cast<const uint32_t*>(A.tab);
+    d.light_root = s->lights.root;
+    d.n_lights = (int32_t)s->lights.tris.size();
+    d.light_area = s->lights.area;
+    if (s->f32_ready) {
+        DSceneT<float>& f = s->k32.d;
+        f.light_nodes = static_cast<const DLightNodeT<float>*>(A.nodes32);
+        f.light_tris = static_cast<const DLightTriT<float>*>(A.tris32);
+        f.light_tab = d.light_tab;
+        f.light_root = d.light_root;
+        f.n_lights = d.n_lights;
+        f.light_area = (float)d.light_area;
+    }
+    ++U.count;
+    U.host_tree_ms = U.staged_host_tree_ms;
+    U.gather_ms = U.staged_gather_ms;
+    U.relaid = U.staged_relaid ? 1u : 0u;
+    U.tables_dropped = U.staged_dropped ? 1u : 0u;
+    if (U.staged_relaid) { // LDS sizing and render_variant may change (PRT_VARIANT_EXTRA depends on the tables' presence)
+        s->k64.blocks_per_cu_rays = 0;
+        s->blocks_wanted = size_kernels(s, s->k64, true);
+        if (s->f32_ready) {
+            s->k32.blocks_per_cu_rays = 0;
+            size_kernels(s, s->k32, false);
+        }
+    }
 }
 
 // The writing phase changes what calls in flight read: `st` waits for both call slots and the last features call first.
@@ -1361,9 +1637,16 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
     PrtScene::Refit& R = s->refit;
     RefitGridHost g;
-    if (const int rc = refit_begin(s, who, d_verts, st, g)) return rc;
+    bool lights_moved = false;
+    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g, &lights_moved)) return rc;
     const float *origin = g.origin, *step = g.step;
-    if (const int rc = refit_wait_readers(s, who, st)) return rc;
+    if (lights_moved)
+        if (const int rc = light_stage(s, who, d_normals != nullptr, st)) return rc;
+    if (const int rc = refit_wait_readers(s, who, st)) {
+        light_unstage(s);
+        return rc;
+    }
+    light_commit(s);
     {
         float cs = std::max(g.root_hi[0], std::max(g.root_hi[1], g.root_hi[2]));
         if (s->bvh_info.built_on_device) // (the device builder also covers the grid's far corner)
@@ -1412,7 +1695,8 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
     PrtScene::Refit& R = s->refit;
     RefitGridHost g;
-    if (const int rc = refit_begin(s, who, d_verts, st, g)) return rc;
+    bool lights_moved = false;
+    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g, &lights_moved)) return rc;
     // Everything the new tree needs is made before anything resident is written: a failure up to the commit below frees
     // what this call made (the owners are locals) and leaves the scene as it was.
     // test hook (PRT_TEST_FAIL_REBUILD=k): the k-th allocation of the rebuild, the builder run counting as one, reports out-of-memory
@@ -1451,7 +1735,12 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
             return fail(PRT_E_OOM, who + ": out of host memory");
         }
     }
-    if ((rc = refit_wait_readers(s, who, st))) return rc;
+    if (lights_moved && (rc = light_stage(s, who, d_normals != nullptr, st))) return rc; // (the last thing that can refuse)
+    if ((rc = refit_wait_readers(s, who, st))) {
+        light_unstage(s);
+        return rc;
+    }
+    light_commit(s); // (before the kernels are sized below)
 
     // Commit.  From here on the refit's wording applies: the generation and the grid are the new ones.  The scene takes
     // the new arrays at once; the ones they replace stay alive in `old` until this call returns (freeing waits for the device).
@@ -1592,6 +1881,54 @@ int prt_scene_refit_info(const PrtScene* s, PrtRefitInfo* out) {
         double sah[2] = {0, 0};
         PRT_HIP(hipMemcpy(sah, R.d_sah, sizeof(sah), hipMemcpyDeviceToHost));
         out->sah_ratio = sah[0] > 0.0 ? sah[1] / sah[0] : 1.0;
+    }
+    return PRT_OK;
+}
+
+int prt_scene_set_dynamic_lights(PrtScene* s, int on) {
+    if (!s) return fail(PRT_E_INVALID, "prt_scene_set_dynamic_lights: null scene");
+    s->dynamic_lights = on != 0;
+    return PRT_OK;
+}
+
+int prt_scene_get_dynamic_lights(const PrtScene* s, int* on) {
+    if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_dynamic_lights: null argument");
+    *on = s->dynamic_lights ? 1 : 0;
+    return PRT_OK;
+}
+
+int prt_scene_light_update_info(const PrtScene* s, PrtLightUpdateInfo* out) {
+    if (!s || !out) return fail(PRT_E_INVALID, "prt_scene_light_update_info: null argument");
+    std::memset(out, 0, sizeof(*out));
+    const PrtScene::LightUpdate& U = s->lu;
+    out->updates = U.count;
+    out->host_tree_ms = U.host_tree_ms;
+    out->gather_ms = U.gather_ms;
+    out->n_tables = s->lights.n_tables;
+    out->table_words = (uint32_t)s->lights.tab.size();
+    out->tables_dropped = U.tables_dropped;
+    out->relaid = U.relaid;
+    if (s->device >= 0 && U.count) {
+        PRT_HIP(hipSetDevice(s->device));
+        float ms = 0.f;
+        if (U.tables_timed) {
+            PRT_HIP(hipEventSynchronize(U.t1.get()));
+            PRT_HIP(hipEventElapsedTime(&ms, U.t0.get(), U.t1.get()));
+            out->tables_ms = ms;
+        }
+    }
+    return PRT_OK;
+}
+
+int prt_scene_light_table_words(PrtScene* s, uint32_t* words, uint64_t cap, uint64_t* n) {
+    if (int rc = require_uploaded(s, "prt_scene_light_table_words")) return rc;
+    if (!n || (!words && cap)) return fail(PRT_E_INVALID, "prt_scene_light_table_words: null argument");
+    const DScene& d = s->k64.d;
+    *n = d.light_tab ? s->lights.tab.size() : 0;
+    const size_t k = (size_t)std::min<uint64_t>(*n, cap);
+    if (k) {
+        PRT_HIP(s->after_refit(nullptr)); // a light update on another stream may still be filling them
+        PRT_HIP(hipMemcpy(words, d.light_tab, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return PRT_OK;
 }

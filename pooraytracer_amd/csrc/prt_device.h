@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "prt_types.h"
+#include "prt_light_pick.h"
 
 #define PRT_DEV __device__ __forceinline__
 // The scalar type of everything that is a real number in the reference (glm::dvec3 arithmetic): double, or float in the
@@ -958,19 +959,8 @@ PRT_DEV LightPick sample_lights(const DScene& S, d3 origin, Rng& rng, const DLig
     if (LTAB && node >= 0) {
         // A subtree on which the descent is a monotone step function of p (prt_types.h, DLightTable): one bucket read gives
         // the first leaf p can reach and the threshold of the next one; thresholds were found by bisection through this
-        // very descent, so the pick is the descent's bit for bit.
-        const uint4* h = reinterpret_cast<const uint4*>(S.light_tab + 8u * ((uint32_t)node & ~(uint32_t)PRT_LIGHT_TABLE_BIT));
-        const uint4 h0 = h[0];                                   // first, n, thr_off, bkt_off
-        const uint2 h1 = *reinterpret_cast<const uint2*>(h + 1); // n_bkt, inv_w
-        const uint32_t k = (uint32_t)fminf(pf * __uint_as_float(h1.y), (float)(h1.x - 1u));
-        const uint2 e = *reinterpret_cast<const uint2*>(S.light_tab + h0.w + 2u * k);
-        uint32_t i = e.x;
-        float next = __uint_as_float(e.y);
-        while (next <= pf) {
-            ++i;
-            next = __uint_as_float(S.light_tab[h0.z + i + 1u]);
-        }
-        node = ~(int32_t)(h0.x + i);
+        // very descent, so the pick is the descent's bit for bit.  (prt_light_pick.h: the lookup a light update verifies.)
+        node = ~light_table_leaf<false>(S.light_tab, (uint32_t)node & ~(uint32_t)PRT_LIGHT_TABLE_BIT, pf);
     }
     LightPick lp;
     lp.tri = ~node;

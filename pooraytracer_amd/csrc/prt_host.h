@@ -68,6 +68,19 @@ struct LightTree {
     std::vector<DLightNode> full_nodes; // the full tree (tests, verification)
     int32_t full_root = -1;
 };
+// The O(1) tables as planned (scene_setup.cpp, plan_light_tables): every header with its final offsets, and room for the
+// thresholds and buckets, which a fill writes: the host's (create, update_vertices) or the device's (light_tables.hip).
+struct LightTablePlan {
+    std::vector<uint32_t> tab;   // DLightTable headers, then zeroed thresholds / buckets
+    std::vector<int32_t> node;   // per table: the root of its subtree in LightTree::full_nodes
+    std::vector<double> area;    // per table: that subtree's area as the reference sums it
+    std::vector<DLightNode> top; // the part of the tree above the tables, breadth-first
+    int32_t root = -1;           // the root as the kernels get it (a node of `top`, or a table ref)
+};
+// Plans the tables of a tree that holds the full tree and no tables yet; false: no subtree gets one.  Runs no descent.
+bool plan_light_tables(const LightTree& lt, LightTablePlan& plan);
+// A planned, filled and verified set of tables becomes the tree's: nodes = the top part, tab = the words.
+void apply_light_tables(LightTree& lt, const LightTablePlan& plan, const std::vector<uint32_t>& tab);
 // Host twin of the kernels' light pick (prt_device.h, sample_lights): leaf (CDF index) reached by the float p.
 int32_t light_pick(const LightTree& lt, float p);
 int32_t light_pick_full_tree(const LightTree& lt, float p);
@@ -76,6 +89,8 @@ int32_t light_pick_full_tree(const LightTree& lt, float p);
 void setup_triangles(const PrtSceneDesc& d, std::vector<HostTri>& out);
 // Re-runs the Triangle constructor for new vertex positions (topology, materials, uv unchanged).
 void update_triangles(const double* vertices, const double* normals, std::vector<HostTri>& tris);
+// ... for the triangles prims[0..n) only: vertices / normals (may be null) hold 9 doubles per listed triangle.
+void update_triangles_listed(const int32_t* prims, size_t n, const double* vertices, const double* normals, std::vector<HostTri>& tris);
 // Material table incl. SetProbabilitiesByNs / HasEmission / SkipLightSampling (Material.h).
 void setup_materials(const PrtSceneDesc& d, std::vector<DMaterial>& out);
 // Binned-SAH BVH2, depth-bounded to PRT_STACK_DEPTH, child boxes rounded outward to fp32.
@@ -90,8 +105,9 @@ int tree_stack_need(const DNode* nodes, size_t n_nodes);
 bool build_bvh_device(const PrimBox* h_boxes, const float box_origin[3], size_t n, DeviceBVH& out, std::string* err);
 // The reference's lights object graph (main.cpp:36-45, BVH.cpp:7-48) reduced to what
 // BVHNode::Sample/TraverseSample read: per-node left area + children, leaves in CDF order.
+// with_tables = false: the full tree only (nodes == full_nodes, no tables): the caller plans and fills them.
 void build_light_tree(const PrtSceneDesc& d, const std::vector<HostTri>& tris, const std::vector<DMaterial>& mats,
-                      LightTree& out);
+                      LightTree& out, bool with_tables = true);
 // Camera::Initialize (Camera.cpp:75-106).
 void setup_camera(const PrtCamera& c, DCamera& out);
 

@@ -132,6 +132,19 @@ struct DLightTable {   // 32 bytes, at uint32 offset 8 * index of light_tab
 };
 static_assert(sizeof(DLightTable) == 32, "DLightTable is 32 bytes");
 
+// What the device-side table build of a light update works on (light_tables.hip; device pointers, set up by prt_api.cpp).
+struct DLightTableBuild {
+    const DLightNodeT<double>* full; // the full tree (every table's subtree is descended in it)
+    const DLightNodeT<double>* top;  // the part above the tables, as the kernels will descend it
+    const int32_t* table_node;       // per table: the root of its subtree in `full`
+    const double* table_area;        // per table: that subtree's area
+    uint32_t* tab;                   // DLightTable headers (from the host plan), then the thresholds / buckets to fill
+    uint32_t* flag;                  // set to 1 by a verification lane that finds a difference
+    uint32_t n_full, n_top, n_tables, n_words;
+    int32_t full_root, root;
+    float total;                     // (float) area of the whole tree
+};
+
 template <typename R>
 struct alignas(sizeof(R) == 8 ? 128 : 16) DLightTriT {
     R v0[3], v1[3], v2[3];

@@ -99,6 +99,18 @@ void setup_triangles(const PrtSceneDesc& d, std::vector<HostTri>& out) {
     }
 }
 
+// ... and for the listed triangles only: vertices / normals hold 9 doubles per LISTED triangle (normals may be null).
+void update_triangles_listed(const int32_t* prims, size_t n, const double* vertices, const double* normals, std::vector<HostTri>& tris) {
+    for (size_t i = 0; i < n; ++i) {
+        V p[3], vn[3];
+        for (int k = 0; k < 3; ++k) {
+            p[k] = load(vertices + i * 9 + k * 3);
+            vn[k] = normals ? load(normals + i * 9 + k * 3) : V{0, 0, 0};
+        }
+        setup_triangle_geometry(tris[(size_t)prims[i]], p, vn);
+    }
+}
+
 // New vertex positions for an existing triangle set (same meshes, materials and texture coordinates).
 void update_triangles(const double* vertices, const double* normals, std::vector<HostTri>& tris) {
     for (size_t t = 0; t < tris.size(); ++t) {
@@ -320,10 +332,17 @@ int32_t light_pick(const LightTree& lt, float p) {
     return ~node;
 }
 
-static void build_light_tables(LightTree& out) {
+// The tables in three parts.  The PLAN is everything that does not need a descent: which subtrees get a table, their
+// headers (first, n, offsets, n_bkt, inv_w) and the part of the tree above them, renumbered.  It depends on the positions
+// only through inv_w being finite and positive; everything else follows from the triangle counts of the light meshes
+// (RefBuilder::build splits at span / 2).  The FILL is the thresholds, then the buckets (which read them); VERIFY compares
+// the table pick with the descent.  prt_scene_create / prt_scene_update_vertices run all three here; a light update of a
+// resident scene (prt_scene_set_dynamic_lights) runs the plan here and fill + verify on the device (light_tables.hip).
+bool plan_light_tables(const LightTree& out, LightTablePlan& plan) {
+    plan = LightTablePlan();
     const std::vector<DLightNode>& full = out.full_nodes;
     const size_t nn = full.size();
-    if (out.full_root < 0 || nn == 0) return;
+    if (out.full_root < 0 || nn == 0) return false;
     // per node: leaves of the subtree (contiguous in CDF order: the flattening is depth-first, left to right), its area as
     // the reference sums it, and whether TraverseSample is monotone on it (no span-1 node over a node inside)
     std::vector<uint32_t> first(nn, 0), count(nn, 0);
@@ -341,65 +360,47 @@ static void build_light_tables(LightTree& out) {
         area[k] = single ? ref_area(n.left) : ref_area(n.left) + ref_area(n.right); // BVH.cpp:21-45
         clean[k] = !(single && n.left >= 0) && (n.left < 0 || clean[n.left]) && (n.right < 0 || clean[n.right]);
     }
-    std::vector<uint32_t> hdr, body; // headers first (8 words each), then thresholds / buckets; offsets fixed up at the end
-    struct Made { int32_t node; uint32_t table; };
-    std::vector<Made> made;
+    std::vector<uint32_t> hdr; // headers first (8 words each), then thresholds / buckets; offsets fixed up at the end
+    uint32_t body = 0;
     std::vector<int32_t> stack{out.full_root};
     while (!stack.empty()) {
         const int32_t k = stack.back();
         stack.pop_back();
         if (clean[k] && count[k] >= PRT_LIGHT_TABLE_MIN) {
-            const uint32_t n = count[k], f0 = first[k];
+            const uint32_t n = count[k];
             DLightTable t{};
-            t.first = f0;
+            t.first = first[k];
             t.n = n;
-            t.thr_off = (uint32_t)body.size();
-            // thr[i]: the smallest p whose descent reaches leaf f0 + i or one to its right
-            body.push_back(float_bits(0.f));
-            for (uint32_t i = 1; i < n; ++i)
-                body.push_back(first_pattern([&](float p) { return descend(full, k, p) >= (int32_t)(f0 + i); }));
-            body.push_back(0x7f800000u); // thr[n] = +inf ends every walk
             uint32_t nb = 1;
             while (nb < 2 * n && nb < (1u << 20)) nb <<= 1;
             t.n_bkt = nb;
             t.inv_w = (float)((double)nb / area[k]);
-            if (!(t.inv_w > 0.f) || !std::isfinite(t.inv_w)) { // degenerate areas: no table for this subtree
-                body.resize(t.thr_off);
-                if (full[k].left >= 0) stack.push_back(full[k].left);
-                if (full[k].right >= 0 && full[k].right != full[k].left) stack.push_back(full[k].right);
+            if (t.inv_w > 0.f && std::isfinite(t.inv_w)) { // (degenerate areas: no table for this subtree, its children are tried)
+                t.thr_off = body; // thr[0..n]
+                t.bkt_off = body + n + 1;
+                body += n + 1 + 2 * nb;
+                plan.node.push_back(k);
+                plan.area.push_back(area[k]);
+                uint32_t w[8];
+                std::memcpy(w, &t, sizeof(t));
+                hdr.insert(hdr.end(), w, w + 8);
                 continue;
             }
-            t.bkt_off = (uint32_t)body.size();
-            const uint32_t* thr = nullptr;
-            for (uint32_t b = 0; b < nb; ++b) {
-                const uint32_t pat = first_pattern([&](float p) { return bucket_of(p, t.inv_w, nb) >= b; });
-                uint32_t i = n - 1; // a bucket no p falls into: anything valid
-                if (pat != 0x7f800000u) i = (uint32_t)descend(full, k, bits_float(pat)) - f0;
-                thr = body.data() + t.thr_off;
-                const uint32_t next = thr[i + 1];
-                body.push_back(i);
-                body.push_back(next);
-            }
-            made.push_back({k, (uint32_t)(hdr.size() / 8)});
-            uint32_t w[8];
-            std::memcpy(w, &t, sizeof(t));
-            hdr.insert(hdr.end(), w, w + 8);
-            continue;
         }
         if (full[k].left >= 0) stack.push_back(full[k].left);
         if (full[k].right >= 0 && full[k].right != full[k].left) stack.push_back(full[k].right);
     }
-    if (made.empty()) return;
+    if (plan.node.empty()) return false;
     const uint32_t shift = (uint32_t)hdr.size();
-    for (size_t t = 0; t < made.size(); ++t) {
+    for (size_t t = 0; t < plan.node.size(); ++t) {
         hdr[8 * t + 2] += shift; // thr_off
         hdr[8 * t + 3] += shift; // bkt_off
     }
-    std::vector<uint32_t> tab(hdr);
-    tab.insert(tab.end(), body.begin(), body.end());
+    plan.tab = hdr;
+    plan.tab.resize((size_t)shift + body, 0u);
     // the part of the tree above the tables, renumbered breadth-first (K3 stages it in LDS: a handful of nodes)
     std::vector<int32_t> table_of(nn, -1);
-    for (const Made& m : made) table_of[m.node] = (int32_t)m.table;
+    for (size_t t = 0; t < plan.node.size(); ++t) table_of[plan.node[t]] = (int32_t)t;
     auto map_ref = [&](int32_t ref, const std::vector<int32_t>& newidx) {
         if (ref < 0) return ref;
         if (table_of[ref] >= 0) return (int32_t)(PRT_LIGHT_TABLE_BIT | (uint32_t)table_of[ref]);
@@ -413,31 +414,71 @@ static void build_light_tables(LightTree& out) {
         if (n.right >= 0 && n.right != n.left && table_of[n.right] < 0) order.push_back(n.right);
     }
     for (size_t i = 0; i < order.size(); ++i) newidx[order[i]] = (int32_t)i;
-    std::vector<DLightNode> top(order.size());
+    plan.top.resize(order.size());
     for (size_t i = 0; i < order.size(); ++i) {
         DLightNode n = full[order[i]];
         n.left = map_ref(n.left, newidx);
         n.right = map_ref(n.right, newidx);
-        top[i] = n;
+        plan.top[i] = n;
     }
-    LightTree cand = out;
-    cand.nodes = top;
-    cand.root = map_ref(out.full_root, newidx);
+    plan.root = map_ref(out.full_root, newidx);
+    return true;
+}
+
+// Thresholds, then buckets, of every planned table into plan.tab.
+static void fill_light_tables(const LightTree& out, LightTablePlan& plan) {
+    const std::vector<DLightNode>& full = out.full_nodes;
+    uint32_t* tab = plan.tab.data();
+    for (size_t ti = 0; ti < plan.node.size(); ++ti) {
+        DLightTable t;
+        std::memcpy(&t, tab + 8 * ti, sizeof(t));
+        const int32_t k = plan.node[ti];
+        const uint32_t n = t.n, f0 = t.first, nb = t.n_bkt;
+        uint32_t* thr = tab + t.thr_off;
+        // thr[i]: the smallest p whose descent reaches leaf f0 + i or one to its right
+        thr[0] = float_bits(0.f);
+        for (uint32_t i = 1; i < n; ++i)
+            thr[i] = first_pattern([&](float p) { return descend(full, k, p) >= (int32_t)(f0 + i); });
+        thr[n] = 0x7f800000u; // thr[n] = +inf ends every walk
+        for (uint32_t b = 0; b < nb; ++b) {
+            const uint32_t pat = first_pattern([&](float p) { return bucket_of(p, t.inv_w, nb) >= b; });
+            uint32_t i = n - 1; // a bucket no p falls into: anything valid
+            if (pat != 0x7f800000u) i = (uint32_t)descend(full, k, bits_float(pat)) - f0;
+            tab[t.bkt_off + 2 * b] = i;
+            tab[t.bkt_off + 2 * b + 1] = thr[i + 1];
+        }
+    }
+}
+
+void apply_light_tables(LightTree& out, const LightTablePlan& plan, const std::vector<uint32_t>& tab) {
+    out.nodes = plan.top;
+    out.root = plan.root;
+    out.tab = tab;
+    out.n_tables = (uint32_t)plan.node.size();
+}
+
+// Verification: the table pick must be the descent's at every threshold and one pattern below it, at both ends of every
+// bucket, at 0, at the areas, far beyond them, and at 2^16 random patterns per table — through the WHOLE tree (the top
+// part included), against the full tree.  Any difference and the scene keeps the tree.
+static bool verify_light_tables(const LightTree& out, const LightTablePlan& plan) {
+    const std::vector<DLightNode>& full = out.full_nodes;
+    const std::vector<uint32_t>& tab = plan.tab;
+    LightTree cand;
+    cand.nodes = plan.top;
+    cand.root = plan.root;
     cand.tab = tab;
-    cand.n_tables = (uint32_t)made.size();
-    // Verification: the table pick must be the descent's at every threshold and one pattern below it, at both ends of every
-    // bucket, at 0, at the areas, far beyond them, and at 2^16 random patterns per table — through the WHOLE tree (the top
-    // part included), against the full tree.  Any difference and the scene keeps the tree.
     auto same = [&](float p) { return light_pick(cand, p) == descend(full, out.full_root, p); };
     bool ok = true;
     uint64_t rng = 0x9E3779B97F4A7C15ull;
     const float total = (float)out.area;
-    for (const Made& m : made) {
+    for (size_t ti = 0; ti < plan.node.size(); ++ti) {
+        const uint32_t table = (uint32_t)ti;
+        const int32_t node = plan.node[ti];
         DLightTable t;
-        std::memcpy(&t, tab.data() + 8 * (size_t)m.table, sizeof(t));
+        std::memcpy(&t, tab.data() + 8 * ti, sizeof(t));
         // p as the table sees it is what is left of the root's p after the top part's subtractions: test the table's own
         // domain through table_pick / descend on the subtree, and the whole pick through the root
-        auto same_sub = [&](float p) { return table_pick(tab.data(), m.table, p) == descend(full, m.node, p); };
+        auto same_sub = [&](float p) { return table_pick(tab.data(), table, p) == descend(full, node, p); };
         for (uint32_t i = 0; i <= t.n && ok; ++i) {
             const uint32_t b = tab[t.thr_off + i];
             if (b != 0x7f800000u) ok = ok && same_sub(bits_float(b));
@@ -450,12 +491,12 @@ static void build_light_tables(LightTree& out) {
             ok = ok && same_sub(bits_float(pat));
             if (pat) ok = ok && same_sub(bits_float(pat - 1));
         }
-        const uint32_t top_pat = float_bits((float)(2.0 * area[m.node]));
+        const uint32_t top_pat = float_bits((float)(2.0 * plan.area[ti]));
         for (int r = 0; r < 65536 && ok; ++r) {
             rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
             ok = ok && same_sub(bits_float((uint32_t)(rng % ((uint64_t)top_pat + 1))));
         }
-        ok = ok && same_sub(0.f) && same_sub((float)area[m.node]) && same_sub(3.0e38f) && same_sub(1e-30f);
+        ok = ok && same_sub(0.f) && same_sub((float)plan.area[ti]) && same_sub(3.0e38f) && same_sub(1e-30f);
     }
     const uint32_t tot_pat = float_bits(total);
     for (int r = 0; r < 262144 && ok; ++r) { // the whole pick, over the patterns p = (float)(sqrt(xi) * area) can take
@@ -464,15 +505,19 @@ static void build_light_tables(LightTree& out) {
     }
     for (uint32_t b = tot_pat > 64 ? tot_pat - 64 : 0; b <= tot_pat + 64 && ok; ++b) ok = ok && same(bits_float(b)); // the wrap-around region
     ok = ok && same(0.f);
-    if (!ok) return;
-    out.nodes.swap(cand.nodes);
-    out.root = cand.root;
-    out.tab.swap(cand.tab);
-    out.n_tables = cand.n_tables;
+    return ok;
+}
+
+static void build_light_tables(LightTree& out) {
+    LightTablePlan plan;
+    if (!plan_light_tables(out, plan)) return;
+    fill_light_tables(out, plan);
+    if (!verify_light_tables(out, plan)) return;
+    apply_light_tables(out, plan, plan.tab);
 }
 
 void build_light_tree(const PrtSceneDesc& d, const std::vector<HostTri>& tris, const std::vector<DMaterial>& mats,
-                      LightTree& out) {
+                      LightTree& out, bool with_tables) {
     out.nodes.clear();
     out.tris.clear();
     out.root = -1;
@@ -520,7 +565,7 @@ void build_light_tree(const PrtSceneDesc& d, const std::vector<HostTri>& tris, c
     out.full_root = out.root;
     out.tab.clear();
     out.n_tables = 0;
-    build_light_tables(out);
+    if (with_tables) build_light_tables(out);
     for (DLightTri& lt : out.tris) { // Triangle::Sample pdf = 1/area; TraverseSample pdf *= area; BVHNode::Sample pdf /= total
         double pdf = 1.0 / lt.area;
         pdf *= lt.area;
