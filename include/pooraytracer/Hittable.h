@@ -3,7 +3,7 @@
 // On the host the scene-graph classes are DESCRIPTORS: they carry the same public data and
 // constructors as the reference's, and Camera::Render flattens them into a PrtSceneDesc for the HIP
 // library (include/prt.h).  Intersection itself never runs on the host: the base Hittable::Hit /
-// Occluded / Sample below forward queries to the device through the same C ABI (K1 / k_sample_lights).
+// Occluded / ClosestPoint / Sample below forward queries to the device through the same C ABI (K1 / K6 / k_sample_lights).
 #pragma once
 #include <memory>
 #include <vector>
@@ -43,6 +43,14 @@ public:
     // Not virtual: nothing overrides them, and the vtable layout of existing clients stays as it was.
     bool Occluded(const Ray& ray, Interval domain) const;
     std::vector<bool> Occluded(const std::vector<Ray>& rays, Interval domain) const;
+    // The point form of Hit: the point of this object's triangles nearest to p and its distance, if any lies within maxDist
+    // (infinity: unbounded) - prt_closest_point (device); false, and closest / distance untouched, where none does.  The
+    // batch form answers every point with the one radius in ONE launch: closest and distance are resized to p.size() and
+    // filled where the returned [i] is true.  The scene keeps its triangles' corners on the device from the first use on
+    // (prt_scene_set_distance_queries).  Not virtual, as Occluded.
+    bool ClosestPoint(const point3& p, double maxDist, point3& closest, double& distance) const;
+    std::vector<bool> ClosestPoint(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
+                                   std::vector<double>& distance) const;
     virtual AABB BoundingBox() const = 0;
     // lights.Sample(origin, record, pdf): one sample through prt_sample_lights (device).
     virtual void Sample(const point3& origin, HitRecord& samplePointRecord, double& pdf) const;

@@ -19,6 +19,8 @@
  *                         caller's own rays: probes, lightmap texels, camera models the reference lacks
  *   prt_render_multi      same over several GPUs of this process: tiles + one RCCL reduce of the fp32 framebuffer
  *                         (replaces the std::thread row bands of Source/Camera.cpp:46-71)
+ *   prt_closest_point     new: for a batch of points, the nearest point of the mesh and its distance, against the same resident
+ *                         BVH (the reference has no point query); needs prt_scene_set_distance_queries
  *   prt_sample_lights     replaces lights.Sample(origin, record, pdf) (Source/HittableList.h:44-59,
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
  *   prt_scene_refit       new vertex positions for a resident scene: records and BVH boxes follow on the GPU, the tree's
@@ -492,6 +494,73 @@ int prt_trace_surface_device(PrtScene* scene, const void* d_rays, size_t n, void
 /* K4 first, as prt_trace_closest_sorted_device: same bytes, the batch traced in a locality order. */
 int prt_trace_surface_sorted_device(PrtScene* scene, const void* d_rays, size_t n, void* d_out,
                                     int count_work, int precision, void* hip_stream);
+
+/*
+ * Closest-point queries: for each of n points, the nearest point of the mesh and its distance - the point form of
+ * prt_trace_closest, against the same resident 4-wide BVH (the reference has no such query).  K6 (closest_point.hip): one
+ * lane per query, a best-first descent with fp32 lower bounds of the point-box distance, fp64 point-triangle tests.
+ *
+ * The switch.  A ray needs a triangle's plane and edge functions (what the scene keeps); a point query needs its corners.
+ * prt_scene_set_distance_queries(scene, 1) makes the scene keep them on the device: 96 bytes per triangle in BVH leaf
+ * order, nothing while the switch is off (the default).  Any time; survives prt_scene_upload / prt_scene_update_vertices.
+ * While it is on, every path that moves the resident geometry keeps the table in step: prt_scene_upload and
+ * prt_scene_update_vertices make it from the host triangles, prt_scene_refit* and prt_scene_rebuild* from the caller's
+ * positions through the resident (the rebuild's NEW) leaf order, on the call's stream in its writing phase; nothing else
+ * those calls write changes.  Switching on for an uploaded scene builds the table at once from the host triangles
+ * (synchronous; PRT_E_OOM / PRT_E_HIP leave the switch off) - and is refused with PRT_E_INVALID while the host geometry is
+ * stale (PrtRefitInfo.host_stale: prt_scene_refit_device / prt_scene_rebuild_device moved the geometry past the host
+ * copy): switch on before moving geometry, or call prt_scene_refit or prt_scene_update_vertices first.  Switching off
+ * frees the table (after the queries in flight).
+ */
+int prt_scene_set_distance_queries(PrtScene* scene, int on);
+int prt_scene_get_distance_queries(const PrtScene* scene, int* on);
+
+typedef struct PrtPointQuery {
+    double p[3];     /* the query point */
+    double max_dist; /* search radius: +inf = unbounded, 0 is legal */
+} PrtPointQuery; /* 32 bytes */
+
+typedef struct PrtClosestPoint { /* 64 bytes */
+    double dist;        /* |p - point|; +inf on a miss */
+    double point[3];    /* the nearest point of the mesh */
+    double alpha, beta; /* point = (1-alpha-beta) v0 + alpha v1 + beta v2 of triangle prim; alpha, beta >= 0, alpha+beta <= 1 */
+    int32_t prim;       /* PrtSceneDesc order; -1 on a miss */
+    int32_t feature;    /* 0 face, 1/2/3 edge v0v1 / v1v2 / v2v0, 4/5/6 vertex v0 / v1 / v2; -1 on a miss */
+    int32_t side;       /* sign of dot(cross(v1-v0, v2-v0), p - point): +1, -1, 0; 0 on a miss */
+    int32_t reserved;   /* written as 0 */
+} PrtClosestPoint;
+/* Contract:
+ *  1. Candidates.  A triangle is a candidate iff its computed squared distance d2 satisfies d2 <= max_dist * max_dist,
+ *     evaluated in fp64.  With no candidate the miss record is written: dist = +inf, prim = feature = -1, side = 0, every
+ *     other field 0.
+ *  2. d2, alpha, beta and feature come from the region-classifying point-triangle algorithm of Ericson, Real-Time Collision
+ *     Detection 5.1.5, run in fp64 (no fused multiply-adds) on the resident corners; point = v0 + alpha (v1 - v0) +
+ *     beta (v2 - v0), d2 = |p - point|^2, dist = sqrt(d2): a pure function of the query and the three corners.  At a vertex
+ *     (alpha, beta) is exactly (0,0), (1,0) or (0,1); on edge v0v1 beta == 0, on v2v0 alpha == 0, on v1v2 alpha == 1 - beta.
+ *     (A query that is bitwise some triangle's v0 therefore has d2 == 0 and is found with max_dist = 0; at a v1 or v2 the
+ *     expression v0 + 1 (v1 - v0) can round to a neighbour of the corner, and d2 to a rounding above 0.)
+ *  3. Ties.  The winner is the candidate with the smallest (d2, prim) in lexicographic order: the record does not depend on
+ *     the tree, the builder, the leaf order or the batch order, bit for bit.  (Stricter than the ray calls' "later-tested
+ *     wins": the traversal skips a subtree only when its lower bound is STRICTLY greater than the best d2 so far.)
+ *  4. Culling is conservative: the fp32 lower bound of a box never exceeds the computed d2 of a triangle below it (the
+ *     derivation is at box_bound, closest_point.hip).  The point is taken relative to the grid origin, so a unit scene at
+ *     coordinate 1e6 is culled as well as one at the origin.
+ *  5. fp64 only: there is no precision argument, no fp32 form and no sorted (K4) form.
+ *  6. Exactly n records are written; bytes beyond them stay as they are.  n == 0 is PRT_OK.  d_out must be 32-byte aligned
+ *     (the kernel stores 32 bytes at a time), else PRT_E_INVALID.
+ *  7. Errors: PRT_E_NO_DEVICE on a scene that is not uploaded (the message names the function); PRT_E_INVALID when the
+ *     switch is off (the message names the function and prt_scene_set_distance_queries), for a null buffer with n > 0, or
+ *     n >= 2^32.  The host-buffer call also returns PRT_E_INVALID for a query with a non-finite p, or a max_dist that is NaN
+ *     or negative (it checks the batch before anything else).  The device call does not read the queries on the host: its
+ *     record for such a query is unspecified, but the call terminates.
+ *  8. The call goes through the scene's two call slots like the trace calls: it orders itself after a refit or rebuild and
+ *     is asynchronous on hip_stream.  Afterwards prt_get_counters reports kernel_ms, rays_closest == 0, rays_shadow == 0 and
+ *     samples == 0; with count_work != 0 also node_fetches (node records read) and tri_tests (point-triangle tests), and in
+ *     inner_rounds / leaf_rounds the stack entries (of inner nodes / of leaves) that were dropped at the pop by the bound
+ *     they carry, without a fetch. */
+int prt_closest_point(PrtScene* scene, const PrtPointQuery* q, size_t n, PrtClosestPoint* out, int count_work); /* host buffers, synchronous */
+/* On device-resident buffers (d_q: n PrtPointQuery, d_out: n PrtClosestPoint, 32-byte aligned); stream may be NULL. */
+int prt_closest_point_device(PrtScene* scene, const void* d_q, size_t n, void* d_out, int count_work, void* hip_stream);
 
 /* NEE point selection for (pixel, sample) keys 0..n-1 of `seed` from given origins (test hook). */
 int prt_sample_lights(PrtScene* scene, const double* origins, size_t n, uint64_t seed,

@@ -221,6 +221,23 @@ class PrtSurface(C.Structure):
     ]
 
 
+class PrtPointQuery(C.Structure):
+    _fields_ = [("p", D3), ("max_dist", C.c_double)]
+
+
+class PrtClosestPoint(C.Structure):
+    _fields_ = [
+        ("dist", C.c_double),
+        ("point", D3),
+        ("alpha", C.c_double),
+        ("beta", C.c_double),
+        ("prim", C.c_int32),
+        ("feature", C.c_int32),
+        ("side", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class PrtLightSample(C.Structure):
     _fields_ = [
         ("position", D3),
@@ -259,7 +276,12 @@ SURFACE_DTYPE = np.dtype(HIT_DTYPE.descr + [
 LIGHT_SAMPLE_DTYPE = np.dtype(
     [("position", "<f8", 3), ("normal", "<f8", 3), ("pdf", "<f8"), ("prim", "<i4"), ("front", "<i4")]
 )
+POINT_QUERY_DTYPE = np.dtype([("p", "<f8", 3), ("max_dist", "<f8")])
+CLOSEST_POINT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", 3), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"),
+                                ("feature", "<i4"), ("side", "<i4"), ("reserved", "<i4")])
 assert RAY_DTYPE.itemsize == C.sizeof(PrtRay) == 64
+assert POINT_QUERY_DTYPE.itemsize == C.sizeof(PrtPointQuery) == 32
+assert CLOSEST_POINT_DTYPE.itemsize == C.sizeof(PrtClosestPoint) == 64
 assert HIT_DTYPE.itemsize == C.sizeof(PrtHit) == 32
 assert SURFACE_DTYPE.itemsize == C.sizeof(PrtSurface) == 192
 assert LIGHT_SAMPLE_DTYPE.itemsize == C.sizeof(PrtLightSample) == 64
@@ -284,6 +306,10 @@ EXPORTS = [
     "prt_scene_rebuild_device",
     "prt_scene_set_dynamic_lights",
     "prt_scene_get_dynamic_lights",
+    "prt_scene_set_distance_queries",
+    "prt_scene_get_distance_queries",
+    "prt_closest_point",
+    "prt_closest_point_device",
     "prt_scene_light_update_info",
     "prt_scene_light_table_words",
     "prt_scene_bvh_info",

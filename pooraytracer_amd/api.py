@@ -61,6 +61,10 @@ def load():
     L.prt_scene_set_dynamic_lights.argtypes = [vp, i32]
     L.prt_scene_get_dynamic_lights.argtypes = [vp, C.POINTER(C.c_int)]
     L.prt_scene_light_update_info.argtypes = [vp, vp]
+    L.prt_scene_set_distance_queries.argtypes = [vp, i32]
+    L.prt_scene_get_distance_queries.argtypes = [vp, C.POINTER(C.c_int)]
+    L.prt_closest_point.argtypes = [vp, vp, sz, vp, i32]
+    L.prt_closest_point_device.argtypes = [vp, vp, sz, vp, i32, vp]
     L.prt_scene_light_table_words.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
@@ -365,6 +369,48 @@ class Scene:
         and sort as trace_closest_device."""
         fn = self._L.prt_trace_surface_sorted_device if sort else self._L.prt_trace_surface_device
         _check(fn(self._h, d_rays_ptr, n, d_out_ptr, int(count_work), int(precision), stream), self._L)
+
+    @property
+    def distance_queries(self):
+        """Whether the scene answers closest_point* (prt_scene_set_distance_queries): off by default; on, an uploaded scene
+        keeps the fp64 corners of every triangle on the device (96 bytes each) and upload / refit* / rebuild* keep them in
+        step.  Switching on after refit_device / rebuild_device moved the geometry past the host copy is refused."""
+        on = C.c_int(0)
+        _check(self._L.prt_scene_get_distance_queries(self._h, C.byref(on)), self._L)
+        return bool(on.value)
+
+    @distance_queries.setter
+    def distance_queries(self, on):
+        _check(self._L.prt_scene_set_distance_queries(self._h, int(bool(on))), self._L)
+
+    def closest_point(self, points, max_dist=np.inf, count_work=False):
+        """Closest-point query (prt_closest_point): points (n, 3) float64, max_dist a scalar or (n,) search radius.  Returns a
+        CLOSEST_POINT_DTYPE array [n]: dist, the nearest point of the mesh, its barycentrics, prim, feature (0 face, 1-3
+        edge, 4-6 vertex) and side; dist = inf and prim = -1 where no triangle lies within max_dist.  Shape and dtype errors
+        are raised here, before any call."""
+        if not isinstance(points, np.ndarray):
+            raise TypeError(f"closest_point: points must be a numpy array, not {type(points).__name__}")
+        if points.dtype != np.float64:
+            raise TypeError(f"closest_point: points must be float64, not {points.dtype}")
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"closest_point: points must have shape (n, 3), not {points.shape}")
+        n = points.shape[0]
+        md = np.asarray(max_dist)
+        if md.dtype.kind not in "fiu":
+            raise TypeError(f"closest_point: max_dist must be real, not {md.dtype}")
+        if md.shape not in ((), (n,)):
+            raise ValueError(f"closest_point: max_dist must be a scalar or have shape ({n},), not {md.shape}")
+        q = np.zeros(n, dtype=_abi.POINT_QUERY_DTYPE)
+        q["p"] = points
+        q["max_dist"] = md
+        out = np.zeros(n, dtype=_abi.CLOSEST_POINT_DTYPE)
+        _check(self._L.prt_closest_point(self._h, q.ctypes.data, n, out.ctypes.data, int(count_work)), self._L)
+        return out
+
+    def closest_point_device(self, d_q_ptr, n, d_out_ptr, count_work=False, stream=None):
+        """prt_closest_point_device: asynchronous, on device buffers (raw pointers: n PrtPointQuery of 32 bytes, n
+        PrtClosestPoint of 64 bytes, 32-byte aligned).  The queries are not checked on the host."""
+        _check(self._L.prt_closest_point_device(self._h, d_q_ptr, int(n), d_out_ptr, int(count_work), stream), self._L)
 
     def sample_lights(self, origins, seed=1):
         origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

@@ -94,6 +94,10 @@ void launch_refit_sah(const DNode* d_nodes, uint32_t n_nodes, const float origin
                       double* d_out, hipStream_t st);
 void launch_gather_tris(const DTri* tri_in, const DTriShade* shade_in, const uint32_t* order, uint32_t n, void* tri_out,
                         uint32_t tri_out_stride, DTriShade* shade_out, hipStream_t st);
+// closest_point.hip: the corner table of a scene that answers distance queries, and K6
+void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint32_t n, DTriCorners* d_out, hipStream_t st);
+hipError_t launch_closest_point(const DScene& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n, PrtClosestPoint* d_out,
+                                DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain, hipStream_t st);
 } // namespace prt
 
 // fp32 fast mode (prt_kernels_f32.hip): K1 and K3 on float records derived from the resident fp64 ones
@@ -295,6 +299,10 @@ struct PrtScene {
         size_t cap_nodes = 0, cap_tris = 0, cap_tab = 0, cap_nodes32 = 0, cap_tris32 = 0;
     };
     LightArrays light_res, light_spare;
+    // prt_scene_set_distance_queries: while it is on, an uploaded scene keeps the fp64 corners of every triangle in BVH leaf
+    // order (96 bytes each, owned by `allocs`); upload, refit and rebuild keep the table in step with the resident geometry
+    bool distance_queries = false; // survives upload / update_vertices
+    DTriCorners* d_corners = nullptr;
     struct LightUpdate {
         double* d_gather = nullptr;    // per light triangle, resident CDF order: 9 doubles of new vertices, then (second half) of vertex normals
         std::vector<double> h_gather;  // ... read back with the refit's decision
@@ -423,6 +431,7 @@ struct PrtScene {
         if (device >= 0) (void)hipSetDevice(device);
         allocs.clear();
         d_order = nullptr;
+        d_corners = nullptr;
         refit = Refit();
         light_res = light_spare = LightArrays();
         lu = LightUpdate();
@@ -820,6 +829,37 @@ int prt_scene_light_order(const PrtScene* s, int32_t* prims, uint64_t cap) {
 
 static int upload_impl(PrtScene* s, int device);
 
+// The corner table of a scene that answers distance queries (prt_scene_set_distance_queries), from the host triangles
+// through the resident leaf order: allocated if the upload has none yet, filled on the null stream, synchronous.  The
+// scene is uploaded and its device is current.
+static int corners_from_host(PrtScene* s, const std::string& who) {
+    const size_t n = s->tris.size();
+    DevBuf<> table;
+    if (!s->d_corners) PRT_HIP_AS(who, dev_alloc(table, std::max<size_t>(n * sizeof(DTriCorners), 256)));
+    if (n) {
+        std::vector<double> v;
+        try {
+            v.resize(n * 9);
+        } catch (const std::bad_alloc&) {
+            return fail(PRT_E_OOM, who + ": out of host memory for the corner table");
+        }
+        for (size_t i = 0; i < n; ++i) std::memcpy(v.data() + i * 9, s->tris[i].v, 9 * sizeof(double));
+        DevBuf<> staged;
+        PRT_HIP_AS(who, dev_alloc(staged, v.size() * sizeof(double)));
+        PRT_HIP_AS(who, hipMemcpy(staged.get(), v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        PRT_HIP_AS(who, s->after_refit(nullptr));
+        prt::launch_gather_corners(static_cast<const double*>(staged.get()), s->d_order, (uint32_t)n,
+                                   s->d_corners ? s->d_corners : static_cast<DTriCorners*>(table.get()), nullptr);
+        PRT_HIP_AS(who, hipGetLastError());
+        PRT_HIP_AS(who, hipDeviceSynchronize());
+    }
+    if (table) {
+        s->d_corners = static_cast<DTriCorners*>(table.get());
+        s->allocs.push_back(std::move(table));
+    }
+    return PRT_OK;
+}
+
 // Either the whole scene is resident afterwards, or nothing is: a failure anywhere (allocation, copy, device build)
 // releases what was uploaded so far and leaves the scene in the not-uploaded state (device = -1), so that no later
 // call can launch a kernel on a half-filled DScene.
@@ -1077,6 +1117,7 @@ static int upload_impl(PrtScene* s, int device) {
     static_assert(sizeof(DLightNode) == 16 && sizeof(DLightTri) % 16 == 0, "LDS staging copies 16-byte pieces");
     // the fp64 kernels render without their LDS tables when the tables would cost a resident block (the fp32 ones do not)
     s->blocks_wanted = size_kernels(s, s->k64, true);
+    if (s->distance_queries && (rc = corners_from_host(s, "prt_scene_upload"))) return rc;
     return PRT_OK;
 }
 
@@ -1656,6 +1697,7 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     PRT_HIP_AS(who, hipEventRecord(R.ev0.get(), st));
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
                            R.d_tbox, g.origin_d, g.delta, st);
+    if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
         const DSceneT<float>& f = s->k32.d;
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
@@ -1782,6 +1824,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     prt::launch_permute_shade(shade_old, order_old, s->d_order, n, static_cast<uint32_t*>(inv.get()), const_cast<DTriShade*>(d.shade), st);
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
                            R.d_tbox, g.origin_d, g.delta, st);
+    if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
         const DSceneT<float>& f = s->k32.d;
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
@@ -1895,6 +1938,92 @@ int prt_scene_get_dynamic_lights(const PrtScene* s, int* on) {
     if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_dynamic_lights: null argument");
     *on = s->dynamic_lights ? 1 : 0;
     return PRT_OK;
+}
+
+int prt_scene_set_distance_queries(PrtScene* s, int on) {
+    const char* who = "prt_scene_set_distance_queries";
+    if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
+    const bool want = on != 0;
+    if (want == s->distance_queries) return PRT_OK;
+    if (s->device < 0) { // not uploaded: the next upload makes the table
+        s->distance_queries = want;
+        return PRT_OK;
+    }
+    PRT_HIP(hipSetDevice(s->device));
+    if (want) {
+        if (s->host_stale)
+            return fail(PRT_E_INVALID, std::string(who) + ": the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device moved the "
+                                                          "resident geometry past it): switch distance queries on before moving geometry, or call "
+                                                          "prt_scene_refit or prt_scene_update_vertices first");
+        if (const int rc = corners_from_host(s, who)) return rc; // (nothing is kept on a failure: the switch stays off)
+        s->distance_queries = true;
+        return PRT_OK;
+    }
+    // off: the table goes once the queries in flight, and a refit that may still be writing it, have ended
+    for (PrtScene::CallSlot& q : s->slots)
+        if (q.timed) PRT_HIP_AS(who, hipEventSynchronize(q.done.get()));
+    if (s->refit.pending) PRT_HIP_AS(who, hipEventSynchronize(s->refit.done.get()));
+    s->take(s->d_corners).reset();
+    s->d_corners = nullptr;
+    s->distance_queries = false;
+    return PRT_OK;
+}
+
+int prt_scene_get_distance_queries(const PrtScene* s, int* on) {
+    if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_distance_queries: null argument");
+    *on = s->distance_queries ? 1 : 0;
+    return PRT_OK;
+}
+
+int prt_closest_point_device(PrtScene* s, const void* d_q, size_t n, void* d_out, int count_work, void* stream) {
+    const char* who = "prt_closest_point_device";
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    const std::string w(who);
+    if (!s->distance_queries || !s->d_corners)
+        return fail(PRT_E_INVALID, w + ": distance queries are off for this scene (prt_scene_set_distance_queries)");
+    if (n && (!d_q || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
+    if (n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 queries in one batch");
+    if (reinterpret_cast<uintptr_t>(d_out) & 31u) // the kernel stores a record 32 bytes at a time
+        return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t we;
+    PrtScene::CallSlot& q = *s->next_slot(st, &we);
+    PRT_HIP_AS(who, we);
+    PRT_HIP_AS(who, q.start(st));
+    const bool count = count_work != 0;
+    PRT_HIP_AS(who, prt::launch_closest_point(s->k64.d, s->d_corners, static_cast<const PrtPointQuery*>(d_q), n,
+                                              static_cast<PrtClosestPoint*>(d_out), q.d_ctr.get(), count, s->stack_need, s->n_cu,
+                                              dev_env("PRT_TUNE_CLOSEST_PLAIN") != nullptr, st)); // (developer: the plain schedule, for A/B runs)
+    PRT_HIP_AS(who, q.stop(st));
+    PRT_HIP_AS(who, q.finish(st, count, 0));
+    return PRT_OK;
+}
+
+int prt_closest_point(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtClosestPoint* out, int count_work) {
+    static_assert(sizeof(PrtPointQuery) == 32 && sizeof(PrtClosestPoint) == 64, "PrtPointQuery is 32 bytes, PrtClosestPoint 64");
+    const char* who = "prt_closest_point";
+    if (!s) return fail(PRT_E_INVALID, "prt_closest_point: null scene");
+    if (n && (!qs || !out)) return fail(PRT_E_INVALID, "prt_closest_point: null buffer");
+    if (n > 0xffffffffull) return fail(PRT_E_INVALID, "prt_closest_point: more than 2^32 - 1 queries in one batch");
+    for (size_t i = 0; i < n; ++i) { // the batch is checked before anything else: a bad query is refused with or without a device
+        const PrtPointQuery& q = qs[i];
+        if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2])))
+            return fail(PRT_E_INVALID, "prt_closest_point: query " + std::to_string(i) + " has a non-finite point");
+        if (!(q.max_dist >= 0.0)) return fail(PRT_E_INVALID, "prt_closest_point: query " + std::to_string(i) + " has a negative or NaN max_dist");
+    }
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    if (!s->distance_queries || !s->d_corners)
+        return fail(PRT_E_INVALID, "prt_closest_point: distance queries are off for this scene (prt_scene_set_distance_queries)");
+    if (n == 0) return PRT_OK;
+    Staging b;
+    void* dq = b.in(qs, n * sizeof(PrtPointQuery));
+    void* dout = b.out(n * sizeof(PrtClosestPoint));
+    if ((rc = b.status(who)) || (rc = prt_closest_point_device(s, dq, n, dout, count_work, nullptr))) return rc;
+    b.sync();
+    b.down(out, dout, n * sizeof(PrtClosestPoint));
+    return b.status(who);
 }
 
 int prt_scene_light_update_info(const PrtScene* s, PrtLightUpdateInfo* out) {

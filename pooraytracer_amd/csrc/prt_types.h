@@ -68,6 +68,19 @@ struct alignas(4 * sizeof(R)) DTriT {
 typedef DTriT<prt_real> DTri;
 static_assert(sizeof(DTriT<double>) == 96 && sizeof(DTriT<float>) == 48, "DTri must be 96 / 48 bytes");
 
+// 96 bytes: the three fp64 corners of a triangle in BVH leaf order, kept only while a scene answers distance queries
+// (prt_scene_set_distance_queries; closest_point.hip).  DTri stores the plane and two edge functions, which a ray needs; a
+// point query needs the corners.  Padded, not packed to 72 bytes: a record never straddles a 32-byte boundary, so a test
+// reads it with 16-byte loads (a 72-byte record is only 8-byte aligned), two of every three records sit in one 128-byte line,
+// and the padding carries the triangle's index in description order - the (d2, prim) tie rule needs it for every tested
+// triangle, and would otherwise read a second line (DTriShade) per test.
+struct alignas(32) DTriCorners {
+    double v0[3], v1[3], v2[3];
+    int32_t prim; // index in PrtSceneDesc order
+    int32_t pad_[5];
+};
+static_assert(sizeof(DTriCorners) == 96, "DTriCorners must be 96 bytes");
+
 template <typename R>
 struct alignas(4 * sizeof(R)) DTriShadeT {
     R tangent[3]; // Triangle.cpp:31-46

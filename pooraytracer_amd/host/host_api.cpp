@@ -194,6 +194,39 @@ std::vector<bool> Hittable::Occluded(const std::vector<Ray>& rays, Interval doma
 
 bool Hittable::Occluded(const Ray& ray, Interval domain) const { return Occluded(std::vector<Ray>(1, ray), domain)[0]; }
 
+std::vector<bool> Hittable::ClosestPoint(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
+                                         std::vector<double>& distance) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    check(prt_scene_set_distance_queries(dc.scene, 1), "prt_scene_set_distance_queries"); // (nothing to do when it is on already)
+    std::vector<PrtPointQuery> q(p.size());
+    for (size_t i = 0; i < p.size(); ++i) {
+        q[i].p[0] = p[i].x; q[i].p[1] = p[i].y; q[i].p[2] = p[i].z;
+        q[i].max_dist = maxDist;
+    }
+    std::vector<PrtClosestPoint> r(p.size());
+    check(prt_closest_point(dc.scene, q.data(), q.size(), r.data(), 0), "prt_closest_point");
+    closest.resize(p.size());
+    distance.resize(p.size());
+    std::vector<bool> found(p.size());
+    for (size_t i = 0; i < p.size(); ++i) {
+        if (r[i].prim < 0) continue;
+        closest[i] = point3(r[i].point[0], r[i].point[1], r[i].point[2]);
+        distance[i] = r[i].dist;
+        found[i] = true;
+    }
+    return found;
+}
+
+bool Hittable::ClosestPoint(const point3& p, double maxDist, point3& closest, double& distance) const {
+    std::vector<point3> c;
+    std::vector<double> d;
+    if (!ClosestPoint(std::vector<point3>(1, p), maxDist, c, d)[0]) return false;
+    closest = c[0];
+    distance = d[0];
+    return true;
+}
+
 void Hittable::Sample(const point3& origin, HitRecord& rec, double& pdf) const {
     DeviceCache& dc = Device();
     dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
