@@ -3,7 +3,8 @@
 // On the host the scene-graph classes are DESCRIPTORS: they carry the same public data and
 // constructors as the reference's, and Camera::Render flattens them into a PrtSceneDesc for the HIP
 // library (include/prt.h).  Intersection itself never runs on the host: the base Hittable::Hit /
-// Occluded / ClosestPoint / Sample below forward queries to the device through the same C ABI (K1 / K6 / k_sample_lights).
+// Occluded / Hits / ClosestPoint / Sample below forward queries to the device through the same C ABI (K1 / K7 / K6 /
+// k_sample_lights).
 #pragma once
 #include <memory>
 #include <vector>
@@ -43,6 +44,12 @@ public:
     // Not virtual: nothing overrides them, and the vtable layout of existing clients stays as it was.
     bool Occluded(const Ray& ray, Interval domain) const;
     std::vector<bool> Occluded(const std::vector<Ray>& rays, Interval domain) const;
+    // The first maxHits (1..8) surfaces along the ray within the domain, nearest first, ties in the order the triangles were
+    // added - the multi-hit query, prt_trace_multi (device): thickness, crossing parity, entry / exit pairs.  Fewer records
+    // than maxHits: the ray has no more hits.  Each record is filled as Hit fills its one.  The batch form answers every ray
+    // over the one domain in ONE launch: out[i] for rays[i].  Not virtual, as Occluded.
+    std::vector<HitRecord> Hits(const Ray& ray, Interval domain, int maxHits) const;
+    std::vector<std::vector<HitRecord>> Hits(const std::vector<Ray>& rays, Interval domain, int maxHits) const;
     // The point form of Hit: the point of this object's triangles nearest to p and its distance, if any lies within maxDist
     // (infinity: unbounded) - prt_closest_point (device); false, and closest / distance untouched, where none does.  The
     // batch form answers every point with the one radius in ONE launch: closest and distance are resized to p.size() and

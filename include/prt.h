@@ -21,6 +21,8 @@
  *                         (replaces the std::thread row bands of Source/Camera.cpp:46-71)
  *   prt_closest_point     new: for a batch of points, the nearest point of the mesh and its distance, against the same resident
  *                         BVH (the reference has no point query); needs prt_scene_set_distance_queries
+ *   prt_trace_multi       new: the first k hits along each ray of a batch, in (t, prim) order, with an exact paging cursor
+ *                         (the reference reports one hit per world.Hit call)
  *   prt_sample_lights     replaces lights.Sample(origin, record, pdf) (Source/HittableList.h:44-59,
  *                          Source/BVH.cpp:62-67,86-100, Source/Triangle.cpp:84-93) — test hook
  *   prt_scene_refit       new vertex positions for a resident scene: records and BVH boxes follow on the GPU, the tree's
@@ -561,6 +563,62 @@ typedef struct PrtClosestPoint { /* 64 bytes */
 int prt_closest_point(PrtScene* scene, const PrtPointQuery* q, size_t n, PrtClosestPoint* out, int count_work); /* host buffers, synchronous */
 /* On device-resident buffers (d_q: n PrtPointQuery, d_out: n PrtClosestPoint, 32-byte aligned); stream may be NULL. */
 int prt_closest_point_device(PrtScene* scene, const void* d_q, size_t n, void* d_out, int count_work, void* hip_stream);
+
+/*
+ * Multi-hit queries: for each of n rays, the first k surfaces along it, in order - thickness and X-ray measurements,
+ * crossing parity, entry/exit pairs of closed shells, layered transparency done by the caller, depth layers.  K7
+ * (multi_hit.hip): K1's persistent waves and box stepping with a leaf step that keeps a sorted per-lane list.  One
+ * traversal instead of k closest-hit calls with tmin moved past the previous t - and, unlike such a peel, exact at ties:
+ * two triangles hit at a bit-identical t (shared edges, coplanar neighbours, duplicated geometry) are both reported.
+ */
+#define PRT_MULTI_HIT_MAX 8
+typedef struct PrtHitCursor {
+    double t;         /* the t of the record to continue after; -inf: from the start of the interval */
+    int32_t prim;     /* ... and its prim; -1 with t = -inf */
+    int32_t reserved; /* must be 0 */
+} PrtHitCursor; /* 16 bytes */
+/* hits holds n * k PrtHit records: ray i owns hits[i*k .. i*k + k-1].
+ * Contract:
+ *  1. Candidates.  A triangle is a candidate for ray i iff the closest-hit call's triangle test accepts it over the
+ *     INCLUSIVE interval [tmin, tmax] (tri_test, prt_device.h: |n.d| >= 1e-8, tmin <= t <= tmax, alpha, beta >= 0,
+ *     alpha + beta <= 1, no NaN) and, if `after` is given, the pair (t, prim) is lexicographically greater than
+ *     (after[i].t, after[i].prim).  after == NULL means no cursor for any ray; {t = -inf, prim = -1} is the neutral cursor
+ *     for one ray.  prim is the PrtSceneDesc index, as everywhere at this boundary.
+ *  2. Result.  The min(k, #candidates) smallest candidates by (t, prim), in ascending order, each written as the PrtHit the
+ *     closest-hit call writes for that triangle (t, alpha, beta, prim, front); every remaining slot holds the miss record
+ *     (t = +inf, alpha = beta = 0, prim = -1, front = 0).  No primitive appears twice.
+ *  3. Independence.  The bytes do not depend on the builder, the tree, the leaf order, the batch order, sorted or plain, or
+ *     count_work.  (Stricter than the closest-hit call's "later-tested wins": a subtree is skipped only when its fp32 entry
+ *     bound lies beyond the k-th t rounded up, so a tying triangle with a smaller prim is never culled; the argument is at
+ *     the kernel.)
+ *  4. Paging.  Feed the last non-miss record of a page back as that ray's cursor to get the next page: for k1 * m <=
+ *     PRT_MULTI_HIT_MAX, m pages of size k1 are, bit for bit, the first k1 * m records of one call with k = k1 * m - also
+ *     when a tie straddles a page boundary.  (A ray whose page ends in a miss record has no further hits.)
+ *  5. Relation to the closest-hit call.  Slot 0 without a cursor is a closest hit by the same test, but is not promised
+ *     bit-equal to prt_trace_closest*: ties resolve differently (smallest prim here, later-tested there), and this kernel's
+ *     triangle arithmetic is compiled with floating-point contraction off, K1's is not.  Both are within the tier-1 (fp64)
+ *     or tier-2 (fp32) tolerance of the exact value.
+ *  6. Precision.  Both precisions at the device calls; rays, cursors and hits stay fp64 records at the boundary.  In fp32 the
+ *     cursor's t is rounded to float on load; a hit's t is a widened float, so paging is exact within fp32 as well.
+ *  7. Errors.  PRT_E_NO_DEVICE on a scene that is not uploaded (the message names the function); PRT_E_INVALID for k < 1 or
+ *     k > PRT_MULTI_HIT_MAX, a null rays or hits with n > 0, an unknown precision, n >= 2^32 in the sorted call, or a d_hits
+ *     that is not 32-byte aligned (the kernel stores 32 bytes at a time).  n == 0 is PRT_OK.  The host call also refuses a
+ *     cursor whose t is NaN or whose reserved != 0.  The device call does not read cursors on the host: a NaN t there has no
+ *     candidate after it (miss records), reserved is not read, and the call terminates on any input.
+ *  8. Written range.  Exactly n * k records are written; bytes beyond them stay as they are.
+ *  9. Ordering and counters.  The call goes through the scene's two call slots and orders itself after a refit or rebuild,
+ *     like the trace calls.  Afterwards prt_get_counters reports rays_closest == n, rays_shadow == 0, samples == 0 and
+ *     kernel_ms (keys + sort + trace for the sorted call); with count_work != 0 also node_fetches / tri_tests / tri_full
+ *     (the at most k re-evaluations of the winners at the write-out are not counted). */
+int prt_trace_multi(PrtScene* scene, const PrtRay* rays, const PrtHitCursor* after, size_t n, int32_t k,
+                    PrtHit* hits, int count_work); /* host buffers, fp64, synchronous */
+/* On device-resident buffers (d_rays: n PrtRay, d_after: n PrtHitCursor or NULL, d_hits: n * k PrtHit, 32-byte aligned);
+ * stream may be NULL. */
+int prt_trace_multi_device(PrtScene* scene, const void* d_rays, const void* d_after, size_t n, int32_t k,
+                           void* d_hits, int count_work, int precision, void* hip_stream);
+/* K4 first, as prt_trace_closest_sorted_device: same bytes, the batch traced in a locality order. */
+int prt_trace_multi_sorted_device(PrtScene* scene, const void* d_rays, const void* d_after, size_t n, int32_t k,
+                                  void* d_hits, int count_work, int precision, void* hip_stream);
 
 /* NEE point selection for (pixel, sample) keys 0..n-1 of `seed` from given origins (test hook). */
 int prt_sample_lights(PrtScene* scene, const double* origins, size_t n, uint64_t seed,

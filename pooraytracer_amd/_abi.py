@@ -202,6 +202,13 @@ class PrtHit(C.Structure):
     ]
 
 
+MULTI_HIT_MAX = 8  # prt.h PRT_MULTI_HIT_MAX
+
+
+class PrtHitCursor(C.Structure):
+    _fields_ = [("t", C.c_double), ("prim", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PrtSurface(C.Structure):
     _fields_ = [
         ("t", C.c_double),
@@ -279,6 +286,8 @@ LIGHT_SAMPLE_DTYPE = np.dtype(
 POINT_QUERY_DTYPE = np.dtype([("p", "<f8", 3), ("max_dist", "<f8")])
 CLOSEST_POINT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", 3), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"),
                                 ("feature", "<i4"), ("side", "<i4"), ("reserved", "<i4")])
+HIT_CURSOR_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("reserved", "<i4")])  # neutral: t = -inf, prim = -1
+assert HIT_CURSOR_DTYPE.itemsize == C.sizeof(PrtHitCursor) == 16
 assert RAY_DTYPE.itemsize == C.sizeof(PrtRay) == 64
 assert POINT_QUERY_DTYPE.itemsize == C.sizeof(PrtPointQuery) == 32
 assert CLOSEST_POINT_DTYPE.itemsize == C.sizeof(PrtClosestPoint) == 64
@@ -325,6 +334,9 @@ EXPORTS = [
     "prt_trace_surface",
     "prt_trace_surface_device",
     "prt_trace_surface_sorted_device",
+    "prt_trace_multi",
+    "prt_trace_multi_device",
+    "prt_trace_multi_sorted_device",
     "prt_sample_lights",
     "prt_render",
     "prt_render_device",

@@ -78,6 +78,9 @@ def load():
     L.prt_trace_surface.argtypes = [vp, vp, sz, vp, i32]
     L.prt_trace_surface_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
     L.prt_trace_surface_sorted_device.argtypes = [vp, vp, sz, vp, i32, i32, vp]
+    L.prt_trace_multi.argtypes = [vp, vp, vp, sz, C.c_int32, vp, i32]
+    L.prt_trace_multi_device.argtypes = [vp, vp, vp, sz, C.c_int32, vp, i32, i32, vp]
+    L.prt_trace_multi_sorted_device.argtypes = [vp, vp, vp, sz, C.c_int32, vp, i32, i32, vp]
     L.prt_sample_lights.argtypes = [vp, vp, sz, u64, vp]
     L.prt_render.argtypes = [vp, vp, vp, vp, vp]
     L.prt_render_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
@@ -369,6 +372,43 @@ class Scene:
         and sort as trace_closest_device."""
         fn = self._L.prt_trace_surface_sorted_device if sort else self._L.prt_trace_surface_device
         _check(fn(self._h, d_rays_ptr, n, d_out_ptr, int(count_work), int(precision), stream), self._L)
+
+    def trace_multi(self, rays, k, after=None, count_work=False):
+        """Multi-hit query (prt_trace_multi): the first k hits along each ray in ascending (t, prim), as an (n, k) array of
+        HIT_DTYPE; slots past a ray's last hit hold the miss record (t = inf, prim = -1).  `after`: None, or an (n,)
+        HIT_CURSOR_DTYPE array - only hits after (t, prim) of a ray's cursor are reported; feeding back the last hit of a
+        page (its t and prim) gives the next page.  Shape and dtype errors are raised here, before any call."""
+        if not isinstance(rays, np.ndarray):
+            raise TypeError(f"trace_multi: rays must be a numpy array, not {type(rays).__name__}")
+        if rays.dtype != _abi.RAY_DTYPE:
+            raise TypeError(f"trace_multi: rays must have RAY_DTYPE, not {rays.dtype}")
+        if rays.ndim != 1:
+            raise ValueError(f"trace_multi: rays must have shape (n,), not {rays.shape}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"trace_multi: k must be an integer, not {type(k).__name__}")
+        if not 1 <= k <= _abi.MULTI_HIT_MAX:
+            raise ValueError(f"trace_multi: k must be 1..{_abi.MULTI_HIT_MAX}, not {k}")
+        n = rays.shape[0]
+        if after is not None:
+            if not isinstance(after, np.ndarray):
+                raise TypeError(f"trace_multi: after must be a numpy array, not {type(after).__name__}")
+            if after.dtype != _abi.HIT_CURSOR_DTYPE:
+                raise TypeError(f"trace_multi: after must have HIT_CURSOR_DTYPE, not {after.dtype}")
+            if after.shape != (n,):
+                raise ValueError(f"trace_multi: after must have shape ({n},), not {after.shape}")
+            after = np.ascontiguousarray(after)
+        rays = np.ascontiguousarray(rays)
+        hits = np.zeros((n, int(k)), dtype=_abi.HIT_DTYPE)
+        _check(self._L.prt_trace_multi(self._h, rays.ctypes.data, None if after is None else after.ctypes.data, n, int(k),
+                                       hits.ctypes.data, int(count_work)), self._L)
+        return hits
+
+    def trace_multi_device(self, d_rays_ptr, n, k, d_hits_ptr, d_after_ptr=None, count_work=False, precision=0, sort=False,
+                           stream=None):
+        """The multi-hit kernel on device buffers (raw pointers: n PrtRay, n * k PrtHit 32-byte aligned, n PrtHitCursor or
+        None); precision and sort as trace_closest_device.  Cursors are not checked on the host."""
+        fn = self._L.prt_trace_multi_sorted_device if sort else self._L.prt_trace_multi_device
+        _check(fn(self._h, d_rays_ptr, d_after_ptr, int(n), int(k), d_hits_ptr, int(count_work), int(precision), stream), self._L)
 
     @property
     def distance_queries(self):

@@ -2168,6 +2168,86 @@ int prt_trace_surface(PrtScene* s, const PrtRay* rays, size_t n, PrtSurface* out
     return trace_batch_host(s, rays, n, out, sizeof(PrtSurface), count_work, PRT_TRACE_SURFACE, "prt_trace_surface");
 }
 
+// One body for the two device multi-hit calls (K7, multi_hit.hip): trace_batch_device's slot, sort-scratch and ordering,
+// with the cursors and k records per ray; `who` names the public function in error messages.
+static int multi_batch_device(PrtScene* s, const void* d_rays, const void* d_after, size_t n, int32_t k, void* d_hits, int count_work,
+                              int precision, void* stream, bool sorted, const char* who) {
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    const std::string w(who);
+    if (k < 1 || k > PRT_MULTI_HIT_MAX) return fail(PRT_E_INVALID, w + ": k must be 1.." + std::to_string(PRT_MULTI_HIT_MAX));
+    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 rays in one batch");
+    if (n && (!d_rays || !d_hits)) return fail(PRT_E_INVALID, w + ": null buffer");
+    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
+    if (reinterpret_cast<uintptr_t>(d_hits) & 31u) // the kernel stores a record 32 bytes at a time
+        return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+    if (precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t we;
+    PrtScene::CallSlot& q = *s->next_slot(st, &we);
+    PRT_HIP_AS(who, we);
+    const bool sort = sorted && n > 1;
+    if (sort) {
+        std::string err;
+        const size_t need = prt::ray_sort_scratch_bytes(n, &err);
+        if (!need) return fail(PRT_E_HIP, err);
+        PRT_HIP_AS(who, s->sort.reserve(need, st));
+    }
+    PRT_HIP_AS(who, q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
+    const uint32_t* d_perm = nullptr;
+    if (sort) {
+        std::string err;
+        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->k64.d.grid_origin, s->k64.d.grid_step, s->sort.get<void>(),
+                               s->sort.cap, st, &err);
+        if (!d_perm) return fail(PRT_E_HIP, err);
+    }
+    const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
+    const PrtHitCursor* after = static_cast<const PrtHitCursor*>(d_after);
+    PrtHit* hits = static_cast<PrtHit*>(d_hits);
+    const bool count = count_work != 0;
+    if (precision == PRT_PRECISION_F32)
+        PRT_HIP_AS(who, prt32::launch_multi_hit(s->k32.d, rays, after, n, k, hits, q.d_ctr.get(), count, s->n_cu, st, d_perm));
+    else
+        PRT_HIP_AS(who, prt::launch_multi_hit(s->k64.d, rays, after, n, k, hits, q.d_ctr.get(), count, s->n_cu, st, d_perm));
+    PRT_HIP_AS(who, q.stop(st));
+    PRT_HIP_AS(who, q.finish(st, count, 0));
+    if (d_perm) PRT_HIP_AS(who, s->sort.used(st));
+    return PRT_OK;
+}
+int prt_trace_multi_device(PrtScene* s, const void* d_rays, const void* d_after, size_t n, int32_t k, void* d_hits, int count_work,
+                           int precision, void* stream) {
+    return multi_batch_device(s, d_rays, d_after, n, k, d_hits, count_work, precision, stream, false, "prt_trace_multi_device");
+}
+int prt_trace_multi_sorted_device(PrtScene* s, const void* d_rays, const void* d_after, size_t n, int32_t k, void* d_hits, int count_work,
+                                  int precision, void* stream) {
+    return multi_batch_device(s, d_rays, d_after, n, k, d_hits, count_work, precision, stream, true, "prt_trace_multi_sorted_device");
+}
+int prt_trace_multi(PrtScene* s, const PrtRay* rays, const PrtHitCursor* after, size_t n, int32_t k, PrtHit* hits, int count_work) {
+    static_assert(sizeof(PrtHitCursor) == 16, "PrtHitCursor is 16 bytes");
+    const char* who = "prt_trace_multi";
+    if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
+    if (k < 1 || k > PRT_MULTI_HIT_MAX) return fail(PRT_E_INVALID, std::string(who) + ": k must be 1.." + std::to_string(PRT_MULTI_HIT_MAX));
+    if (n && (!rays || !hits)) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
+    if (after) // the cursors are checked before anything else: a bad one is refused with or without a device
+        for (size_t i = 0; i < n; ++i) {
+            if (after[i].t != after[i].t) return fail(PRT_E_INVALID, std::string(who) + ": cursor " + std::to_string(i) + " has a NaN t");
+            if (after[i].reserved != 0) return fail(PRT_E_INVALID, std::string(who) + ": cursor " + std::to_string(i) + " has a nonzero reserved field");
+        }
+    int rc = require_uploaded(s, who);
+    if (rc) return rc;
+    if (n == 0) return PRT_OK;
+    Staging b;
+    void* dr = b.in(rays, n * sizeof(PrtRay));
+    void* da = b.in(after, n * sizeof(PrtHitCursor));
+    void* dh = b.out(n * (size_t)k * sizeof(PrtHit));
+    if ((rc = b.status(who)) ||
+        (rc = multi_batch_device(s, dr, da, n, k, dh, count_work, PRT_PRECISION_F64, nullptr, false, "prt_trace_multi_device")))
+        return rc;
+    b.sync();
+    b.down(hits, dh, n * (size_t)k * sizeof(PrtHit));
+    return b.status(who);
+}
+
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {
     int rc = require_uploaded(s, "prt_sample_lights");
     if (rc) return rc;

@@ -126,6 +126,17 @@ Hittable::DeviceCache& Hittable::Device() const {
     return *cache_;
 }
 
+// A HitRecord from the device's PrtHit and the host's triangle (Hit and Hits).
+static void FillRecord(const Ray& ray, const PrtHit& h, const Triangle& t, HitRecord& record) {
+    record.position = ray(h.t);
+    record.time = h.t;
+    record.material = t.material;
+    record.tangent = t.tangent;
+    record.uv = vec2((1. - h.alpha - h.beta) * t.texCoords[0].x + h.alpha * t.texCoords[1].x + h.beta * t.texCoords[2].x,
+                     (1. - h.alpha - h.beta) * t.texCoords[0].y + h.alpha * t.texCoords[1].y + h.beta * t.texCoords[2].y);
+    record.SetFaceNormal(ray, t.normal);
+}
+
 bool Hittable::Hit(const Ray& ray, Interval domain, HitRecord& record) const {
     DeviceCache& dc = Device();
     dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
@@ -137,15 +148,34 @@ bool Hittable::Hit(const Ray& ray, Interval domain, HitRecord& record) const {
     PrtHit h;
     check(prt_trace_closest(dc.scene, &r, 1, &h, 0), "prt_trace_closest");
     if (h.prim < 0) return false;
-    const Triangle& t = *dc.flat.triangles[(size_t)h.prim];
-    record.position = ray(h.t);
-    record.time = h.t;
-    record.material = t.material;
-    record.tangent = t.tangent;
-    record.uv = vec2((1. - h.alpha - h.beta) * t.texCoords[0].x + h.alpha * t.texCoords[1].x + h.beta * t.texCoords[2].x,
-                     (1. - h.alpha - h.beta) * t.texCoords[0].y + h.alpha * t.texCoords[1].y + h.beta * t.texCoords[2].y);
-    record.SetFaceNormal(ray, t.normal);
+    FillRecord(ray, h, *dc.flat.triangles[(size_t)h.prim], record);
     return true;
+}
+
+std::vector<std::vector<HitRecord>> Hittable::Hits(const std::vector<Ray>& rays, Interval domain, int maxHits) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    std::vector<PrtRay> r(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        r[i].o[0] = rays[i].origin.x; r[i].o[1] = rays[i].origin.y; r[i].o[2] = rays[i].origin.z;
+        r[i].d[0] = rays[i].direction.x; r[i].d[1] = rays[i].direction.y; r[i].d[2] = rays[i].direction.z;
+        r[i].tmin = domain.min;
+        r[i].tmax = domain.max;
+    }
+    const size_t k = maxHits > 0 ? (size_t)maxHits : 0; // (the library refuses a k outside 1..PRT_MULTI_HIT_MAX)
+    std::vector<PrtHit> h(rays.size() * k);
+    check(prt_trace_multi(dc.scene, r.data(), nullptr, r.size(), maxHits, h.data(), 0), "prt_trace_multi");
+    std::vector<std::vector<HitRecord>> out(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i)
+        for (size_t j = 0; j < k && h[i * k + j].prim >= 0; ++j) {
+            out[i].emplace_back();
+            FillRecord(rays[i], h[i * k + j], *dc.flat.triangles[(size_t)h[i * k + j].prim], out[i].back());
+        }
+    return out;
+}
+
+std::vector<HitRecord> Hittable::Hits(const Ray& ray, Interval domain, int maxHits) const {
+    return Hits(std::vector<Ray>(1, ray), domain, maxHits)[0];
 }
 
 std::vector<bool> Hittable::Hit(const std::vector<Ray>& rays, Interval domain, std::vector<HitRecord>& records) const {
