@@ -31,6 +31,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "prt_host.h"
+#include "prt_launch.h"
 
 namespace prt {
 namespace {

@@ -25,16 +25,11 @@
 
 #pragma clang fp contract(off)
 
+#include "prt_launch.h"
+
 namespace prt {
 
-// result of the first phase (device memory; the host reads it back once)
-struct RefitCheck {
-    double lo[3], hi[3]; // bounds of the triangles' padded boxes (HostTri::lo / hi)
-    double scale;        // max(1, largest |coordinate| of those boxes)
-    uint32_t flags;
-    uint32_t pad_;
-};
-static_assert(sizeof(RefitCheck) == 64, "RefitCheck layout (prt_api.cpp mirrors it)");
+// RefitCheck::flags (the struct, the result of the first phase, is in prt_launch.h)
 #define PRT_REFIT_BAD_VERTEX 1u // a coordinate is not finite or beyond 1e18
 #define PRT_REFIT_LIGHT_MOVED 2u // a light triangle's vertex differs bitwise from the resident one
 

@@ -34,6 +34,8 @@
 
 #pragma clang fp contract(off)
 
+#include "prt_launch.h"
+
 namespace prt {
 namespace {
 

@@ -32,6 +32,8 @@
 
 #pragma clang fp contract(off)
 
+#include "prt_launch.h"
+
 namespace prt {
 namespace {
 

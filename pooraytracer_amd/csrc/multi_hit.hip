@@ -41,6 +41,7 @@
 
 #include "../../include/prt.h"
 #include "prt_device.h"
+#include "prt_launch.h"
 
 #ifndef PRT_F32_TU
 #define PRT_F32_TU 0

@@ -21,99 +21,7 @@
 #include <vector>
 
 #include "prt_host.h"
-
-namespace prt {
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
-int render_permutation(int feat);
-int render_lds_budget(int feat, int stack_depth);
-size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
-                  int n_cu, hipStream_t st, const uint32_t* d_perm);
-// K4 (ray_sort.hip): a permutation of a ray batch in which consecutive rays start close together
-size_t ray_sort_scratch_bytes(size_t n, std::string* err);
-const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
-                         size_t scratch_bytes, hipStream_t st, std::string* err);
-void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,
-                   bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
-void launch_finalize(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d64, float* d32,
-                     hipStream_t st);
-void launch_finalize_rays(const DRenderParams& P, const double* d_partial, double* d64, float* d32, hipStream_t st);
-void launch_accumulate(const DCamera& C, const DRenderParams& P, const double* d_partial, double* d_sum, hipStream_t st);
-void launch_resolve(const double* d_sum, size_t n, uint64_t samples, const uint32_t* d_counts, double* d64, float* d32,
-                    uint8_t* d8, hipStream_t st);
-// adaptive sampling: the active pixels of a round (d_seg holds adapt_segments(owned items) words), and one launch's sums
-uint32_t adapt_segments(uint64_t owned_items);
-void launch_adapt_select(const DCamera& C, const DRenderParams& P, const DAdaptRule& R, const double* d_sum,
-                         const double* d_moment, const uint32_t* d_count, uint32_t* d_seg, int32_t* d_list, uint32_t* d_total,
-                         hipStream_t st);
-void launch_accumulate_list(const DRenderParams& P, const double* d_partial, const int32_t* d_list, uint32_t batch,
-                            uint32_t samples, double* d_sum, double* d_moment, uint32_t* d_count, hipStream_t st);
-void launch_accum_variance(const double* d_sum, const double* d_moment, const uint32_t* d_count, size_t npx, uint32_t batch,
-                           float* d_var, hipStream_t st);
-void launch_sample_lights(const DScene& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
-                          hipStream_t st);
-void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
-void launch_features(const DScene& S, const DCamera& C, uint64_t seed_key, int jitter, int spp, float* albedo, float* normal,
-                     float* depth, int32_t* prim, hipStream_t st);
-size_t denoise_scratch_bytes(int w, int h);
-void launch_denoise(int w, int h, const float* rgb, const float* albedo, const float* normal, const float* depth,
-                    int iterations, int demod, const float sigma[4], void* scratch, float* out, hipStream_t st);
-void launch_denoise_guided(int w, int h, const float* rgb, const float* var, const float* albedo, const float* normal,
-                           const float* depth, int iterations, int demod, const float sigma[4], void* scratch, float* out,
-                           float* out_var, hipStream_t st);
-void launch_add_f32(float* dst, const float* src, size_t n, hipStream_t st);
-void launch_material_eval(const DScene& S, int material, const double* wi, const double* wo, const double* uv, size_t n,
-                          uint64_t seed, double* out, hipStream_t st);
-void launch_material_scatter(const DScene& S, int material, const double* rd, const double* normal, const double* tangent,
-                             const double* uv, size_t n, uint64_t seed, double* wi_out, double* att_out, int32_t* ok_out,
-                             hipStream_t st);
-void launch_texture_value(const DScene& S, int texture, const double* uv, size_t n, double* out, hipStream_t st);
-// bvh_refit.hip
-struct RefitCheck {
-    double lo[3], hi[3], scale;
-    uint32_t flags, pad_;
-};
-size_t refit_scratch_bytes();
-// light_tables.hip: thresholds, buckets and verification of the planned tables of a light update
-hipError_t launch_light_tables(const DLightTableBuild& A, hipStream_t st);
-void launch_refit_check(const double* d_verts, uint32_t n, const DLightTriT<double>* d_ltris, uint32_t n_lights, void* d_scratch,
-                        RefitCheck* d_out, hipStream_t st, const double* d_normals, double* d_gather_v, double* d_gather_n);
-void launch_refit_tris(const double* d_verts, const double* d_normals, const uint32_t* d_order, uint32_t n, void* d_tris,
-                       uint32_t tri_stride, DTriShadeT<double>* d_shade, float* d_tbox, const double origin[3], double delta,
-                       hipStream_t st);
-void launch_refit_parents(const DNode* d_nodes, uint32_t n_nodes, uint32_t* d_parent, hipStream_t st);
-void launch_prim_boxes(const double* d_verts, uint32_t n, float* d_boxes, const double origin[3], double delta, hipStream_t st);
-void launch_permute_shade(const DTriShadeT<double>* d_shade_old, const uint32_t* d_old_order, const uint32_t* d_new_order,
-                          uint32_t n, uint32_t* d_inv, DTriShadeT<double>* d_shade_new, hipStream_t st);
-// bvh_build_gpu.hip: the device builder on boxes that are on the device already, on a stream (build_bvh_device: prt_host.h)
-bool build_bvh_device_boxes(const PrimBox* d_boxes, const float box_origin[3], size_t n, DeviceBVH& out, std::string* err,
-                            hipStream_t st);
-hipError_t launch_refit_boxes(DNode* d_nodes, uint32_t n_nodes, const uint32_t* d_parent, uint32_t* d_cnt, const float* d_tbox,
-                              uint32_t n_tris, const float step[3], hipStream_t st);
-void launch_refit_sah(const DNode* d_nodes, uint32_t n_nodes, const float origin[3], const float step[3], void* d_scratch,
-                      double* d_out, hipStream_t st);
-void launch_gather_tris(const DTri* tri_in, const DTriShade* shade_in, const uint32_t* order, uint32_t n, void* tri_out,
-                        uint32_t tri_out_stride, DTriShade* shade_out, hipStream_t st);
-// closest_point.hip: the corner table of a scene that answers distance queries, and K6
-void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint32_t n, DTriCorners* d_out, hipStream_t st);
-hipError_t launch_closest_point(const DScene& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n, PrtClosestPoint* d_out,
-                                DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain, hipStream_t st);
-} // namespace prt
-
-// fp32 fast mode (prt_kernels_f32.hip): K1 and K3 on float records derived from the resident fp64 ones
-namespace prt32 {
-typedef DSceneT<float> Scene32;
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
-int render_lds_budget(int feat, int stack_depth);
-size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
-void launch_trace(const Scene32& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
-                  int n_cu, hipStream_t st, const uint32_t* d_perm);
-void launch_render(const Scene32& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
-                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
-void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
-void launch_convert_shade(const DTriShadeT<double>* in, uint32_t n, DTriShadeT<float>* out, hipStream_t st);
-void launch_convert_reals(const double* in, size_t n, float* out, hipStream_t st);
-} // namespace prt32
+#include "prt_launch.h" // every launcher of the .hip files, declared once
 
 namespace {
 thread_local std::string g_err;
@@ -1975,29 +1883,88 @@ int prt_scene_get_distance_queries(const PrtScene* s, int* on) {
     return PRT_OK;
 }
 
-int prt_closest_point_device(PrtScene* s, const void* d_q, size_t n, void* d_out, int count_work, void* stream) {
-    const char* who = "prt_closest_point_device";
+// ---- the batched queries against the resident BVH (K1, K6, K7): one call frame for the device forms, one for the host forms
+// The device frame: a call slot, K4's order when the call sorts, the entry point's launch, the slot's end.  `refuse(w)` holds
+// the entry point's argument checks (w = `who`, the prefix of every text; it returns PRT_OK or what fail() returned) and
+// `launch(f32, d_ctr, count, d_perm, st)` its kernel launch (a hipError_t); `who` names the public function in every
+// message, a HIP runtime failure included ("<who>: <hip error string>").  d_rays is read only by the sort.
+extern "C++" { // (templates: this part of the file is inside extern "C")
+template <typename Refuse, typename Launch>
+static int batch_device(PrtScene* s, const char* who, const void* d_rays, size_t n, int count_work, int precision, void* stream,
+                        bool sorted, Refuse refuse, Launch launch) {
     int rc = require_uploaded(s, who);
-    if (rc) return rc;
-    const std::string w(who);
-    if (!s->distance_queries || !s->d_corners)
-        return fail(PRT_E_INVALID, w + ": distance queries are off for this scene (prt_scene_set_distance_queries)");
-    if (n && (!d_q || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
-    if (n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 queries in one batch");
-    if (reinterpret_cast<uintptr_t>(d_out) & 31u) // the kernel stores a record 32 bytes at a time
-        return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+    if (rc || (rc = refuse(std::string(who)))) return rc;
+    const bool f32 = precision == PRT_PRECISION_F32;
+    if (f32 && (rc = ensure_f32(s))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipError_t we;
     PrtScene::CallSlot& q = *s->next_slot(st, &we);
     PRT_HIP_AS(who, we);
-    PRT_HIP_AS(who, q.start(st));
+    const bool sort = sorted && n > 1;
+    std::string err;
+    if (sort) {
+        const size_t need = prt::ray_sort_scratch_bytes(n, &err);
+        if (!need) return fail(PRT_E_HIP, err);
+        PRT_HIP_AS(who, s->sort.reserve(need, st));
+    }
+    PRT_HIP_AS(who, q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
+    const uint32_t* d_perm = nullptr;
+    if (sort) {
+        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->k64.d.grid_origin, s->k64.d.grid_step, s->sort.get<void>(),
+                               s->sort.cap, st, &err);
+        if (!d_perm) return fail(PRT_E_HIP, err);
+    }
     const bool count = count_work != 0;
-    PRT_HIP_AS(who, prt::launch_closest_point(s->k64.d, s->d_corners, static_cast<const PrtPointQuery*>(d_q), n,
-                                              static_cast<PrtClosestPoint*>(d_out), q.d_ctr.get(), count, s->stack_need, s->n_cu,
-                                              dev_env("PRT_TUNE_CLOSEST_PLAIN") != nullptr, st)); // (developer: the plain schedule, for A/B runs)
+    PRT_HIP_AS(who, launch(f32, q.d_ctr.get(), count, d_perm, st));
     PRT_HIP_AS(who, q.stop(st));
     PRT_HIP_AS(who, q.finish(st, count, 0));
+    if (d_perm) PRT_HIP_AS(who, s->sort.used(st));
     return PRT_OK;
+}
+// The checks the ray-batch entry points share, in the order that decides which message a doubly-wrong call gets.
+// `aligned32`: the kernel stores a record 32 bytes at a time.
+static int refuse_ray_batch(const std::string& w, bool sorted, size_t n, const void* d_rays, const void* d_out, int precision,
+                            bool aligned32) {
+    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 rays in one batch");
+    if (n && (!d_rays || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
+    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
+    if (aligned32 && (reinterpret_cast<uintptr_t>(d_out) & 31u)) return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+    return PRT_OK;
+}
+// The host frame, behind the entry point's own checks (n > 0): device copies of the inputs (in1 may be null), room for the
+// output, `device(d_in0, d_in1, d_out)` = the entry point's device form on the null stream, and the output back.
+template <typename Device>
+static int batch_host(const char* who, const void* in0, size_t in0_bytes, const void* in1, size_t in1_bytes, void* out,
+                      size_t out_bytes, Device device) {
+    Staging b;
+    void* d_in0 = b.in(in0, in0_bytes);
+    void* d_in1 = b.in(in1, in1_bytes);
+    void* d_out = b.out(out_bytes);
+    int rc;
+    if ((rc = b.status(who)) || (rc = device(d_in0, d_in1, d_out))) return rc;
+    b.sync();
+    b.down(out, d_out, out_bytes);
+    return b.status(who);
+}
+} // extern "C++"
+
+int prt_closest_point_device(PrtScene* s, const void* d_q, size_t n, void* d_out, int count_work, void* stream) {
+    return batch_device(
+        s, "prt_closest_point_device", nullptr, n, count_work, PRT_PRECISION_F64, stream, false,
+        [&](const std::string& w) {
+            if (!s->distance_queries || !s->d_corners)
+                return fail(PRT_E_INVALID, w + ": distance queries are off for this scene (prt_scene_set_distance_queries)");
+            if (n && (!d_q || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
+            if (n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 queries in one batch");
+            if (reinterpret_cast<uintptr_t>(d_out) & 31u) // the kernel stores a record 32 bytes at a time
+                return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+            return PRT_OK;
+        },
+        [&](bool, DCounters* d_ctr, bool count, const uint32_t*, hipStream_t st) {
+            return prt::launch_closest_point(s->k64.d, s->d_corners, static_cast<const PrtPointQuery*>(d_q), n,
+                                             static_cast<PrtClosestPoint*>(d_out), d_ctr, count, s->stack_need, s->n_cu,
+                                             dev_env("PRT_TUNE_CLOSEST_PLAIN") != nullptr, st); // (developer: the plain schedule, for A/B runs)
+        });
 }
 
 int prt_closest_point(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtClosestPoint* out, int count_work) {
@@ -2012,18 +1979,12 @@ int prt_closest_point(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtClosest
             return fail(PRT_E_INVALID, "prt_closest_point: query " + std::to_string(i) + " has a non-finite point");
         if (!(q.max_dist >= 0.0)) return fail(PRT_E_INVALID, "prt_closest_point: query " + std::to_string(i) + " has a negative or NaN max_dist");
     }
-    int rc = require_uploaded(s, who);
-    if (rc) return rc;
+    if (const int rc = require_uploaded(s, who)) return rc;
     if (!s->distance_queries || !s->d_corners)
         return fail(PRT_E_INVALID, "prt_closest_point: distance queries are off for this scene (prt_scene_set_distance_queries)");
     if (n == 0) return PRT_OK;
-    Staging b;
-    void* dq = b.in(qs, n * sizeof(PrtPointQuery));
-    void* dout = b.out(n * sizeof(PrtClosestPoint));
-    if ((rc = b.status(who)) || (rc = prt_closest_point_device(s, dq, n, dout, count_work, nullptr))) return rc;
-    b.sync();
-    b.down(out, dout, n * sizeof(PrtClosestPoint));
-    return b.status(who);
+    return batch_host(who, qs, n * sizeof(PrtPointQuery), nullptr, 0, out, n * sizeof(PrtClosestPoint),
+                      [&](void* dq, void*, void* dout) { return prt_closest_point_device(s, dq, n, dout, count_work, nullptr); });
 }
 
 int prt_scene_light_update_info(const PrtScene* s, PrtLightUpdateInfo* out) {
@@ -2066,10 +2027,19 @@ int prt_trace_closest_device(PrtScene* s, const void* d_rays, size_t n, void* d_
     return prt_trace_closest_device_prec(s, d_rays, n, d_hits, count_work, PRT_PRECISION_F64, stream);
 }
 
-// One body for the six device batch calls: `mode` (PRT_TRACE_*) picks what K1 writes per ray — a PrtHit, the any-hit byte
-// (any-hit traversal) or a PrtSurface; `who` names the public function in error messages.
+// The six device calls of K1: `mode` (PRT_TRACE_*) picks what K1 writes per ray — a PrtHit, the any-hit byte (any-hit
+// traversal) or a PrtSurface; `who` names the public function in error messages.
 static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
-                              bool sorted, int mode, const char* who);
+                              bool sorted, int mode, const char* who) {
+    return batch_device(
+        s, who, d_rays, n, count_work, precision, stream, sorted,
+        [&](const std::string& w) { return refuse_ray_batch(w, sorted, n, d_rays, d_out, precision, mode == PRT_TRACE_SURFACE); },
+        [&](bool f32, DCounters* d_ctr, bool count, const uint32_t* d_perm, hipStream_t st) {
+            const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
+            return f32 ? prt32::launch_trace(s->k32.d, rays, n, d_out, d_ctr, count, mode, s->n_cu, st, d_perm)
+                       : prt::launch_trace(s->k64.d, rays, n, d_out, d_ctr, count, mode, s->n_cu, st, d_perm);
+        });
+}
 int prt_trace_closest_device_prec(PrtScene* s, const void* d_rays, size_t n, void* d_hits, int count_work, int precision,
                                   void* stream) {
     return trace_batch_device(s, d_rays, n, d_hits, count_work, precision, stream, false, PRT_TRACE_CLOSEST, "prt_trace_closest_device");
@@ -2096,66 +2066,18 @@ int prt_trace_surface_sorted_device(PrtScene* s, const void* d_rays, size_t n, v
     return trace_batch_device(s, d_rays, n, d_out, count_work, precision, stream, true, PRT_TRACE_SURFACE,
                               "prt_trace_surface_sorted_device");
 }
-static int trace_batch_device(PrtScene* s, const void* d_rays, size_t n, void* d_out, int count_work, int precision, void* stream,
-                              bool sorted, int mode, const char* who) {
-    int rc = require_uploaded(s, who);
-    if (rc) return rc;
-    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, std::string(who) + ": more than 2^32 - 1 rays in one batch");
-    if (n && (!d_rays || !d_out)) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
-    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, std::string(who) + ": unsupported precision");
-    if (mode == PRT_TRACE_SURFACE && (reinterpret_cast<uintptr_t>(d_out) & 31u)) // the kernel stores a record 32 bytes at a time
-        return fail(PRT_E_INVALID, std::string(who) + ": output buffer is not 32-byte aligned");
-    if (precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t we;
-    PrtScene::CallSlot& q = *s->next_slot(st, &we);
-    PRT_HIP(we);
-    const bool sort = sorted && n > 1;
-    if (sort) {
-        std::string err;
-        const size_t need = prt::ray_sort_scratch_bytes(n, &err);
-        if (!need) return fail(PRT_E_HIP, err);
-        PRT_HIP_AS(who, s->sort.reserve(need, st));
-    }
-    PRT_HIP(q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
-    const uint32_t* d_perm = nullptr;
-    if (sort) {
-        std::string err;
-        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->k64.d.grid_origin, s->k64.d.grid_step, s->sort.get<void>(),
-                               s->sort.cap, st, &err);
-        if (!d_perm) return fail(PRT_E_HIP, err);
-    }
-    const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
-    const bool count = count_work != 0;
-    if (precision == PRT_PRECISION_F32)
-        prt32::launch_trace(s->k32.d, rays, n, d_out, q.d_ctr.get(), count, mode, s->n_cu, st, d_perm);
-    else
-        prt::launch_trace(s->k64.d, rays, n, d_out, q.d_ctr.get(), count, mode, s->n_cu, st, d_perm);
-    PRT_HIP(hipGetLastError());
-    PRT_HIP(q.stop(st));
-    PRT_HIP(q.finish(st, count, 0));
-    if (d_perm) PRT_HIP(s->sort.used(st));
-    return PRT_OK;
-}
 
-// One body for the three host-buffer batch calls (fp64, unsorted): `elem` = bytes per ray of the output (a PrtHit, the
-// any-hit byte, or a PrtSurface); `who` names the public function in error messages, and its device call (`who`_device)
-// does the work.
+// The three host-buffer calls of K1 (fp64, unsorted): `elem` = bytes per ray of the output (a PrtHit, the any-hit byte, or
+// a PrtSurface); `who` names the public function in error messages, and its device call (`who`_device) does the work.
 static int trace_batch_host(PrtScene* s, const PrtRay* rays, size_t n, void* out, size_t elem, int count_work, int mode,
                             const char* who) {
-    int rc = require_uploaded(s, who);
-    if (rc) return rc;
+    if (const int rc = require_uploaded(s, who)) return rc;
     if (n == 0) return PRT_OK;
     if (!rays || !out) return fail(PRT_E_INVALID, std::string(who) + ": null buffer");
-    Staging b;
-    void* dr = b.in(rays, n * sizeof(PrtRay));
-    void* dh = b.out(n * elem);
     const std::string dev = std::string(who) + "_device";
-    if ((rc = b.status(who)) || (rc = trace_batch_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr, false, mode, dev.c_str())))
-        return rc;
-    b.sync();
-    b.down(out, dh, n * elem);
-    return b.status(who);
+    return batch_host(who, rays, n * sizeof(PrtRay), nullptr, 0, out, n * elem, [&](void* dr, void*, void* dh) {
+        return trace_batch_device(s, dr, n, dh, count_work, PRT_PRECISION_F64, nullptr, false, mode, dev.c_str());
+    });
 }
 int prt_trace_closest(PrtScene* s, const PrtRay* rays, size_t n, PrtHit* hits, int count_work) {
     return trace_batch_host(s, rays, n, hits, sizeof(PrtHit), count_work, PRT_TRACE_CLOSEST, "prt_trace_closest");
@@ -2168,51 +2090,22 @@ int prt_trace_surface(PrtScene* s, const PrtRay* rays, size_t n, PrtSurface* out
     return trace_batch_host(s, rays, n, out, sizeof(PrtSurface), count_work, PRT_TRACE_SURFACE, "prt_trace_surface");
 }
 
-// One body for the two device multi-hit calls (K7, multi_hit.hip): trace_batch_device's slot, sort-scratch and ordering,
-// with the cursors and k records per ray; `who` names the public function in error messages.
+// The two device multi-hit calls (K7, multi_hit.hip): K1's frame with the cursors and k records per ray.
 static int multi_batch_device(PrtScene* s, const void* d_rays, const void* d_after, size_t n, int32_t k, void* d_hits, int count_work,
                               int precision, void* stream, bool sorted, const char* who) {
-    int rc = require_uploaded(s, who);
-    if (rc) return rc;
-    const std::string w(who);
-    if (k < 1 || k > PRT_MULTI_HIT_MAX) return fail(PRT_E_INVALID, w + ": k must be 1.." + std::to_string(PRT_MULTI_HIT_MAX));
-    if (sorted && n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 rays in one batch");
-    if (n && (!d_rays || !d_hits)) return fail(PRT_E_INVALID, w + ": null buffer");
-    if (precision != PRT_PRECISION_F64 && precision != PRT_PRECISION_F32) return fail(PRT_E_INVALID, w + ": unsupported precision");
-    if (reinterpret_cast<uintptr_t>(d_hits) & 31u) // the kernel stores a record 32 bytes at a time
-        return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
-    if (precision == PRT_PRECISION_F32 && (rc = ensure_f32(s))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t we;
-    PrtScene::CallSlot& q = *s->next_slot(st, &we);
-    PRT_HIP_AS(who, we);
-    const bool sort = sorted && n > 1;
-    if (sort) {
-        std::string err;
-        const size_t need = prt::ray_sort_scratch_bytes(n, &err);
-        if (!need) return fail(PRT_E_HIP, err);
-        PRT_HIP_AS(who, s->sort.reserve(need, st));
-    }
-    PRT_HIP_AS(who, q.start(st)); // (the sort is inside the timed region: kernel_ms is keys + sort + trace)
-    const uint32_t* d_perm = nullptr;
-    if (sort) {
-        std::string err;
-        d_perm = prt::ray_sort(static_cast<const PrtRay*>(d_rays), n, s->k64.d.grid_origin, s->k64.d.grid_step, s->sort.get<void>(),
-                               s->sort.cap, st, &err);
-        if (!d_perm) return fail(PRT_E_HIP, err);
-    }
-    const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
-    const PrtHitCursor* after = static_cast<const PrtHitCursor*>(d_after);
-    PrtHit* hits = static_cast<PrtHit*>(d_hits);
-    const bool count = count_work != 0;
-    if (precision == PRT_PRECISION_F32)
-        PRT_HIP_AS(who, prt32::launch_multi_hit(s->k32.d, rays, after, n, k, hits, q.d_ctr.get(), count, s->n_cu, st, d_perm));
-    else
-        PRT_HIP_AS(who, prt::launch_multi_hit(s->k64.d, rays, after, n, k, hits, q.d_ctr.get(), count, s->n_cu, st, d_perm));
-    PRT_HIP_AS(who, q.stop(st));
-    PRT_HIP_AS(who, q.finish(st, count, 0));
-    if (d_perm) PRT_HIP_AS(who, s->sort.used(st));
-    return PRT_OK;
+    return batch_device(
+        s, who, d_rays, n, count_work, precision, stream, sorted,
+        [&](const std::string& w) {
+            if (k < 1 || k > PRT_MULTI_HIT_MAX) return fail(PRT_E_INVALID, w + ": k must be 1.." + std::to_string(PRT_MULTI_HIT_MAX));
+            return refuse_ray_batch(w, sorted, n, d_rays, d_hits, precision, true);
+        },
+        [&](bool f32, DCounters* d_ctr, bool count, const uint32_t* d_perm, hipStream_t st) {
+            const PrtRay* rays = static_cast<const PrtRay*>(d_rays);
+            const PrtHitCursor* after = static_cast<const PrtHitCursor*>(d_after);
+            PrtHit* hits = static_cast<PrtHit*>(d_hits);
+            return f32 ? prt32::launch_multi_hit(s->k32.d, rays, after, n, k, hits, d_ctr, count, s->n_cu, st, d_perm)
+                       : prt::launch_multi_hit(s->k64.d, rays, after, n, k, hits, d_ctr, count, s->n_cu, st, d_perm);
+        });
 }
 int prt_trace_multi_device(PrtScene* s, const void* d_rays, const void* d_after, size_t n, int32_t k, void* d_hits, int count_work,
                            int precision, void* stream) {
@@ -2233,19 +2126,12 @@ int prt_trace_multi(PrtScene* s, const PrtRay* rays, const PrtHitCursor* after, 
             if (after[i].t != after[i].t) return fail(PRT_E_INVALID, std::string(who) + ": cursor " + std::to_string(i) + " has a NaN t");
             if (after[i].reserved != 0) return fail(PRT_E_INVALID, std::string(who) + ": cursor " + std::to_string(i) + " has a nonzero reserved field");
         }
-    int rc = require_uploaded(s, who);
-    if (rc) return rc;
+    if (const int rc = require_uploaded(s, who)) return rc;
     if (n == 0) return PRT_OK;
-    Staging b;
-    void* dr = b.in(rays, n * sizeof(PrtRay));
-    void* da = b.in(after, n * sizeof(PrtHitCursor));
-    void* dh = b.out(n * (size_t)k * sizeof(PrtHit));
-    if ((rc = b.status(who)) ||
-        (rc = multi_batch_device(s, dr, da, n, k, dh, count_work, PRT_PRECISION_F64, nullptr, false, "prt_trace_multi_device")))
-        return rc;
-    b.sync();
-    b.down(hits, dh, n * (size_t)k * sizeof(PrtHit));
-    return b.status(who);
+    return batch_host(who, rays, n * sizeof(PrtRay), after, n * sizeof(PrtHitCursor), hits, n * (size_t)k * sizeof(PrtHit),
+                      [&](void* dr, void* da, void* dh) {
+                          return multi_batch_device(s, dr, da, n, k, dh, count_work, PRT_PRECISION_F64, nullptr, false, "prt_trace_multi_device");
+                      });
 }
 
 int prt_sample_lights(PrtScene* s, const double* origins, size_t n, uint64_t seed, PrtLightSample* out) {

@@ -20,6 +20,8 @@
 
 #include <cmath>
 
+#include "prt_launch.h"
+
 namespace {
 
 #define PRT_DN_TILE 16

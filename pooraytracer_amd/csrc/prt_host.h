@@ -123,17 +123,3 @@ inline uint64_t seed_key(uint64_t seed) {
 }
 
 } // namespace prt
-
-// K7 (multi_hit.hip / multi_hit_f32.hip): one batch of rays, k records per ray into d_out (32-byte aligned), d_after null
-// or one cursor per ray, d_perm K4's order or null.  The signatures use the HIP runtime's types, so they are declared for
-// the translation units that include it before this header (prt_api.cpp); the host-only ones do not see them.
-#ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H
-namespace prt {
-hipError_t launch_multi_hit(const DSceneT<double>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,
-                            DCounters* d_ctr, bool count, int n_cu, hipStream_t st, const uint32_t* d_perm);
-}
-namespace prt32 {
-hipError_t launch_multi_hit(const DSceneT<float>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,
-                            DCounters* d_ctr, bool count, int n_cu, hipStream_t st, const uint32_t* d_perm);
-}
-#endif

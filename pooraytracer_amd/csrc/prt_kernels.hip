@@ -30,6 +30,7 @@
 
 #include "../../include/prt.h"
 #include "prt_device.h"
+#include "prt_launch.h"
 
 // This file is compiled twice: as it stands (fp64, the reference's arithmetic: namespace prt, every kernel) and through
 // prt_kernels_f32.hip with PRT_REAL = float (the fp32 fast mode: namespace prt32, K1 and K3 only — K5, the tone map and
@@ -1592,17 +1593,21 @@ int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_dep
 }
 
 // One batch of rays through K1: `mode` (PRT_TRACE_*, prt_types.h) picks the closest-hit form (d_out = one PrtHit per ray), the
-// any-hit form (one byte per ray) or the surface form (one PrtSurface per ray, 32-byte aligned).
-void launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
-                  int n_cu, hipStream_t st, const uint32_t* d_perm) {
-    if (n == 0) return;
+// any-hit form (one byte per ray) or the surface form (one PrtSurface per ray, 32-byte aligned).  Returns hipGetLastError()
+// behind the launch (an empty batch launches nothing and still polls, as its callers always have).
+hipError_t launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
+                        int n_cu, hipStream_t st, const uint32_t* d_perm) {
+    if (n == 0) return hipGetLastError();
     size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
     const size_t per_cu = std::max<size_t>(1, (160u * 1024u) / (sizeof(uint32_t) * PRT_STACK_DEPTH * PRT_BLOCK)); // LDS stacks per CU
     unsigned grid = (unsigned)std::min<size_t>(want, (size_t)n_cu * per_cu);
     const bool pad = S.tri_stride == PRT_TRI_PAD_STRIDE(real) && sizeof(DTri) != PRT_TRI_PAD_STRIDE(real);
     const bool any_hit = mode == PRT_TRACE_ANY;
     const int pick = (count ? 4 : 0) | (pad ? 2 : 0) | (any_hit ? 1 : 0);
-    auto go = [&](auto k, auto* out) { hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, out, d_ctr, d_perm); };
+    auto go = [&](auto k, auto* out) {
+        hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), 0, st, S, d_rays, n, out, d_ctr, d_perm);
+        return hipGetLastError();
+    };
     PrtHit* hits = static_cast<PrtHit*>(d_out);
     uint8_t* bytes = static_cast<uint8_t*>(d_out);
     if (mode == PRT_TRACE_SURFACE) {

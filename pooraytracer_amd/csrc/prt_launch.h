@@ -1,0 +1,120 @@
+// prt_launch.h — every launcher and device-side helper that prt_api.cpp calls, declared once.  Declarations only: the
+// file that defines a function includes this header too, so a definition that drifts from its declaration (a default
+// argument, a struct passed by value) does not compile.  Scene types are spelled with their precision, so the fp64 and the
+// fp32 translation units read the same text.  Default arguments live here and nowhere else.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string> // ray_sort's and the device builder's `std::string* err`
+
+#include "../../include/prt.h"
+#include "prt_types.h"
+
+namespace prt {
+// prt_kernels.hip
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
+int render_permutation(int feat);
+int render_lds_budget(int feat, int stack_depth);
+size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
+hipError_t launch_trace(const DSceneT<double>& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
+                        int n_cu, hipStream_t st, const uint32_t* d_perm);
+// K4 (ray_sort.hip): a permutation of a ray batch in which consecutive rays start close together
+size_t ray_sort_scratch_bytes(size_t n, std::string* err);
+const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
+                         size_t scratch_bytes, hipStream_t st, std::string* err);
+void launch_render(const DSceneT<double>& S, const DCameraT<double>& C, const DRenderParamsT<double>& P, double* d_partial,
+                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
+void launch_finalize(const DCameraT<double>& C, const DRenderParamsT<double>& P, const double* d_partial, double* d64, float* d32,
+                     hipStream_t st);
+void launch_finalize_rays(const DRenderParamsT<double>& P, const double* d_partial, double* d64, float* d32, hipStream_t st);
+void launch_accumulate(const DCameraT<double>& C, const DRenderParamsT<double>& P, const double* d_partial, double* d_sum,
+                       hipStream_t st);
+void launch_resolve(const double* d_sum, size_t n, uint64_t samples, const uint32_t* d_counts, double* d64, float* d32,
+                    uint8_t* d8, hipStream_t st);
+// adaptive sampling: the active pixels of a round (d_seg holds adapt_segments(owned items) words), and one launch's sums
+uint32_t adapt_segments(uint64_t owned_items);
+void launch_adapt_select(const DCameraT<double>& C, const DRenderParamsT<double>& P, const DAdaptRule& R, const double* d_sum,
+                         const double* d_moment, const uint32_t* d_count, uint32_t* d_seg, int32_t* d_list, uint32_t* d_total,
+                         hipStream_t st);
+void launch_accumulate_list(const DRenderParamsT<double>& P, const double* d_partial, const int32_t* d_list, uint32_t batch,
+                            uint32_t samples, double* d_sum, double* d_moment, uint32_t* d_count, hipStream_t st);
+void launch_accum_variance(const double* d_sum, const double* d_moment, const uint32_t* d_count, size_t npx, uint32_t batch,
+                           float* d_var, hipStream_t st);
+void launch_sample_lights(const DSceneT<double>& S, const double* d_origins, size_t n, uint64_t seed, PrtLightSample* d_out,
+                          hipStream_t st);
+void launch_tonemap(const float* d_in, size_t n, uint8_t* d_out, hipStream_t st);
+void launch_features(const DSceneT<double>& S, const DCameraT<double>& C, uint64_t seed_key, int jitter, int spp, float* albedo,
+                     float* normal, float* depth, int32_t* prim, hipStream_t st);
+void launch_add_f32(float* dst, const float* src, size_t n, hipStream_t st);
+void launch_material_eval(const DSceneT<double>& S, int material, const double* wi, const double* wo, const double* uv, size_t n,
+                          uint64_t seed, double* out, hipStream_t st);
+void launch_material_scatter(const DSceneT<double>& S, int material, const double* rd, const double* normal, const double* tangent,
+                             const double* uv, size_t n, uint64_t seed, double* wi_out, double* att_out, int32_t* ok_out,
+                             hipStream_t st);
+void launch_texture_value(const DSceneT<double>& S, int texture, const double* uv, size_t n, double* out, hipStream_t st);
+// prt_denoise.hip
+size_t denoise_scratch_bytes(int w, int h);
+void launch_denoise(int w, int h, const float* rgb, const float* albedo, const float* normal, const float* depth,
+                    int iterations, int demod, const float sigma[4], void* scratch, float* out, hipStream_t st);
+void launch_denoise_guided(int w, int h, const float* rgb, const float* var, const float* albedo, const float* normal,
+                           const float* depth, int iterations, int demod, const float sigma[4], void* scratch, float* out,
+                           float* out_var, hipStream_t st);
+// light_tables.hip: thresholds, buckets and verification of the planned tables of a light update
+hipError_t launch_light_tables(const DLightTableBuild& A, hipStream_t st);
+// bvh_refit.hip.  RefitCheck: result of the first phase (device memory; the host reads it back once)
+struct RefitCheck {
+    double lo[3], hi[3]; // bounds of the triangles' padded boxes (HostTri::lo / hi)
+    double scale;        // max(1, largest |coordinate| of those boxes)
+    uint32_t flags;      // bit 0: a coordinate is not finite or beyond 1e18; bit 1: a light triangle's vertex moved
+    uint32_t pad_;
+};
+static_assert(sizeof(RefitCheck) == 64, "RefitCheck layout (the kernels write it, prt_api.cpp reads it back)");
+size_t refit_scratch_bytes();
+void launch_refit_check(const double* d_verts, uint32_t n, const DLightTriT<double>* d_ltris, uint32_t n_lights, void* d_scratch,
+                        RefitCheck* d_out, hipStream_t st, const double* d_normals, double* d_gather_v, double* d_gather_n);
+void launch_refit_tris(const double* d_verts, const double* d_normals, const uint32_t* d_order, uint32_t n, void* d_tris,
+                       uint32_t tri_stride, DTriShadeT<double>* d_shade, float* d_tbox, const double origin[3], double delta,
+                       hipStream_t st);
+void launch_refit_parents(const DNode* d_nodes, uint32_t n_nodes, uint32_t* d_parent, hipStream_t st);
+void launch_prim_boxes(const double* d_verts, uint32_t n, float* d_boxes, const double origin[3], double delta, hipStream_t st);
+void launch_permute_shade(const DTriShadeT<double>* d_shade_old, const uint32_t* d_old_order, const uint32_t* d_new_order,
+                          uint32_t n, uint32_t* d_inv, DTriShadeT<double>* d_shade_new, hipStream_t st);
+hipError_t launch_refit_boxes(DNode* d_nodes, uint32_t n_nodes, const uint32_t* d_parent, uint32_t* d_cnt, const float* d_tbox,
+                              uint32_t n_tris, const float step[3], hipStream_t st);
+void launch_refit_sah(const DNode* d_nodes, uint32_t n_nodes, const float origin[3], const float step[3], void* d_scratch,
+                      double* d_out, hipStream_t st);
+// bvh_build_gpu.hip: the device builder on boxes that are on the device already, on a stream (build_bvh_device: prt_host.h,
+// which also defines the two structs)
+struct PrimBox;
+struct DeviceBVH;
+bool build_bvh_device_boxes(const PrimBox* d_boxes, const float box_origin[3], size_t n, DeviceBVH& out, std::string* err,
+                            hipStream_t st);
+void launch_gather_tris(const DTriT<double>* tri_in, const DTriShadeT<double>* shade_in, const uint32_t* order, uint32_t n,
+                        void* tri_out, uint32_t tri_out_stride, DTriShadeT<double>* shade_out, hipStream_t st);
+// closest_point.hip: the corner table of a scene that answers distance queries, and K6
+void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint32_t n, DTriCorners* d_out, hipStream_t st);
+hipError_t launch_closest_point(const DSceneT<double>& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n,
+                                PrtClosestPoint* d_out, DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain,
+                                hipStream_t st);
+// K7 (multi_hit.hip / multi_hit_f32.hip): one batch of rays, k records per ray into d_out (32-byte aligned), d_after null
+// or one cursor per ray, d_perm K4's order or null
+hipError_t launch_multi_hit(const DSceneT<double>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,
+                            DCounters* d_ctr, bool count, int n_cu, hipStream_t st, const uint32_t* d_perm);
+} // namespace prt
+
+// fp32 fast mode (prt_kernels_f32.hip): K1 and K3 on float records derived from the resident fp64 ones
+namespace prt32 {
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays);
+int render_permutation(int feat);
+int render_lds_budget(int feat, int stack_depth);
+size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
+hipError_t launch_trace(const DSceneT<float>& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
+                        int n_cu, hipStream_t st, const uint32_t* d_perm);
+void launch_render(const DSceneT<float>& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
+                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays = false);
+void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
+void launch_convert_shade(const DTriShadeT<double>* in, uint32_t n, DTriShadeT<float>* out, hipStream_t st);
+void launch_convert_reals(const double* in, size_t n, float* out, hipStream_t st);
+hipError_t launch_multi_hit(const DSceneT<float>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,
+                            DCounters* d_ctr, bool count, int n_cu, hipStream_t st, const uint32_t* d_perm);
+} // namespace prt32

@@ -13,6 +13,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/prt.h"
+#include "prt_launch.h"
 
 namespace prt {
 
