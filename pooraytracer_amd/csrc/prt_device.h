@@ -212,6 +212,43 @@ PRT_DEV bool tri_test(const DTri* __restrict__ T, d3 o, d3 d, real tmin, real tm
     return true;
 }
 
+// The same test for the leaf loop of the fp64 one-pass render kernels (Trav::test_leaf_pp): the record's first 32 bytes come
+// in by reference, and the inside test is ONE conjunction of ordered comparisons.  Written as above — NaN rejection, then
+// (alpha < 0) || (beta < 0) || (alpha + beta > 1) — the compiler folds the two sign tests into a minimum and quiets both
+// operands first (two v_max_f64 x, x per test, after the NaN check has already excluded them).  Same decisions: a NaN
+// barycentric fails `>= 0` as it failed the NaN check; alpha + beta is NaN only for a NaN or for +inf - inf, and either side
+// of that is rejected by both forms.
+// The VALUES are tri_test's as the render kernels compile it, operation for operation, which has to be said explicitly:
+// under -ffp-contract=fast the compiler is free to turn x*X + y*Y + z*Z into fma(z, Z, fma(x, X, y*Y)) or into
+// fma(z, Z, fma(y, Y, x*X)); in tri_test, inlined into test_leaf, it takes the first for all four sums, and in this function,
+// written with the same infix expressions, it took the second for the two dot products (33 pixels of a 40 x 32 frame left
+// the previous build's, tests/test_gpu_wave_loop.py).  So the four sums are spelled as the fused operations tri_test gets.
+PRT_DEV real dot_yxz(real ax, real ay, real az, real bx, real by, real bz) { return fma(az, bz, fma(ax, bx, ay * by)); }
+PRT_DEV bool tri_test_ord(const DTri* __restrict__ T, d3 o, d3 d, real tmin, real tmax, real& t_out, real& a_out,
+                          real& b_out, const real4& q0, uint32_t* n_full) {
+    const real4* q = reinterpret_cast<const real4*>(T);
+    real4 q1 = q[1];
+    real denom = dot_yxz(q0.x, q0.y, q0.z, d.x, d.y, d.z);
+    if (fabs(denom) < RL(1e-8)) return false;
+    real t = ieee_div(q0.w - dot_yxz(q0.x, q0.y, q0.z, o.x, o.y, o.z), denom);
+    if (!(tmin <= t && t <= tmax)) return false;
+    if (n_full) ++*n_full;
+    const real4 q2 = q[2];
+    const d3 p = mk3(fma(d.x, t, o.x), fma(d.y, t, o.y), fma(d.z, t, o.z)); // o + d * t
+    const real alpha = dot_yxz(p.x, p.y, p.z, q1.x, q1.y, q1.z) - q1.w;
+    const real beta = dot_yxz(p.x, p.y, p.z, q2.x, q2.y, q2.z) - q2.w;
+    if (!(alpha >= 0 && beta >= 0 && alpha + beta <= 1)) return false;
+    t_out = t;
+    a_out = alpha;
+    b_out = beta;
+    return true;
+}
+
+// The lanes of the wave for which `p` holds, as a mask.  Taken straight from a comparison this is the comparison's own
+// result (one v_cmp into a scalar pair); __ballot() takes an int and puts a select and a second compare in front.  A bool
+// that has lived across branches costs that select and compare either way: take masks from comparisons of lane values.
+PRT_DEV unsigned long long lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // Conservative double -> float conversions (round-to-nearest error <= 2^-24 relative, widened by 2^-22).
 PRT_DEV float f32_up(real x) {
     const float f = (float)x;
@@ -414,12 +451,55 @@ struct Trav {
         return stop;
     }
 
-    // Leaf round of this lane: the triangles of the leaf it is parked at, then pop.
+    // test_leaf for the fp64 one-pass render kernels (k_render, WAVE_DIET): the same tests of the same triangles in the same
+    // order, the same six loads per triangle requested in the same order.  The loop body is written out twice and the plane
+    // fetched ahead alternates between two register sets (qa is tested while qb arrives, then qb while qa arrives), so
+    // nothing rotates a "next" plane into a "current" one per iteration (four v_mov_b64 in test_leaf); one record address
+    // runs through the leaf; the inside test is tri_test_ord's.  A leaf of an odd number of triangles leaves the loop
+    // after the first half of the body, an even one after the second.
     template <bool COUNT>
+    PRT_DEV bool test_leaf_pp(const DScene& S, int32_t ref, WorkCount& wc, real tmin_use, bool any_hit) {
+        const uint32_t enc = ~(uint32_t)ref;
+        const uint32_t first = enc >> 3, cnt = (enc & 7u) + 1u;
+        constexpr uint32_t STRIDE = PAD ? PRT_TRI_PAD_STRIDE(real) : (uint32_t)sizeof(DTri);
+        const char* rec = reinterpret_cast<const char*>(tri_at<PAD>(S, first));
+        bool stop = false;
+        uint32_t i = 0;
+        auto test = [&](const real4& q0) {
+            real t, al, be;
+            if (COUNT) wc.tris++;
+            if (tri_test_ord(reinterpret_cast<const DTri*>(rec), o, d, tmin_use, hit.t, t, al, be, q0, COUNT ? &wc.tris_full : nullptr)) {
+                hit.t = t;
+                if (!any_hit) { // (as in test_leaf: a shadow traversal leaves the shading point's barycentrics alone)
+                    hit.alpha = al;
+                    hit.beta = be;
+                }
+                hit.tri = (int32_t)(first + i);
+                tbestf = f32_up(t);
+                if (any_hit) stop = true;
+            }
+        };
+        real4 qa = *reinterpret_cast<const real4*>(rec), qb; // (qb is read only after the fetch below has run: i + 1 < cnt then)
+        for (;;) {
+            if (i + 1 < cnt) qb = *reinterpret_cast<const real4*>(rec + STRIDE);
+            test(qa);
+            if (++i == cnt) break;
+            rec += STRIDE;
+            if (i + 1 < cnt) qa = *reinterpret_cast<const real4*>(rec + STRIDE);
+            test(qb);
+            if (++i == cnt) break;
+            rec += STRIDE;
+        }
+        return stop;
+    }
+
+    // Leaf round of this lane: the triangles of the leaf it is parked at, then pop.  PP: through test_leaf_pp.
+    template <bool COUNT, bool PP = false>
     PRT_DEV void leaf_step(const DScene& S, uint32_t* stk, WorkCount& wc, real tmin_use, bool any_hit) {
         bool stop = false;
         if (cur < 0 && cur != PRT_NOCUR) {
-            stop = test_leaf<COUNT>(S, cur, wc, tmin_use, any_hit);
+            if constexpr (PP) stop = test_leaf_pp<COUNT>(S, cur, wc, tmin_use, any_hit);
+            else stop = test_leaf<COUNT>(S, cur, wc, tmin_use, any_hit);
             cur = PRT_NOCUR;
         }
         if (stop) {

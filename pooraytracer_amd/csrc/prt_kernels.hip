@@ -587,6 +587,10 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     // normalize) differently, and their frames would leave the previous ones by a few fp32 ulps; they
     // keep the order they had.  fp32 CookTorrance and every fp64 kernel give the same bits either way.
     constexpr bool TURN = ONE_PASS && PRT_SAMPLE_TURNOVER && !(PRT_F32 && !(FEAT & PRT_FEAT_CT));
+    // WAVE_DIET (the fp64 one-pass permutations): the wave loop below takes its control from lane masks in scalar registers
+    // and tests leaves through Trav::test_leaf_pp — fewer vector instructions per round for the same rounds (DESIGN.md
+    // section 4).  Every other permutation, and both fp32 translation units, keep the loop and the code they had.
+    constexpr bool WAVE_DIET = ONE_PASS && !PRT_F32;
     d3 pending = mk3(0, 0, 0);   // ONE_PASS, ST_SHADOW: (throughput * direct light) / spp, added if the shadow ray escapes
     d3 next_d = mk3(0, 0, 1);    // ONE_PASS, ST_SHADOW: the scattered direction (valid if cont)
     bool cont = false;           // ONE_PASS, ST_SHADOW: the path goes on after this vertex
@@ -1087,6 +1091,67 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
         if (wave_count(state == ST_CACHED) >= P.cached_min) continue;
 
         // ---------------- traversal steps until enough lanes have finished to be worth refilling
+        if constexpr (WAVE_DIET) {
+            // The loop below with its control in scalar code.  Trav::round and the tests around it ask the wave five questions
+            // per round (lanes parked, lanes descending, a leaf to test, chained lanes, lanes active), each a __ballot of a bool
+            // that lives in a scalar mask across branches: a select and a compare per question (the ballot builtin costs the
+            // same; only a mask taken from a comparison IS the comparison's result).  So every mask here is a compare of tr.cur:
+            // inside this loop an idle lane holds cur == PRT_NOCUR.  Both steps of Trav drop `active` only with that value,
+            // and Trav::start leaves cur = 0 with `active` set (no triangles: not set, hence the two assignments), so
+            //   at an inner node  <=>  cur >= 0,    parked at a leaf  <=>  cur > PRT_NOCUR as unsigned,    active  <=>  either.
+            // The two masks are taken once after the node visit, the active lanes again after a leaf step; the chain test needs
+            // no vector instruction: the lanes in ST_SHADOW whose path goes on change only in a pass or a chain step (m_chain),
+            // and `fin` is those of them that are idle.  Same thresholds, same order of node visit, leaf step and chain step,
+            // same lanes in each: the schedule is the loop's below, round for round.
+            bool sh = state == ST_SHADOW;                                // the lane traces a shadow ray: interval and any-hit rule
+            unsigned long long m_chain = lane_mask(sh && cont);          // ... and its path goes on after it
+            unsigned long long m_act;
+            if (!tr.active) tr.cur = PRT_NOCUR;
+            do {
+                if (COUNT && lane_mask(tr.cur >= 0) != 0ULL) wc.inner_rounds++;
+                if (tr.cur >= 0) tr.template inner_step<COUNT>(S, stk, wc);
+                const unsigned long long m_inner = lane_mask(tr.cur >= 0);
+                const unsigned long long m_parked = lane_mask((uint32_t)tr.cur > (uint32_t)PRT_NOCUR);
+                m_act = m_inner | m_parked;
+                if (__popcll(m_parked) >= P.leaf_batch || __popcll(m_inner) <= P.inner_min) {
+                    if (COUNT && m_parked != 0ULL) wc.leaf_rounds++;
+                    // (the counting instantiations keep test_leaf: with their counters the two-at-a-time loop spills 9 to 10 registers more)
+                    if ((uint32_t)tr.cur > (uint32_t)PRT_NOCUR) tr.template leaf_step<COUNT, !COUNT>(S, stk, wc, sh ? RL(0.001) : RL(0.0001), sh);
+                    m_act = lane_mask(tr.cur != PRT_NOCUR);
+                }
+                const unsigned long long m_fin = m_chain & ~m_act; // shadow ray back, path goes on (the loop below's `fin`)
+                if (__popcll(m_fin) >= P.chain_min) {
+                    PROF_MARK(0);
+                    if (tr.cur == PRT_NOCUR && sh && cont) {
+                        if (tr.hit.tri < 0) {
+                            PST_ST(S_ACC, PST_LD(S_ACC) + pending);
+                            TRACE_FLAG_AT(nee_v, PRT_TRACE_VISIBLE);
+                        }
+                        tr.d = next_d;
+                        state = ST_CLOSEST;
+                        sh = false;
+                        if (COUNT && ctr->ray_dump != nullptr) { // (developer experiment, as at the end of a pass)
+                            const unsigned long long k = atomicAdd(&ctr->ray_dump_n, 1ULL);
+                            if (k < ctr->ray_dump_cap) {
+                                PrtRay r;
+                                r.o[0] = (double)tr.o.x; r.o[1] = (double)tr.o.y; r.o[2] = (double)tr.o.z;
+                                r.d[0] = (double)tr.d.x; r.d[1] = (double)tr.d.y; r.d[2] = (double)tr.d.z;
+                                r.tmin = 0.0001;
+                                r.tmax = __builtin_huge_val();
+                                static_cast<PrtRay*>(ctr->ray_dump)[k] = r;
+                            }
+                        }
+                        tr.start(S, RL(0.0001), PRT_INF);
+                        if (!tr.active) tr.cur = PRT_NOCUR;
+                    }
+                    if (lane == 0) atomicAdd(&s_rays[wave], (unsigned long long)__popcll(m_fin)); // closest rays: the low half
+                    m_chain &= m_act; // the chained lanes have left ST_SHADOW; the others keep their state
+                    m_act = lane_mask(tr.cur != PRT_NOCUR);
+                    PROF_MARK(5); // chain step
+                }
+            } while (__popcll(m_act) > P.keep);
+            tr.active = tr.cur != PRT_NOCUR; // (what the steps left there: said once, so that the loop itself need not carry it)
+        } else
         do {
             // the interval's lower end and the any-hit rule follow from the kind of ray: not kept as traversal state
             tr.template round<COUNT>(S, stk, wc, P.leaf_batch, P.inner_min, state == ST_SHADOW ? RL(0.001) : RL(0.0001), state == ST_SHADOW);
