@@ -58,6 +58,12 @@ public:
     bool ClosestPoint(const point3& p, double maxDist, point3& closest, double& distance) const;
     std::vector<bool> ClosestPoint(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
                                    std::vector<double>& distance) const;
+    // ClosestPoint's batch form with a signed distance - prt_signed_distance (device): signedDistance[i] is negative where
+    // p[i] lies inside this object, which is meaningful for a closed object whose faces are counter-clockwise seen from
+    // outside (the sign is that of the angle-weighted pseudonormal of the nearest face, edge or vertex).  The scene keeps the
+    // welded topology and the pseudonormals on the device from the first use on (prt_scene_set_signed_queries).  Not virtual.
+    std::vector<bool> SignedDistance(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
+                                     std::vector<double>& signedDistance) const;
     virtual AABB BoundingBox() const = 0;
     // lights.Sample(origin, record, pdf): one sample through prt_sample_lights (device).
     virtual void Sample(const point3& origin, HitRecord& samplePointRecord, double& pdf) const;

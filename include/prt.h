@@ -565,6 +565,90 @@ int prt_closest_point(PrtScene* scene, const PrtPointQuery* q, size_t n, PrtClos
 int prt_closest_point_device(PrtScene* scene, const void* d_q, size_t n, void* d_out, int count_work, void* hip_stream);
 
 /*
+ * Signed distance queries: prt_closest_point with a sign that is right at edges and vertices too.  PrtClosestPoint.side is
+ * the side of the winning triangle's plane, which is the inside/outside answer only where the nearest feature is a face: at
+ * an edge or a vertex it depends on which incident triangle wins the (d2, prim) tie, and across an acute dihedral angle some
+ * of them face away from the query.  The exact answer for closed meshes is the angle-weighted pseudonormal (Baerentzen and
+ * Aanaes, "Signed distance computation using the angle weighted pseudonormal", IEEE TVCG 2005): the face normal at a face,
+ * the sum of the unit normals of its faces at an edge, the sum of (interior angle x unit face normal) over the incident
+ * faces at a vertex.
+ *
+ * Topology.  The triangles of the WHOLE scene are welded (objects are routinely split into meshes by material): two corners
+ * are one vertex iff their three coordinates are bitwise equal after -0.0 -> +0.0; vertex ids ascend in order of first
+ * appearance in (prim, corner) order.  An edge is an unordered pair of distinct vertex ids, numbered in first-appearance
+ * order over (prim, edge v0v1, v1v2, v2v0); a triangle edge whose ends welded to one vertex has no id and its triangle counts
+ * as degenerate.  prt_scene_topology_info reports what the weld found, computed on demand from the host triangles: it works
+ * on any created scene, without a device and without the switch, and returns PRT_E_INVALID while PrtRefitInfo.host_stale is
+ * set.
+ */
+typedef struct PrtTopologyInfo {
+    uint64_t n_vertices, n_edges;
+    uint64_t boundary_edges;     /* one face */
+    uint64_t nonmanifold_edges;  /* three or more faces */
+    uint64_t inconsistent_edges; /* two faces that traverse the edge in the same direction */
+    uint64_t degenerate_tris;    /* two corners welded, or cross(v1-v0, v2-v0) is exactly zero */
+    uint64_t max_valence;        /* faces at the busiest vertex */
+    uint64_t table_bytes;        /* device bytes the signed-query tables hold (0 while off / not uploaded) */
+    uint32_t closed;             /* 1 iff boundary == nonmanifold == inconsistent == 0 */
+    uint32_t reserved;
+} PrtTopologyInfo;
+int prt_scene_topology_info(const PrtScene* scene, PrtTopologyInfo* out);
+
+/*
+ * The switch.  prt_scene_set_signed_queries(scene, 1) makes an uploaded scene keep, beside the corner table of the distance
+ * queries, six uint32 ids per triangle (vertex ids, edge ids, in description order), the two adjacency lists (vertex ->
+ * (prim, corner), edge -> prim, each ascending), per triangle its unit normal and corner angles, and one fp64 pseudonormal
+ * per vertex and per edge: PrtTopologyInfo.table_bytes, about 152 bytes per triangle of a closed mesh.  Any time; survives
+ * prt_scene_upload / prt_scene_update_vertices.  Switching on also switches distance queries on (a failure leaves both
+ * switches as they were), and prt_scene_set_distance_queries(scene, 0) while signed queries are on is PRT_E_INVALID.
+ * Switching on for an uploaded scene is synchronous (a host pass: weld + adjacency), and refused while the host geometry is
+ * stale, by prt_scene_set_distance_queries' rule.  Switching off frees the tables (distance queries stay on).
+ * The ids are made by prt_scene_upload, by prt_scene_update_vertices and by switch-on for an uploaded scene.
+ * prt_scene_refit* and prt_scene_rebuild* KEEP them (they are in description order: a new leaf order needs no permutation)
+ * and recompute the pseudonormals from the new positions on the call's stream, in their writing phase.  A caller who moves
+ * two welded corners apart with one of those calls therefore gets the sign of the OLD connectivity;
+ * prt_scene_update_vertices welds again.
+ *
+ * Pseudonormals (pseudonormals.hip; fp64, no fused multiply-adds).  Per triangle n = cross(v1-v0, v2-v0), nu = n / sqrt(dot(n,n)),
+ * the interior angle at corner k = atan2(|cross(e1,e2)|, dot(e1,e2)) with e1 = v[k+1]-v[k], e2 = v[k+2]-v[k].  A triangle
+ * whose dot(n,n) is 0 or not finite, or one of whose edges has no id, contributes nothing.  vn[v] = sum of angle * nu over
+ * the vertex's faces, en[e] = sum of nu over the edge's faces, each in ascending prim order from 0.0: the same bits on every
+ * run and for every builder or leaf order.  Neither is normalised: only a sign is taken from them.
+ *
+ * prt_scene_pseudonormals (test hook): out[t][0..2] = en of edges v0v1, v1v2, v2v0 and out[t][3..5] = vn of v0, v1, v2 of
+ * triangle t in description order (features 1..6), zeros for a slot without an id; *n = the scene's triangles, of which
+ * min(*n, cap_tris) are written.  Synchronous.  PRT_E_INVALID while the switch is off, PRT_E_NO_DEVICE unless uploaded.
+ */
+int prt_scene_set_signed_queries(PrtScene* scene, int on);
+int prt_scene_get_signed_queries(const PrtScene* scene, int* on);
+int prt_scene_pseudonormals(PrtScene* scene, double* out /* [n_tris][6][3] */, uint64_t cap_tris, uint64_t* n);
+
+typedef struct PrtSignedDistance { /* 64 bytes, the layout of PrtClosestPoint */
+    double sdist;       /* sign < 0 ? -dist : dist; +inf on a miss */
+    double point[3];
+    double alpha, beta;
+    int32_t prim;
+    int32_t feature;
+    int32_t side;       /* as PrtClosestPoint.side */
+    int32_t sign;       /* of dot(N, p - point), N the pseudonormal of the nearest feature: +1, -1, 0 */
+} PrtSignedDistance;
+/* Contract:
+ *  1. Every field but sdist and sign is, bit for bit, what prt_closest_point* writes for the same query, and |sdist| equals
+ *     that call's dist bit for bit.
+ *  2. sign.  s = dot(N, p - point) evaluated as x*x + y*y + z*z in fp64 without contraction.  Feature 0: N = cross(v1-v0,
+ *     v2-v0) of the winner, so s is side's expression and sign == side.  Features 1-3: N = en[eid[feature-1]]; features
+ *     4-6: N = vn[vid[feature-4]], of the winning triangle.  sign = +1 for s > 0, -1 for s < 0, 0 otherwise: s == 0, s NaN,
+ *     a slot without an id, a miss.  sdist = sign < 0 ? -dist : dist; +inf on a miss.
+ *  3. Meaning.  On a scene with PrtTopologyInfo.closed == 1 whose faces are counter-clockwise seen from outside, sign == -1
+ *     means inside.  On any other scene the formula still defines the value; nothing is promised about it.
+ *  4. The record does not depend on the tree, the builder, the leaf order or the batch order, bit for bit (the (d2, prim)
+ *     rule, and sums in prim order).
+ *  5. Items 1, 5, 6, 7 and 8 of the closest-point contract apply, with this difference: PRT_E_INVALID while the signed
+ *     switch is off (the message names the function and prt_scene_set_signed_queries) is reported before PRT_E_NO_DEVICE. */
+int prt_signed_distance(PrtScene* scene, const PrtPointQuery* q, size_t n, PrtSignedDistance* out, int count_work); /* host buffers, synchronous */
+int prt_signed_distance_device(PrtScene* scene, const void* d_q, size_t n, void* d_out, int count_work, void* hip_stream);
+
+/*
  * Multi-hit queries: for each of n rays, the first k surfaces along it, in order - thickness and X-ray measurements,
  * crossing parity, entry/exit pairs of closed shells, layered transparency done by the caller, depth layers.  K7
  * (multi_hit.hip): K1's persistent waves and box stepping with a leaf step that keeps a sorted per-lane list.  One

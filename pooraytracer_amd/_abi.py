@@ -245,6 +245,34 @@ class PrtClosestPoint(C.Structure):
     ]
 
 
+class PrtSignedDistance(C.Structure):  # the layout of PrtClosestPoint
+    _fields_ = [
+        ("sdist", C.c_double),
+        ("point", D3),
+        ("alpha", C.c_double),
+        ("beta", C.c_double),
+        ("prim", C.c_int32),
+        ("feature", C.c_int32),
+        ("side", C.c_int32),
+        ("sign", C.c_int32),
+    ]
+
+
+class PrtTopologyInfo(C.Structure):
+    _fields_ = [
+        ("n_vertices", C.c_uint64),
+        ("n_edges", C.c_uint64),
+        ("boundary_edges", C.c_uint64),
+        ("nonmanifold_edges", C.c_uint64),
+        ("inconsistent_edges", C.c_uint64),
+        ("degenerate_tris", C.c_uint64),
+        ("max_valence", C.c_uint64),
+        ("table_bytes", C.c_uint64),
+        ("closed", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class PrtLightSample(C.Structure):
     _fields_ = [
         ("position", D3),
@@ -286,6 +314,9 @@ LIGHT_SAMPLE_DTYPE = np.dtype(
 POINT_QUERY_DTYPE = np.dtype([("p", "<f8", 3), ("max_dist", "<f8")])
 CLOSEST_POINT_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", 3), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"),
                                 ("feature", "<i4"), ("side", "<i4"), ("reserved", "<i4")])
+SIGNED_DISTANCE_DTYPE = np.dtype([("sdist", "<f8"), ("point", "<f8", 3), ("alpha", "<f8"), ("beta", "<f8"), ("prim", "<i4"),
+                                  ("feature", "<i4"), ("side", "<i4"), ("sign", "<i4")])
+assert SIGNED_DISTANCE_DTYPE.itemsize == C.sizeof(PrtSignedDistance) == 64
 HIT_CURSOR_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("reserved", "<i4")])  # neutral: t = -inf, prim = -1
 assert HIT_CURSOR_DTYPE.itemsize == C.sizeof(PrtHitCursor) == 16
 assert RAY_DTYPE.itemsize == C.sizeof(PrtRay) == 64
@@ -319,6 +350,12 @@ EXPORTS = [
     "prt_scene_get_distance_queries",
     "prt_closest_point",
     "prt_closest_point_device",
+    "prt_scene_topology_info",
+    "prt_scene_set_signed_queries",
+    "prt_scene_get_signed_queries",
+    "prt_scene_pseudonormals",
+    "prt_signed_distance",
+    "prt_signed_distance_device",
     "prt_scene_light_update_info",
     "prt_scene_light_table_words",
     "prt_scene_bvh_info",

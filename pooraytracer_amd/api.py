@@ -65,6 +65,12 @@ def load():
     L.prt_scene_get_distance_queries.argtypes = [vp, C.POINTER(C.c_int)]
     L.prt_closest_point.argtypes = [vp, vp, sz, vp, i32]
     L.prt_closest_point_device.argtypes = [vp, vp, sz, vp, i32, vp]
+    L.prt_scene_topology_info.argtypes = [vp, vp]
+    L.prt_scene_set_signed_queries.argtypes = [vp, i32]
+    L.prt_scene_get_signed_queries.argtypes = [vp, C.POINTER(C.c_int)]
+    L.prt_scene_pseudonormals.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.prt_signed_distance.argtypes = [vp, vp, sz, vp, i32]
+    L.prt_signed_distance_device.argtypes = [vp, vp, sz, vp, i32, vp]
     L.prt_scene_light_table_words.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
@@ -134,6 +140,26 @@ def load():
             raise
     _libs[_LIB_PATH] = L
     return L
+
+
+def _point_queries(name, points, max_dist):
+    """The PrtPointQuery batch of closest_point / signed_distance; shape and dtype errors are raised here."""
+    if not isinstance(points, np.ndarray):
+        raise TypeError(f"{name}: points must be a numpy array, not {type(points).__name__}")
+    if points.dtype != np.float64:
+        raise TypeError(f"{name}: points must be float64, not {points.dtype}")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"{name}: points must have shape (n, 3), not {points.shape}")
+    n = points.shape[0]
+    md = np.asarray(max_dist)
+    if md.dtype.kind not in "fiu":
+        raise TypeError(f"{name}: max_dist must be real, not {md.dtype}")
+    if md.shape not in ((), (n,)):
+        raise ValueError(f"{name}: max_dist must be a scalar or have shape ({n},), not {md.shape}")
+    q = np.zeros(n, dtype=_abi.POINT_QUERY_DTYPE)
+    q["p"] = points
+    q["max_dist"] = md
+    return q
 
 
 class dev_hooks:
@@ -428,21 +454,8 @@ class Scene:
         CLOSEST_POINT_DTYPE array [n]: dist, the nearest point of the mesh, its barycentrics, prim, feature (0 face, 1-3
         edge, 4-6 vertex) and side; dist = inf and prim = -1 where no triangle lies within max_dist.  Shape and dtype errors
         are raised here, before any call."""
-        if not isinstance(points, np.ndarray):
-            raise TypeError(f"closest_point: points must be a numpy array, not {type(points).__name__}")
-        if points.dtype != np.float64:
-            raise TypeError(f"closest_point: points must be float64, not {points.dtype}")
-        if points.ndim != 2 or points.shape[1] != 3:
-            raise ValueError(f"closest_point: points must have shape (n, 3), not {points.shape}")
-        n = points.shape[0]
-        md = np.asarray(max_dist)
-        if md.dtype.kind not in "fiu":
-            raise TypeError(f"closest_point: max_dist must be real, not {md.dtype}")
-        if md.shape not in ((), (n,)):
-            raise ValueError(f"closest_point: max_dist must be a scalar or have shape ({n},), not {md.shape}")
-        q = np.zeros(n, dtype=_abi.POINT_QUERY_DTYPE)
-        q["p"] = points
-        q["max_dist"] = md
+        q = _point_queries("closest_point", points, max_dist)
+        n = q.shape[0]
         out = np.zeros(n, dtype=_abi.CLOSEST_POINT_DTYPE)
         _check(self._L.prt_closest_point(self._h, q.ctypes.data, n, out.ctypes.data, int(count_work)), self._L)
         return out
@@ -451,6 +464,48 @@ class Scene:
         """prt_closest_point_device: asynchronous, on device buffers (raw pointers: n PrtPointQuery of 32 bytes, n
         PrtClosestPoint of 64 bytes, 32-byte aligned).  The queries are not checked on the host."""
         _check(self._L.prt_closest_point_device(self._h, d_q_ptr, int(n), d_out_ptr, int(count_work), stream), self._L)
+
+    @property
+    def signed_queries(self):
+        """Whether the scene answers signed_distance* (prt_scene_set_signed_queries): off by default; switching on also
+        switches distance_queries on, and an uploaded scene then keeps the welded topology's ids and the angle-weighted
+        pseudonormals of every vertex and edge on the device; refit* / rebuild* refresh the pseudonormals."""
+        on = C.c_int(0)
+        _check(self._L.prt_scene_get_signed_queries(self._h, C.byref(on)), self._L)
+        return bool(on.value)
+
+    @signed_queries.setter
+    def signed_queries(self, on):
+        _check(self._L.prt_scene_set_signed_queries(self._h, int(bool(on))), self._L)
+
+    def topology_info(self):
+        """prt_scene_topology_info as a dict: what welding the whole scene's corners found (works without a device)."""
+        info = _abi.PrtTopologyInfo()
+        _check(self._L.prt_scene_topology_info(self._h, C.byref(info)), self._L)
+        return {f: int(getattr(info, f)) for f, _ in _abi.PrtTopologyInfo._fields_ if f != "reserved"}
+
+    def pseudonormals(self):
+        """prt_scene_pseudonormals: float64 [n_tris, 6, 3] - per triangle the (unnormalised) pseudonormals of its edges
+        v0v1, v1v2, v2v0 and vertices v0, v1, v2 as the device holds them; zeros for a slot without an id."""
+        n = C.c_uint64(0)
+        out = np.zeros((int(np.asarray(self.data.vertices).shape[0]), 6, 3), dtype=np.float64)
+        _check(self._L.prt_scene_pseudonormals(self._h, out.ctypes.data, out.shape[0], C.byref(n)), self._L)
+        assert n.value == out.shape[0]
+        return out
+
+    def signed_distance(self, points, max_dist=np.inf, count_work=False):
+        """Signed distance query (prt_signed_distance): arguments as closest_point.  Returns a SIGNED_DISTANCE_DTYPE array
+        [n]: closest_point's record with sdist = sign * dist in place of dist and sign in place of reserved; sign is that of
+        dot(N, p - point) with N the angle-weighted pseudonormal of the nearest feature (-1: inside a closed mesh)."""
+        q = _point_queries("signed_distance", points, max_dist)
+        out = np.zeros(q.shape[0], dtype=_abi.SIGNED_DISTANCE_DTYPE)
+        _check(self._L.prt_signed_distance(self._h, q.ctypes.data, q.shape[0], out.ctypes.data, int(count_work)), self._L)
+        return out
+
+    def signed_distance_device(self, d_q_ptr, n, d_out_ptr, count_work=False, stream=None):
+        """prt_signed_distance_device: asynchronous, on device buffers (n PrtPointQuery, n PrtSignedDistance of 64 bytes,
+        32-byte aligned).  The queries are not checked on the host."""
+        _check(self._L.prt_signed_distance_device(self._h, d_q_ptr, int(n), d_out_ptr, int(count_work), stream), self._L)
 
     def sample_lights(self, origins, seed=1):
         origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

@@ -25,9 +25,11 @@
 // (tests/closest_point_model.py evaluates the same expressions in numpy), and the bound below is derived for individually
 // rounded operations.  fp64 division and sqrt are correctly rounded.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/prt.h"
 #include "prt_types.h"
@@ -155,6 +157,11 @@ struct ClosestArgs {
     int32_t stack_depth;
     float g0[3], gs[3], E;
 };
+struct SignedArgs : ClosestArgs { // the SIGNED instantiations' (the others keep their kernel arguments)
+    const uint32_t* slot; // DSignedTables::slot / normal (prt_launch.h)
+    const double* normal;
+    uint32_t n_normals; // edges + vertices
+};
 
 __device__ __forceinline__ V corner(const double4 c0, const double4 c1, const double2 c2, int k) {
     return k == 0 ? V{c0.x, c0.y, c0.z} : k == 1 ? V{c0.w, c1.x, c1.y} : V{c1.z, c1.w, c2.x};
@@ -173,8 +180,11 @@ __device__ __forceinline__ V corner(const double4 c0, const double4 c1, const do
 // (developer hook PRT_TUNE_CLOSEST_PLAIN).  Either way a record is a pure function of its query.
 // LDS decides the occupancy: two blocks per CU at the builders' stack bound (40 entries: 80 KB of stacks), up to four for
 // the shallow trees of small scenes, which is what the 106 registers per lane (no scratch) leave room for.
-template <bool COUNT, bool REFILL>
-__global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(ClosestArgs A) {
+// SIGNED (prt_signed_distance): the write-out also takes the sign of dot(N, p - point), N the pseudonormal of the nearest
+// feature - the descent is the same code, and at the write-out the lane already holds p, point, the feature and the prim:
+// one id load and one 24-byte load per query, and only where the feature is an edge or a vertex.
+template <bool COUNT, bool REFILL, bool SIGNED = false>
+__global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional_t<SIGNED, SignedArgs, ClosestArgs> A) {
     extern __shared__ uint32_t s_stack[]; // [2][PRT_BLOCK / 64][stack_depth][64]: refs, then bounds
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* stk_ref = s_stack + (size_t)(wave * A.stack_depth) * 64 + lane;
@@ -196,7 +206,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(ClosestArgs A) {
     for (;;) {
         if (!active && have) { // the lane's descent has ended: its record
             double4 o0 = make_double4(__builtin_huge_val(), 0.0, 0.0, 0.0), o1 = make_double4(0.0, 0.0, 0.0, 0.0);
-            int32_t prim = -1, feature = -1, side = 0;
+            int32_t prim = -1, feature = -1, side = 0, sign = 0; // sign: PrtClosestPoint.reserved = 0 unless SIGNED
             if (best_prim != INT32_MAX) {
                 const double4* rec = reinterpret_cast<const double4*>(A.corners + best_at);
                 const double4 c0 = rec[0], c1 = rec[1];
@@ -208,9 +218,24 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(ClosestArgs A) {
                 o1.x = best_al, o1.y = best_be;
                 prim = best_prim, feature = best_feature;
                 side = s > 0.0 ? 1 : (s < 0.0 ? -1 : 0);
+                if constexpr (SIGNED) {
+                    sign = side; // a face: N = cross(v1 - v0, v2 - v0), s is side's expression
+                    if (feature != 0) {
+                        sign = 0;
+                        // (prim < n_tris and id < n_normals by construction; never read out of the tables)
+                        const uint32_t id = (uint32_t)prim < A.n_tris ? A.slot[(size_t)(uint32_t)prim * 6 + (uint32_t)(feature - 1)] : kNoKey;
+                        if (id < A.n_normals) { // kNoKey: a slot without an id
+                            const double* nrm = A.normal + (size_t)id * 3;
+                            const double sn = dot(V{nrm[0], nrm[1], nrm[2]}, sub(p, pt));
+                            sign = sn > 0.0 ? 1 : (sn < 0.0 ? -1 : 0);
+                        }
+                    }
+                    if (sign < 0) o0.x = -o0.x;
+                }
             }
             o1.z = __longlong_as_double((long long)(((unsigned long long)(uint32_t)feature << 32) | (uint32_t)prim));
-            o1.w = __longlong_as_double((long long)(unsigned long long)(uint32_t)side); // reserved = 0
+            o1.w = SIGNED ? __longlong_as_double((long long)(((unsigned long long)(uint32_t)sign << 32) | (uint32_t)side))
+                          : __longlong_as_double((long long)(unsigned long long)(uint32_t)side); // reserved = 0
             double4* o = reinterpret_cast<double4*>(A.out + qi);
             o[0] = o0;
             o[1] = o1;
@@ -377,17 +402,13 @@ void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint3
     if (n) k_gather_corners<<<(n + 255) / 256, 256, 0, st>>>(d_verts, d_order, n, d_out);
 }
 
-// One batch of queries through K6.  stack_depth: entries per lane (what the resident tree can need); d_out 32-byte aligned;
-// d_ctr->next_item is zero (the call slot's start clears the counters); plain: the one-block-per-256-queries form.
-hipError_t launch_closest_point(const DScene& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n, PrtClosestPoint* d_out,
-                                DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain, hipStream_t st) {
-    static_assert(sizeof(PrtPointQuery) == 32 && sizeof(PrtClosestPoint) == 64, "query and answer records");
-    if (n == 0) return hipSuccess;
-    ClosestArgs A;
+namespace {
+void fill_args(ClosestArgs& A, const DScene& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n, void* d_out, DCounters* d_ctr,
+               int stack_depth) {
     A.nodes = S.nodes;
     A.corners = d_corners;
     A.q = d_q;
-    A.out = d_out;
+    A.out = static_cast<PrtClosestPoint*>(d_out);
     A.ctr = d_ctr;
     A.n = n;
     A.n_tris = S.n_tris;
@@ -397,20 +418,49 @@ hipError_t launch_closest_point(const DScene& S, const DTriCorners* d_corners, c
         A.gs[a] = S.grid_step[a];
     }
     A.E = S.slab_scale;
+}
+template <typename Kernel, typename Args>
+hipError_t launch_k6(Kernel k, const Args& A, int n_cu, bool plain, hipStream_t st) {
     const size_t lds = (size_t)2 * PRT_BLOCK * A.stack_depth * sizeof(uint32_t);
-    auto k = plain ? (count ? k_closest_point<true, false> : k_closest_point<false, false>)
-                   : (count ? k_closest_point<true, true> : k_closest_point<false, true>);
     if (lds > 64u * 1024u) { // more dynamic LDS than a launch may ask for by default
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     // the plain form: a block per 256 queries; persistent waves: as many blocks as can be resident (LDS: 160 KB per CU;
     // registers: four waves per SIMD)
-    const size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
+    const size_t want = (A.n + PRT_BLOCK - 1) / PRT_BLOCK;
     const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / lds));
     const unsigned grid = (unsigned)(plain ? want : std::min<size_t>(want, (size_t)std::max(n_cu, 1) * per_cu));
     hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), lds, st, A);
     return hipGetLastError();
+}
+} // namespace
+
+// One batch of queries through K6.  stack_depth: entries per lane (what the resident tree can need); d_out 32-byte aligned;
+// d_ctr->next_item is zero (the call slot's start clears the counters); plain: the one-block-per-256-queries form.
+hipError_t launch_closest_point(const DScene& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n, PrtClosestPoint* d_out,
+                                DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain, hipStream_t st) {
+    static_assert(sizeof(PrtPointQuery) == 32 && sizeof(PrtClosestPoint) == 64, "query and answer records");
+    if (n == 0) return hipSuccess;
+    ClosestArgs A;
+    fill_args(A, S, d_corners, d_q, n, d_out, d_ctr, stack_depth);
+    auto k = plain ? (count ? k_closest_point<true, false> : k_closest_point<false, false>)
+                   : (count ? k_closest_point<true, true> : k_closest_point<false, true>);
+    return launch_k6(k, A, n_cu, plain, st);
+}
+
+// ... with the sign of the nearest feature's pseudonormal: PrtSignedDistance records (the layout of PrtClosestPoint).
+hipError_t launch_signed_distance(const DScene& S, const DTriCorners* d_corners, const DSignedTables& T, const PrtPointQuery* d_q, size_t n,
+                                  PrtSignedDistance* d_out, DCounters* d_ctr, bool count, int stack_depth, int n_cu, hipStream_t st) {
+    static_assert(sizeof(PrtSignedDistance) == sizeof(PrtClosestPoint) && offsetof(PrtSignedDistance, sign) == offsetof(PrtClosestPoint, reserved),
+                  "PrtSignedDistance has the layout of PrtClosestPoint");
+    if (n == 0) return hipSuccess;
+    SignedArgs A;
+    fill_args(A, S, d_corners, d_q, n, d_out, d_ctr, stack_depth);
+    A.slot = T.slot;
+    A.normal = T.normal;
+    A.n_normals = T.n_edges + T.n_vertices;
+    return launch_k6(count ? k_closest_point<true, true, true> : k_closest_point<false, true, true>, A, n_cu, false, st);
 }
 
 } // namespace prt

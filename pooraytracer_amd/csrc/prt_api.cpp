@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "mesh_topology.h"
 #include "prt_host.h"
 #include "prt_launch.h" // every launcher of the .hip files, declared once
 
@@ -211,6 +212,13 @@ struct PrtScene {
     // order (96 bytes each, owned by `allocs`); upload, refit and rebuild keep the table in step with the resident geometry
     bool distance_queries = false; // survives upload / update_vertices
     DTriCorners* d_corners = nullptr;
+    // prt_scene_set_signed_queries: while it is on (distance queries are then on too), an uploaded scene also keeps the ids,
+    // adjacency lists, face terms and pseudonormals of pseudonormals.hip (all owned by `allocs`; `signed_bytes` of them).  The
+    // ids and lists are in description order and belong to the topology: upload and switch-on make them, refit and rebuild
+    // keep them and refresh face terms and pseudonormals behind the corner gather.
+    bool signed_queries = false; // survives upload / update_vertices
+    prt::DSignedTables sq;
+    size_t signed_bytes = 0;
     struct LightUpdate {
         double* d_gather = nullptr;    // per light triangle, resident CDF order: 9 doubles of new vertices, then (second half) of vertex normals
         std::vector<double> h_gather;  // ... read back with the refit's decision
@@ -340,6 +348,8 @@ struct PrtScene {
         allocs.clear();
         d_order = nullptr;
         d_corners = nullptr;
+        sq = prt::DSignedTables();
+        signed_bytes = 0;
         refit = Refit();
         light_res = light_spare = LightArrays();
         lu = LightUpdate();
@@ -768,6 +778,71 @@ static int corners_from_host(PrtScene* s, const std::string& who) {
     return PRT_OK;
 }
 
+// The tables of a scene that answers signed distance queries (prt_scene_set_signed_queries): the weld, ids and adjacency
+// lists of the host triangles (mesh_topology.cpp: a host pass), uploaded, and the pseudonormals from the resident corner
+// table, on the null stream, synchronous.  The scene is uploaded, its device is current, it has its corner table and no
+// signed tables.  All or nothing: a failure keeps none of them.
+static int signed_from_host(PrtScene* s, const std::string& who) {
+    const size_t n = s->tris.size();
+    prt::MeshTopology topo;
+    std::vector<uint32_t> slot;
+    try {
+        prt::build_topology(n ? &s->tris[0].v[0][0] : nullptr, sizeof(prt::HostTri) / sizeof(double), n, topo);
+        const uint32_t ne = (uint32_t)topo.info.n_edges;
+        slot.resize(n * 6);
+        for (size_t t = 0; t < n; ++t)
+            for (int k = 0; k < 3; ++k) {
+                slot[t * 6 + k] = topo.eid[t * 3 + k]; // (kNoTopoId is the kernels' "no slot")
+                slot[t * 6 + 3 + k] = ne + topo.vid[t * 3 + k];
+            }
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, who + ": out of host memory for the mesh topology");
+    }
+    static_assert(sizeof(prt::HostTri) % sizeof(double) == 0, "HostTri is addressed in doubles");
+    const size_t nv = topo.info.n_vertices, ne = topo.info.n_edges;
+    const std::vector<uint32_t>* src[5] = {&slot, &topo.v_start, &topo.v_list, &topo.e_start, &topo.e_list};
+    const size_t reals[2] = {n * 6, (nv + ne) * 3};
+    DevBuf<> buf[7];
+    size_t bytes = 0;
+    for (int i = 0; i < 7; ++i) {
+        const size_t b = i < 5 ? src[i]->size() * sizeof(uint32_t) : reals[i - 5] * sizeof(double);
+        PRT_HIP_AS(who, dev_alloc(buf[i], std::max<size_t>(b, 256)));
+        if (i < 5 && b) PRT_HIP_AS(who, hipMemcpy(buf[i].get(), src[i]->data(), b, hipMemcpyHostToDevice));
+        if (i >= 5) PRT_HIP_AS(who, hipMemset(buf[i].get(), 0, std::max<size_t>(b, 256)));
+        bytes += b;
+    }
+    prt::DSignedTables T;
+    T.slot = static_cast<const uint32_t*>(buf[0].get());
+    T.v_start = static_cast<const uint32_t*>(buf[1].get());
+    T.v_list = static_cast<const uint32_t*>(buf[2].get());
+    T.e_start = static_cast<const uint32_t*>(buf[3].get());
+    T.e_list = static_cast<const uint32_t*>(buf[4].get());
+    T.face = static_cast<double*>(buf[5].get());
+    T.normal = static_cast<double*>(buf[6].get());
+    T.n_tris = (uint32_t)n, T.n_vertices = (uint32_t)nv, T.n_edges = (uint32_t)ne;
+    PRT_HIP_AS(who, s->after_refit(nullptr));
+    prt::launch_pseudonormals(s->d_corners, T, nullptr);
+    PRT_HIP_AS(who, hipGetLastError());
+    PRT_HIP_AS(who, hipDeviceSynchronize());
+    try {
+        s->allocs.reserve(s->allocs.size() + 7);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, who + ": out of host memory");
+    }
+    for (DevBuf<>& b : buf) s->allocs.push_back(std::move(b));
+    s->sq = T;
+    s->signed_bytes = bytes;
+    return PRT_OK;
+}
+
+// The signed tables go (after the work that may still read or write them): switch-off.
+static void signed_free(PrtScene* s) {
+    const void* owned[7] = {s->sq.slot, s->sq.v_start, s->sq.v_list, s->sq.e_start, s->sq.e_list, s->sq.face, s->sq.normal};
+    for (const void* p : owned) s->take(p).reset();
+    s->sq = prt::DSignedTables();
+    s->signed_bytes = 0;
+}
+
 // Either the whole scene is resident afterwards, or nothing is: a failure anywhere (allocation, copy, device build)
 // releases what was uploaded so far and leaves the scene in the not-uploaded state (device = -1), so that no later
 // call can launch a kernel on a half-filled DScene.
@@ -1026,6 +1101,7 @@ static int upload_impl(PrtScene* s, int device) {
     // the fp64 kernels render without their LDS tables when the tables would cost a resident block (the fp32 ones do not)
     s->blocks_wanted = size_kernels(s, s->k64, true);
     if (s->distance_queries && (rc = corners_from_host(s, "prt_scene_upload"))) return rc;
+    if (s->signed_queries && (rc = signed_from_host(s, "prt_scene_upload"))) return rc;
     return PRT_OK;
 }
 
@@ -1606,6 +1682,7 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
                            R.d_tbox, g.origin_d, g.delta, st);
     if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
+    if (s->d_corners && s->sq.slot) prt::launch_pseudonormals(s->d_corners, s->sq, st);      // signed queries: the pseudonormals too
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
         const DSceneT<float>& f = s->k32.d;
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
@@ -1733,6 +1810,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
                            R.d_tbox, g.origin_d, g.delta, st);
     if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
+    if (s->d_corners && s->sq.slot) prt::launch_pseudonormals(s->d_corners, s->sq, st);      // signed queries: the pseudonormals too
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
         const DSceneT<float>& f = s->k32.d;
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
@@ -1853,6 +1931,9 @@ int prt_scene_set_distance_queries(PrtScene* s, int on) {
     if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
     const bool want = on != 0;
     if (want == s->distance_queries) return PRT_OK;
+    if (!want && s->signed_queries)
+        return fail(PRT_E_INVALID, std::string(who) + ": signed distance queries are on and need the corner table "
+                                                      "(call prt_scene_set_signed_queries(scene, 0) first)");
     if (s->device < 0) { // not uploaded: the next upload makes the table
         s->distance_queries = want;
         return PRT_OK;
@@ -1880,6 +1961,92 @@ int prt_scene_set_distance_queries(PrtScene* s, int on) {
 int prt_scene_get_distance_queries(const PrtScene* s, int* on) {
     if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_distance_queries: null argument");
     *on = s->distance_queries ? 1 : 0;
+    return PRT_OK;
+}
+
+int prt_scene_set_signed_queries(PrtScene* s, int on) {
+    const char* who = "prt_scene_set_signed_queries";
+    if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
+    const bool want = on != 0;
+    if (want == s->signed_queries) return PRT_OK;
+    if (s->device < 0) { // not uploaded: the next upload makes the tables
+        s->signed_queries = want;
+        if (want) s->distance_queries = true;
+        return PRT_OK;
+    }
+    PRT_HIP(hipSetDevice(s->device));
+    if (want) {
+        if (s->host_stale)
+            return fail(PRT_E_INVALID, std::string(who) + ": the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device moved the "
+                                                          "resident geometry past it): switch signed queries on before moving geometry, or call "
+                                                          "prt_scene_refit or prt_scene_update_vertices first");
+        const bool had_corners = s->distance_queries;
+        if (!had_corners)
+            if (const int rc = corners_from_host(s, who)) return rc;
+        if (const int rc = signed_from_host(s, who)) {
+            if (!had_corners) { // both switches as they were
+                s->take(s->d_corners).reset();
+                s->d_corners = nullptr;
+            }
+            return rc;
+        }
+        s->distance_queries = s->signed_queries = true;
+        return PRT_OK;
+    }
+    // off: the tables go once the queries in flight, and a refit that may still be writing them, have ended
+    for (PrtScene::CallSlot& q : s->slots)
+        if (q.timed) PRT_HIP_AS(who, hipEventSynchronize(q.done.get()));
+    if (s->refit.pending) PRT_HIP_AS(who, hipEventSynchronize(s->refit.done.get()));
+    signed_free(s);
+    s->signed_queries = false;
+    return PRT_OK;
+}
+
+int prt_scene_get_signed_queries(const PrtScene* s, int* on) {
+    if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_signed_queries: null argument");
+    *on = s->signed_queries ? 1 : 0;
+    return PRT_OK;
+}
+
+int prt_scene_topology_info(const PrtScene* s, PrtTopologyInfo* out) {
+    if (!s || !out) return fail(PRT_E_INVALID, "prt_scene_topology_info: null argument");
+    std::memset(out, 0, sizeof(*out));
+    if (s->host_stale)
+        return fail(PRT_E_INVALID, "prt_scene_topology_info: the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device "
+                                   "moved the resident geometry past it; call prt_scene_refit or prt_scene_update_vertices first)");
+    try {
+        prt::MeshTopology topo;
+        const size_t n = s->tris.size();
+        prt::build_topology(n ? &s->tris[0].v[0][0] : nullptr, sizeof(prt::HostTri) / sizeof(double), n, topo, false);
+        *out = topo.info;
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, "prt_scene_topology_info: out of host memory");
+    }
+    out->table_bytes = s->signed_bytes;
+    return PRT_OK;
+}
+
+int prt_scene_pseudonormals(PrtScene* s, double* out, uint64_t cap_tris, uint64_t* n) {
+    const char* who = "prt_scene_pseudonormals";
+    if (!s || !n || (!out && cap_tris)) return fail(PRT_E_INVALID, std::string(who) + ": null argument");
+    if (!s->signed_queries)
+        return fail(PRT_E_INVALID, std::string(who) + ": signed distance queries are off for this scene (prt_scene_set_signed_queries)");
+    if (const int rc = require_uploaded(s, who)) return rc;
+    const prt::DSignedTables& T = s->sq;
+    *n = T.n_tris;
+    const size_t m = (size_t)std::min<uint64_t>(T.n_tris, cap_tris), nn = (size_t)T.n_edges + T.n_vertices;
+    if (m == 0) return PRT_OK;
+    try {
+        std::vector<uint32_t> slot(m * 6);
+        std::vector<double> nrm(nn * 3);
+        PRT_HIP_AS(who, hipDeviceSynchronize()); // a refit on any stream has written its pseudonormals
+        PRT_HIP_AS(who, hipMemcpy(slot.data(), T.slot, slot.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        PRT_HIP_AS(who, hipMemcpy(nrm.data(), T.normal, nrm.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < m * 6; ++i)
+            for (int a = 0; a < 3; ++a) out[i * 3 + a] = slot[i] < nn ? nrm[(size_t)slot[i] * 3 + a] : 0.0;
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, std::string(who) + ": out of host memory");
+    }
     return PRT_OK;
 }
 
@@ -1985,6 +2152,49 @@ int prt_closest_point(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtClosest
     if (n == 0) return PRT_OK;
     return batch_host(who, qs, n * sizeof(PrtPointQuery), nullptr, 0, out, n * sizeof(PrtClosestPoint),
                       [&](void* dq, void*, void* dout) { return prt_closest_point_device(s, dq, n, dout, count_work, nullptr); });
+}
+
+static int refuse_unsigned(const PrtScene* s, const std::string& w) {
+    if (!s->signed_queries || (s->device >= 0 && (!s->d_corners || !s->sq.slot)))
+        return fail(PRT_E_INVALID, w + ": signed distance queries are off for this scene (prt_scene_set_signed_queries)");
+    return PRT_OK;
+}
+
+int prt_signed_distance_device(PrtScene* s, const void* d_q, size_t n, void* d_out, int count_work, void* stream) {
+    if (!s) return fail(PRT_E_INVALID, "prt_signed_distance_device: null scene");
+    if (const int rc = refuse_unsigned(s, "prt_signed_distance_device")) return rc; // (before the missing device: contract 5)
+    return batch_device(
+        s, "prt_signed_distance_device", nullptr, n, count_work, PRT_PRECISION_F64, stream, false,
+        [&](const std::string& w) {
+            if (n && (!d_q || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
+            if (n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 queries in one batch");
+            if (reinterpret_cast<uintptr_t>(d_out) & 31u) // the kernel stores a record 32 bytes at a time
+                return fail(PRT_E_INVALID, w + ": output buffer is not 32-byte aligned");
+            return PRT_OK;
+        },
+        [&](bool, DCounters* d_ctr, bool count, const uint32_t*, hipStream_t st) {
+            return prt::launch_signed_distance(s->k64.d, s->d_corners, s->sq, static_cast<const PrtPointQuery*>(d_q), n,
+                                               static_cast<PrtSignedDistance*>(d_out), d_ctr, count, s->stack_need, s->n_cu, st);
+        });
+}
+
+int prt_signed_distance(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtSignedDistance* out, int count_work) {
+    static_assert(sizeof(PrtSignedDistance) == 64, "PrtSignedDistance is 64 bytes");
+    const char* who = "prt_signed_distance";
+    if (!s) return fail(PRT_E_INVALID, "prt_signed_distance: null scene");
+    if (n && (!qs || !out)) return fail(PRT_E_INVALID, "prt_signed_distance: null buffer");
+    if (n > 0xffffffffull) return fail(PRT_E_INVALID, "prt_signed_distance: more than 2^32 - 1 queries in one batch");
+    for (size_t i = 0; i < n; ++i) { // the batch is checked before anything else, as prt_closest_point checks it
+        const PrtPointQuery& q = qs[i];
+        if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2])))
+            return fail(PRT_E_INVALID, "prt_signed_distance: query " + std::to_string(i) + " has a non-finite point");
+        if (!(q.max_dist >= 0.0)) return fail(PRT_E_INVALID, "prt_signed_distance: query " + std::to_string(i) + " has a negative or NaN max_dist");
+    }
+    if (const int rc = refuse_unsigned(s, who)) return rc;
+    if (const int rc = require_uploaded(s, who)) return rc;
+    if (n == 0) return PRT_OK;
+    return batch_host(who, qs, n * sizeof(PrtPointQuery), nullptr, 0, out, n * sizeof(PrtSignedDistance),
+                      [&](void* dq, void*, void* dout) { return prt_signed_distance_device(s, dq, n, dout, count_work, nullptr); });
 }
 
 int prt_scene_light_update_info(const PrtScene* s, PrtLightUpdateInfo* out) {

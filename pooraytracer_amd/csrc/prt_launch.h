@@ -96,6 +96,24 @@ void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint3
 hipError_t launch_closest_point(const DSceneT<double>& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n,
                                 PrtClosestPoint* d_out, DCounters* d_ctr, bool count, int stack_depth, int n_cu, bool plain,
                                 hipStream_t st);
+// ... and K6 with the sign of the nearest feature's pseudonormal (prt_signed_distance): the persistent-wave schedule only
+struct DSignedTables;
+hipError_t launch_signed_distance(const DSceneT<double>& S, const DTriCorners* d_corners, const DSignedTables& T, const PrtPointQuery* d_q,
+                                  size_t n, PrtSignedDistance* d_out, DCounters* d_ctr, bool count, int stack_depth, int n_cu,
+                                  hipStream_t st);
+// pseudonormals.hip: the device tables of a scene that answers signed distance queries (all in description order; ids
+// and lists from mesh_topology.cpp, uploaded once per topology), and the refresh of `face` and `normal` from the corner table
+struct DSignedTables {
+    const uint32_t* slot = nullptr;    // [n_tris][6]: index into `normal` of edge v0v1, v1v2, v2v0, vertex v0, v1, v2; 0xffffffff: none
+    const uint32_t* v_start = nullptr; // CSR vertex -> (prim << 2 | corner), ascending
+    const uint32_t* v_list = nullptr;
+    const uint32_t* e_start = nullptr; // CSR edge -> prim, ascending
+    const uint32_t* e_list = nullptr;
+    double* face = nullptr;            // [n_tris][6]: the unit normal, the interior angles at v0, v1, v2 (zeros: contributes nothing)
+    double* normal = nullptr;          // [n_edges + n_vertices][3]: en of every edge, then vn of every vertex
+    uint32_t n_tris = 0, n_vertices = 0, n_edges = 0;
+};
+void launch_pseudonormals(const DTriCorners* d_corners, const DSignedTables& T, hipStream_t st);
 // K7 (multi_hit.hip / multi_hit_f32.hip): one batch of rays, k records per ray into d_out (32-byte aligned), d_after null
 // or one cursor per ray, d_perm K4's order or null
 hipError_t launch_multi_hit(const DSceneT<double>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,

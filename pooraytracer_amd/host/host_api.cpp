@@ -248,6 +248,30 @@ std::vector<bool> Hittable::ClosestPoint(const std::vector<point3>& p, double ma
     return found;
 }
 
+std::vector<bool> Hittable::SignedDistance(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
+                                           std::vector<double>& signedDistance) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    check(prt_scene_set_signed_queries(dc.scene, 1), "prt_scene_set_signed_queries"); // (nothing to do when it is on already)
+    std::vector<PrtPointQuery> q(p.size());
+    for (size_t i = 0; i < p.size(); ++i) {
+        q[i].p[0] = p[i].x; q[i].p[1] = p[i].y; q[i].p[2] = p[i].z;
+        q[i].max_dist = maxDist;
+    }
+    std::vector<PrtSignedDistance> r(p.size());
+    check(prt_signed_distance(dc.scene, q.data(), q.size(), r.data(), 0), "prt_signed_distance");
+    closest.resize(p.size());
+    signedDistance.resize(p.size());
+    std::vector<bool> found(p.size());
+    for (size_t i = 0; i < p.size(); ++i) {
+        if (r[i].prim < 0) continue;
+        closest[i] = point3(r[i].point[0], r[i].point[1], r[i].point[2]);
+        signedDistance[i] = r[i].sdist;
+        found[i] = true;
+    }
+    return found;
+}
+
 bool Hittable::ClosestPoint(const point3& p, double maxDist, point3& closest, double& distance) const {
     std::vector<point3> c;
     std::vector<double> d;
