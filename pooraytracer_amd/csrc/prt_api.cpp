@@ -30,6 +30,11 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
+// A failure's text survives the cleanup that follows it (calls that may fail again, or succeed): restored on scope exit.
+struct KeepError {
+    const std::string msg = g_err;
+    ~KeepError() { g_err = msg; }
+};
 // Developer / test hooks are environment variables (PRT_TUNE_*: scheduling thresholds, table sizes, layouts for A/B runs;
 // PRT_TEST_*: failure injection; PRT_VALIDATE_BVH).  The shipped libprt_hip.so does NOT read them: only a build with
 // -DPRT_DEV_HOOKS=1 does (pooraytracer_amd/build.py builds that one as libprt_hip_dev.so for the tests and sweep tools
@@ -343,6 +348,64 @@ struct PrtScene {
             }
         return out;
     }
+    // What k32.d shares with k64.d: the light tables' place and totals (thresholds are floats in either mode), the tree (the
+    // 32-entry collapse where the scene keeps one), the grid, the texture headers, the counts.  Called by whoever changes one.
+    void share_with_f32() {
+        const DScene& d = k64.d;
+        DSceneT<float>& f = k32.d;
+        f.light_tab = d.light_tab;
+        f.light_root = d.light_root;
+        f.n_lights = d.n_lights;
+        f.light_area = (float)d.light_area;
+        f.nodes = d_nodes_shallow ? d_nodes_shallow : d.nodes;
+        f.n_nodes = d_nodes_shallow ? n_nodes_shallow : d.n_nodes;
+        f.textures = d.textures;
+        f.n_tris = d.n_tris;
+        f.tex_compact = d.tex_compact;
+        f.slab_scale = d.slab_scale;
+        for (int a = 0; a < 3; ++a) {
+            f.grid_origin[a] = d.grid_origin[a];
+            f.grid_step[a] = d.grid_step[a];
+        }
+    }
+    // The quantisation grid of the resident tree, in every copy: the host tree's and both DScenes'.
+    void set_grid(const float origin[3], const float step[3], float coord_scale) {
+        DScene& d = k64.d;
+        // box coordinates reach the slab test relative to the grid origin: what bounds its rounding is the grid's extent
+        double e = 0.0;
+        for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)step[a]);
+        bvh.coord_scale = coord_scale;
+        for (int a = 0; a < 3; ++a) {
+            bvh.grid_origin[a] = d.grid_origin[a] = origin[a];
+            bvh.grid_step[a] = d.grid_step[a] = step[a];
+        }
+        d.slab_scale = std::nextafter((float)e, std::numeric_limits<float>::infinity());
+        if (f32_ready) share_with_f32();
+    }
+    // A tree the device builder made is the scene's from here on (its arrays have an owner already): what the kernels, the
+    // refit, the host tree's record and the reports get of it.
+    void adopt_device_tree(const prt::DeviceBVH& db) {
+        k64.d.nodes = db.d_nodes;
+        k64.d.n_nodes = db.n_nodes;
+        d_order = db.d_order;
+        bvh.depth = db.depth;
+        last.bvh_nodes = bvh_info.n_nodes = db.n_nodes;
+        last.bvh_depth = bvh_info.depth = db.depth;
+        bvh_info.built_on_device = 1;
+        bvh_info.build_ms = db.ms_total;
+        bvh_info.sort_ms = db.ms_sort;
+        bvh_info.tree_ms = db.ms_tree;
+        bvh_info.split_ms = db.ms_split;
+    }
+    void set_stack_need(int need) { stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH); }
+    // The 32-entry collapse of a deep host-built tree becomes resident (same leaf order as the full tree: the records fit
+    // both), unless it is already or the scene has none.  Not one of the uploads PRT_TEST_FAIL_UPLOAD counts.
+    int shallow_resident() {
+        if (stack_need <= PRT_STACK_SHALLOW || d_nodes_shallow || bvh_info.built_on_device || bvh.nodes_shallow.empty()) return PRT_OK;
+        if (int rc = up(bvh.nodes_shallow, &d_nodes_shallow, false)) return rc;
+        n_nodes_shallow = (uint32_t)bvh.nodes_shallow.size();
+        return PRT_OK;
+    }
     void release() {
         if (device >= 0) (void)hipSetDevice(device);
         allocs.clear();
@@ -461,6 +524,17 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
                          k.blocks_per_cu[0], k.stack_depth, k.mat_lds, k.ltri_lds, k.light_lds);
     }
     return wanted;
+}
+
+// Both precisions' kernels sized again, as at upload and in ensure_f32, for a resident scene whose tree or light tables
+// changed (the ray-batch kernel's blocks per CU are asked for again by its next call).
+static void size_kernels_again(PrtScene* s) {
+    s->k64.blocks_per_cu_rays = 0;
+    s->blocks_wanted = size_kernels(s, s->k64, true);
+    if (s->f32_ready) {
+        s->k32.blocks_per_cu_rays = 0;
+        size_kernels(s, s->k32, false);
+    }
 }
 
 // Resident blocks per CU of the ray-batch kernel of a scene (the production kernels' are queried at upload; this one by the
@@ -747,6 +821,17 @@ int prt_scene_light_order(const PrtScene* s, int32_t* prims, uint64_t cap) {
 
 static int upload_impl(PrtScene* s, int device);
 
+// The stack entries a traversal of a device-built tree can need: the nodes come back once for the count (at most 128 MB;
+// larger trees keep the builders' bound).  Synchronous; host memory for the nodes may run out (std::bad_alloc).
+static hipError_t device_tree_stack_need(const DNode* d_nodes, uint32_t n_nodes, int* need) {
+    *need = PRT_STACK_DEPTH;
+    if (n_nodes > (1u << 21)) return hipSuccess;
+    std::vector<DNode> hn(n_nodes);
+    const hipError_t e = hipMemcpy(hn.data(), d_nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) *need = prt::tree_stack_need(hn.data(), hn.size());
+    return e;
+}
+
 // The corner table of a scene that answers distance queries (prt_scene_set_distance_queries), from the host triangles
 // through the resident leaf order: allocated if the upload has none yet, filled on the null stream, synchronous.  The
 // scene is uploaded and its device is current.
@@ -853,9 +938,8 @@ int prt_scene_upload(PrtScene* s, int device) {
                                    "pass every position to prt_scene_update_vertices or prt_scene_refit first)");
     const int rc = upload_impl(s, device);
     if (rc != PRT_OK) {
-        const std::string keep = g_err;
+        KeepError keep;
         s->release();
-        g_err = keep;
     }
     return rc;
 }
@@ -937,8 +1021,6 @@ static int upload_impl(PrtScene* s, int device) {
         if (!prt::build_bvh_device(pb.data(), box_origin, n, db, &err)) return fail(PRT_E_HIP, "prt_scene_upload: " + err);
         s->allocs.emplace_back(db.d_nodes);
         s->allocs.emplace_back(db.d_order); // the leaf order: the gather below, and prt_scene_refit later
-        s->d_order = db.d_order;
-        d.nodes = db.d_nodes;
         if (dev_env("PRT_VALIDATE_BVH")) { // tests: check the device-built tree on the host before any ray visits it
             std::vector<DNode> hn(db.n_nodes);
             PRT_HIP(hipMemcpy(hn.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
@@ -965,24 +1047,15 @@ static int upload_impl(PrtScene* s, int device) {
         PRT_HIP_AS("prt_scene_upload", hipDeviceSynchronize());
         d.tris = static_cast<const DTri*>(t_out);
         d.shade = static_cast<const DTriShade*>(s_out);
-        s->bvh.depth = db.depth;
-        s->bvh.coord_scale = db.coord_scale;
-        for (int a = 0; a < 3; ++a) {
-            s->bvh.grid_origin[a] = db.grid_origin[a];
-            s->bvh.grid_step[a] = db.grid_step[a];
-        }
-        s->last.bvh_nodes = s->bvh_info.n_nodes = db.n_nodes;
-        s->last.bvh_depth = s->bvh_info.depth = db.depth;
-        s->bvh_info.built_on_device = 1;
-        s->bvh_info.build_ms = db.ms_total;
-        s->bvh_info.sort_ms = db.ms_sort;
-        s->bvh_info.tree_ms = db.ms_tree;
-        s->bvh_info.split_ms = db.ms_split;
+        s->set_grid(db.grid_origin, db.grid_step, db.coord_scale);
+        s->adopt_device_tree(db);
     } else {
         if ((rc = s->up(s->bvh.nodes, &d.nodes))) return rc;
+        d.n_nodes = (uint32_t)s->bvh.nodes.size();
         if ((rc = up_tris(&d.tris))) return rc;
         if ((rc = s->up(ds, &d.shade))) return rc;
         if ((rc = s->up(s->bvh.order, &s->d_order, false))) return rc; // (for prt_scene_refit; not one of the counted table uploads)
+        s->set_grid(s->bvh.grid_origin, s->bvh.grid_step, s->bvh.coord_scale); // (the host tree's own)
     }
     if ((rc = s->up(s->mats, &d.materials))) return rc;
     {
@@ -1045,19 +1118,7 @@ static int upload_impl(PrtScene* s, int device) {
     d.light_root = s->lights.root;
     d.n_lights = (int32_t)s->lights.tris.size();
     d.light_area = s->lights.area;
-    d.n_nodes = s->device_bvh ? (uint32_t)s->bvh_info.n_nodes : (uint32_t)s->bvh.nodes.size();
     d.n_tris = (uint32_t)n;
-    d.slab_scale = s->bvh.coord_scale;
-    for (int a = 0; a < 3; ++a) {
-        d.grid_origin[a] = s->bvh.grid_origin[a];
-        d.grid_step[a] = s->bvh.grid_step[a];
-    }
-    {
-        // box coordinates reach the slab test relative to the grid origin: what bounds its rounding is the grid's extent
-        double e = 0.0;
-        for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)s->bvh.grid_step[a]);
-        d.slab_scale = std::nextafter((float)e, std::numeric_limits<float>::infinity());
-    }
     for (PrtScene::CallSlot& q : s->slots) {
         PRT_HIP_AS("hipMalloc", dev_alloc(q.d_ctr, sizeof(DCounters)));
         PRT_HIP(hipMemset(q.d_ctr.get(), 0, sizeof(DCounters)));
@@ -1080,15 +1141,12 @@ static int upload_impl(PrtScene* s, int device) {
     // Measured: materials cornell +2.5 %, bathroom2 +3 %, veach-mis +2 %; light tree veach-mis +5 %.
     // LDS traversal stacks of K3 are sized from what THIS tree can need (tree_stack_need), not from the builders' bound
     {
-        int need = PRT_STACK_DEPTH;
-        if (!s->bvh_info.built_on_device) need = s->bvh.stack_need;
-        else if (d.n_nodes <= (1u << 21)) { // device-built: the nodes come back once for the count (at most 128 MB; larger trees keep the bound)
-            std::vector<DNode> hn(d.n_nodes);
-            PRT_HIP(hipMemcpy(hn.data(), d.nodes, (size_t)d.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
-            need = prt::tree_stack_need(hn.data(), hn.size());
-        }
+        int need = s->bvh.stack_need;
+        if (s->bvh_info.built_on_device) // (the text is the one this failure has had since the copy stood here)
+            PRT_HIP_AS("hipMemcpy(hn.data(), d.nodes, (size_t)d.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost)",
+                       device_tree_stack_need(d.nodes, d.n_nodes, &need));
         if (dump_path && (rc = dump_bvh(dump_path, s, dump_nodes.data(), dump_nodes.size(), dump_order.data(), need))) return rc;
-        s->stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH);
+        s->set_stack_need(need);
         s->d_nodes_shallow = nullptr;
         s->n_nodes_shallow = 0;
         // The fp64 render kernels keep STATIC stacks of PRT_STACK_DEPTH entries per lane (they are register-limited to three
@@ -1185,12 +1243,11 @@ static int ensure_f32(PrtScene* s) {
     const size_t mark = s->allocs.size();
     const int rc = ensure_f32_impl(s);
     if (rc != PRT_OK) {
-        const std::string keep = g_err;
+        KeepError keep;
         s->allocs.resize(mark);
         s->k32 = KernelConfig<float>();
         s->light_res.nodes32 = s->light_res.tris32 = nullptr;
         s->light_res.cap_nodes32 = s->light_res.cap_tris32 = 0;
-        g_err = keep;
     }
     return rc;
 }
@@ -1235,40 +1292,20 @@ static int ensure_f32_impl(PrtScene* s) {
     s->light_res.cap_nodes32 = ln.size();
     s->light_res.cap_tris32 = lt.size();
     PRT_HIP(hipDeviceSynchronize());
-    f.nodes = d.nodes;
     f.tris = static_cast<const DTriT<float>*>(t);
     f.shade = static_cast<const DTriShadeT<float>*>(sh);
-    f.textures = d.textures;
     f.texels_lin = static_cast<const float*>(tx);
-    f.light_root = d.light_root;
-    f.light_tab = d.light_tab; // thresholds are floats in either mode
-    f.n_lights = d.n_lights;
-    f.light_area = (float)d.light_area;
-    f.n_nodes = d.n_nodes;
-    f.n_tris = d.n_tris;
-    f.slab_scale = d.slab_scale;
-    for (int a = 0; a < 3; ++a) {
-        f.grid_origin[a] = d.grid_origin[a];
-        f.grid_step[a] = d.grid_step[a];
-    }
     f.tri_stride = stride;
-    f.tex_compact = d.tex_compact;
     // The fp32 kernels have the registers for a fourth wave per SIMD; whether the LDS has room for a fourth block per CU
     // is decided by the traversal stacks: 32 entries per lane (32 KB per block) leave it, the builders' bound of
     // PRT_STACK_DEPTH does not.  Most trees need far fewer entries than that bound (tree_stack_need).
     {
         int need = s->stack_need; // of the tree the fp64 K3 traverses
-        if (need > PRT_STACK_SHALLOW && !s->d_nodes_shallow && !s->bvh_info.built_on_device && !s->bvh.nodes_shallow.empty()) {
-            // the same binary tree collapsed for 32 entries (same leaf order: the records above fit both): the fp32 kernels
-            // have the registers for a fourth block per CU, which 32-entry stacks leave the LDS for
-            if ((rc = s->up(s->bvh.nodes_shallow, &s->d_nodes_shallow, false))) return rc;
-            s->n_nodes_shallow = (uint32_t)s->bvh.nodes_shallow.size();
-        }
-        if (s->d_nodes_shallow) {
-            f.nodes = s->d_nodes_shallow;
-            f.n_nodes = s->n_nodes_shallow;
-            need = std::min(need, PRT_STACK_SHALLOW);
-        }
+        // the same binary tree collapsed for 32 entries: the fp32 kernels have the registers for a fourth block per CU,
+        // which 32-entry stacks leave the LDS for
+        if ((rc = s->shallow_resident())) return rc;
+        if (s->d_nodes_shallow) need = std::min(need, PRT_STACK_SHALLOW);
+        s->share_with_f32(); // (the collapse, where there is one, is the tree k32 traverses)
         k.stack_depth = f32_stack_depth(need);
         if (dev_env("PRT_TUNE_VERBOSE")) std::fprintf(stderr, "[prt] fp32 tables: tree needs %d stack entries, using %d\n", need, k.stack_depth);
     }
@@ -1299,6 +1336,16 @@ float f32_round_up(double v) {
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 } // namespace
 
+// The refit state of the resident tree's topology, on `st`: the parents of every node, and the SAH cost that sah_ratio is
+// measured against from now on.  The copy's status comes back; the launches report through hipGetLastError.
+static hipError_t refit_baseline(PrtScene* s, hipStream_t st) {
+    const PrtScene::Refit& R = s->refit;
+    const DScene& d = s->k64.d;
+    prt::launch_refit_parents(d.nodes, d.n_nodes, R.d_parent, st);
+    prt::launch_refit_sah(d.nodes, d.n_nodes, d.grid_origin, d.grid_step, R.d_scratch, R.d_sah, st);
+    return hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st);
+}
+
 // What the first refit after an upload adds to the resident scene: its working arrays and events, the 32-entry collapse
 // of a deep host-built tree (so that every resident node array is refitted from the first time on), the parents of
 // every node, and the SAH cost of the tree as built.
@@ -1316,18 +1363,14 @@ static int refit_prepare(PrtScene* s, hipStream_t st) {
         PRT_HIP(make_event(R.ev1, hipEventDefault));
         PRT_HIP(make_event(R.ev2, hipEventDefault));
         PRT_HIP(make_event(R.done, hipEventDisableTiming));
-        if (s->stack_need > PRT_STACK_SHALLOW && !s->d_nodes_shallow && !s->bvh_info.built_on_device && !s->bvh.nodes_shallow.empty()) {
-            if ((rc = s->up(s->bvh.nodes_shallow, &s->d_nodes_shallow, false))) return rc; // (ensure_f32 then finds it resident)
-            s->n_nodes_shallow = (uint32_t)s->bvh.nodes_shallow.size();
-        }
+        if ((rc = s->shallow_resident())) return rc; // (ensure_f32 then finds it resident)
         R.d_tbox = static_cast<float*>(tbox);
         R.d_parent = static_cast<uint32_t*>(parent);
         R.d_cnt = static_cast<uint32_t*>(cnt);
         R.d_scratch = scratch;
         R.d_sah = static_cast<double*>(sah);
-        prt::launch_refit_parents(d.nodes, d.n_nodes, R.d_parent, st);
-        prt::launch_refit_sah(d.nodes, d.n_nodes, d.grid_origin, d.grid_step, R.d_scratch, R.d_sah, st);
-        PRT_HIP(hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st));
+        // (the text is the one a failure of the copy has had since the copy stood here)
+        PRT_HIP_AS("hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st)", refit_baseline(s, st));
         PRT_HIP(hipGetLastError());
         R.d_check = static_cast<prt::RefitCheck*>(check);
     }
@@ -1348,17 +1391,19 @@ static int refit_prepare(PrtScene* s, hipStream_t st) {
 struct RefitGridHost {
     float origin[3], step[3], root_hi[3]; // the fp32 grid origin; the grid's steps and the root box's upper corner relative to it
     double origin_d[3], delta;            // the origin widened; prim_boxes' margin
+    bool lights_moved = false;            // ... and whether light_stage has work (see refit_begin)
 };
 
 // What a refit and a rebuild share up to the decision.  after_refit, the working arrays (refit_prepare; a failure frees what
 // this call made), then phase 1, read-only: vertex range, scene bounds, emitters in place; the one read-back; the grid.
-// *lights_moved: an emitter vertex differs and the scene accepts that (prt_scene_set_dynamic_lights): the gathered new
+// g.lights_moved: an emitter vertex differs and the scene accepts that (prt_scene_set_dynamic_lights): the gathered new
 // vertices (and vertex normals, with d_normals) of the light triangles are in s->lu.h_gather.
 static int refit_begin(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st,
-                       RefitGridHost& g, bool* lights_moved) {
+                       RefitGridHost& g) {
     DScene& d = s->k64.d;
     const uint32_t n = d.n_tris;
     PrtScene::Refit& R = s->refit;
+    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
     PRT_HIP_AS(who, s->after_refit(st)); // one refit at a time: they share the working arrays
     {
         const size_t mark = s->allocs.size();
@@ -1367,7 +1412,7 @@ static int refit_begin(PrtScene* s, const std::string& who, const double* d_vert
         const uint32_t n_shallow_before = s->n_nodes_shallow;
         const int rc = refit_prepare(s, st);
         if (rc != PRT_OK) { // (nothing resident has been written)
-            const std::string keep = g_err;
+            KeepError keep;
             if (fresh) {
                 (void)hipDeviceSynchronize();
                 s->allocs.resize(mark);
@@ -1375,11 +1420,9 @@ static int refit_begin(PrtScene* s, const std::string& who, const double* d_vert
                 s->d_nodes_shallow = shallow_before; // only what this call uploaded went with `mark`
                 s->n_nodes_shallow = n_shallow_before;
             }
-            g_err = keep;
             return rc;
         }
     }
-    *lights_moved = false;
     PrtScene::LightUpdate& U = s->lu;
     const size_t nl = (size_t)d.n_lights;
     const bool gather = s->dynamic_lights && nl > 0;
@@ -1416,7 +1459,7 @@ static int refit_begin(PrtScene* s, const std::string& who, const double* d_vert
     if ((c.flags & 2u) && !s->dynamic_lights)
         return fail(PRT_E_INVALID, who + ": a vertex of a light mesh moved; emitters stay in place under a refit (the light tree is not "
                                          "rebuilt) - use prt_scene_update_vertices");
-    *lights_moved = (c.flags & 2u) != 0;
+    g.lights_moved = (c.flags & 2u) != 0;
     // the quantisation grid of the new bounds: prim_boxes' origin and margin, quant_grid's steps.  The root box of the
     // builders is the union of the triangles' fp32 boxes; rounding and the subtraction are monotone, so its upper corner
     // is the box rule applied to the upper corner of the bounds.
@@ -1492,9 +1535,8 @@ static int light_stage(PrtScene* s, const std::string& who, bool normals, hipStr
         U.staged_gather_ms = hipEventElapsedTime(&ms, U.g0.get(), U.g1.get()) == hipSuccess ? ms : 0.0;
     }
     auto failed = [&](int rc) {
-        const std::string keep = g_err;
+        KeepError keep;
         light_unstage(s);
-        g_err = keep;
         return rc;
     };
     if (U.next.tris.size() != nl) return failed(fail(PRT_E_INVALID, who + ": the set of light triangles changed"));
@@ -1599,31 +1641,30 @@ static void light_commit(PrtScene* s) {
         DSceneT<float>& f = s->k32.d;
         f.light_nodes = static_cast<const DLightNodeT<float>*>(A.nodes32);
         f.light_tris = static_cast<const DLightTriT<float>*>(A.tris32);
-        f.light_tab = d.light_tab;
-        f.light_root = d.light_root;
-        f.n_lights = d.n_lights;
-        f.light_area = (float)d.light_area;
+        s->share_with_f32();
     }
     ++U.count;
     U.host_tree_ms = U.staged_host_tree_ms;
     U.gather_ms = U.staged_gather_ms;
     U.relaid = U.staged_relaid ? 1u : 0u;
     U.tables_dropped = U.staged_dropped ? 1u : 0u;
-    if (U.staged_relaid) { // LDS sizing and render_variant may change (PRT_VARIANT_EXTRA depends on the tables' presence)
-        s->k64.blocks_per_cu_rays = 0;
-        s->blocks_wanted = size_kernels(s, s->k64, true);
-        if (s->f32_ready) {
-            s->k32.blocks_per_cu_rays = 0;
-            size_kernels(s, s->k32, false);
-        }
-    }
+    if (U.staged_relaid) size_kernels_again(s); // LDS sizing and render_variant may change (PRT_VARIANT_EXTRA depends on the tables' presence)
 }
 
-// The writing phase changes what calls in flight read: `st` waits for both call slots and the last features call first.
-static int refit_wait_readers(PrtScene* s, const std::string& who, hipStream_t st) {
+// From the decision to the writing phase: moved emitters are staged (the last thing that can refuse); the writing phase
+// changes what calls in flight read, so `st` waits for both call slots and the last features call first; then the swap.
+static int lights_then_readers(PrtScene* s, const std::string& who, bool lights_moved, bool normals, hipStream_t st) {
+    if (lights_moved)
+        if (const int rc = light_stage(s, who, normals, st)) return rc;
+    hipError_t e = hipSuccess;
     for (PrtScene::CallSlot& q : s->slots)
-        if (q.timed) PRT_HIP_AS(who, hipStreamWaitEvent(st, q.done.get(), 0));
-    if (s->feat_pending) PRT_HIP_AS(who, hipStreamWaitEvent(st, s->feat_done.get(), 0));
+        if (q.timed && e == hipSuccess) e = hipStreamWaitEvent(st, q.done.get(), 0);
+    if (s->feat_pending && e == hipSuccess) e = hipStreamWaitEvent(st, s->feat_done.get(), 0);
+    if (e != hipSuccess) {
+        light_unstage(s);
+        return hip_fail(who, e);
+    }
+    light_commit(s);
     return PRT_OK;
 }
 
@@ -1631,20 +1672,14 @@ static int refit_wait_readers(PrtScene* s, const std::string& who, hipStream_t s
 // generation and the grid, in every copy (the host tree's, both DScenes), go first, so that a scene whose records were
 // partly rewritten never passes for the old one.
 static void refit_commit_grid(PrtScene* s, const float origin[3], const float step[3], float coord_scale) {
-    DScene& d = s->k64.d;
-    double e = 0.0;
-    for (int a = 0; a < 3; ++a) e = std::max(e, 65535.0 * (double)step[a]);
-    s->bvh.coord_scale = coord_scale;
-    for (int a = 0; a < 3; ++a) {
-        s->bvh.grid_origin[a] = d.grid_origin[a] = s->k32.d.grid_origin[a] = origin[a];
-        s->bvh.grid_step[a] = d.grid_step[a] = s->k32.d.grid_step[a] = step[a];
-    }
-    d.slab_scale = s->k32.d.slab_scale = std::nextafter((float)e, std::numeric_limits<float>::infinity());
+    s->set_grid(origin, step, coord_scale);
     ++s->generation;
 }
 
-// PRT_TEST_DUMP_BVH: the resident tree, as the kernels now get it (synchronous)
-static int dump_resident_bvh(PrtScene* s, const std::string& who, const char* path, hipStream_t st) {
+// PRT_TEST_DUMP_BVH: the resident tree (refitted or rebuilt), as the kernels now get it (synchronous)
+static int dump_resident_bvh(PrtScene* s, const std::string& who, hipStream_t st) {
+    const char* path = dev_env("PRT_TEST_DUMP_BVH");
+    if (!path) return PRT_OK;
     const DScene& d = s->k64.d;
     std::vector<DNode> hn(d.n_nodes);
     std::vector<uint32_t> ho(d.n_tris);
@@ -1654,33 +1689,13 @@ static int dump_resident_bvh(PrtScene* s, const std::string& who, const char* pa
     return dump_bvh(path, s, hn.data(), hn.size(), ho.data(), s->stack_need);
 }
 
-// d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
-static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
-    DScene& d = s->k64.d;
+// Everything resident that follows new positions, on `st`: the fp64 records and the triangles' boxes (R.d_tbox), then what
+// is derived from them.  A resident table that follows the geometry is added HERE, for the refit and the rebuild alike.
+static void launch_position_followers(PrtScene* s, const double* d_verts, const double* d_normals, const RefitGridHost& g, hipStream_t st) {
+    const DScene& d = s->k64.d;
     const uint32_t n = d.n_tris;
-    if (n == 0) return PRT_OK; // nothing to move (the empty scene's root is never traversed)
-    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
-    PrtScene::Refit& R = s->refit;
-    RefitGridHost g;
-    bool lights_moved = false;
-    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g, &lights_moved)) return rc;
-    const float *origin = g.origin, *step = g.step;
-    if (lights_moved)
-        if (const int rc = light_stage(s, who, d_normals != nullptr, st)) return rc;
-    if (const int rc = refit_wait_readers(s, who, st)) {
-        light_unstage(s);
-        return rc;
-    }
-    light_commit(s);
-    {
-        float cs = std::max(g.root_hi[0], std::max(g.root_hi[1], g.root_hi[2]));
-        if (s->bvh_info.built_on_device) // (the device builder also covers the grid's far corner)
-            for (int a = 0; a < 3; ++a) cs = std::max(cs, (float)(65535.0 * (double)step[a]));
-        refit_commit_grid(s, origin, step, std::nextafter(cs, std::numeric_limits<float>::infinity()));
-    }
-    PRT_HIP_AS(who, hipEventRecord(R.ev0.get(), st));
     prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
-                           R.d_tbox, g.origin_d, g.delta, st);
+                           s->refit.d_tbox, g.origin_d, g.delta, st);
     if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
     if (s->d_corners && s->sq.slot) prt::launch_pseudonormals(s->d_corners, s->sq, st);      // signed queries: the pseudonormals too
     if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
@@ -1688,8 +1703,28 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
         prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
         prt32::launch_convert_shade(d.shade, n, const_cast<DTriShadeT<float>*>(f.shade), st);
     }
+}
+
+// d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
+static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
+    DScene& d = s->k64.d;
+    const uint32_t n = d.n_tris;
+    if (n == 0) return PRT_OK; // nothing to move (the empty scene's root is never traversed)
+    PrtScene::Refit& R = s->refit;
+    RefitGridHost g;
+    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g)) return rc;
+    const float *origin = g.origin, *step = g.step;
+    if (const int rc = lights_then_readers(s, who, g.lights_moved, d_normals != nullptr, st)) return rc;
+    {
+        float cs = std::max(g.root_hi[0], std::max(g.root_hi[1], g.root_hi[2]));
+        if (s->bvh_info.built_on_device) // (the device builder also covers the grid's far corner)
+            for (int a = 0; a < 3; ++a) cs = std::max(cs, (float)(65535.0 * (double)step[a]));
+        refit_commit_grid(s, origin, step, std::nextafter(cs, std::numeric_limits<float>::infinity()));
+    }
+    PRT_HIP_AS(who, hipEventRecord(R.ev0.get(), st));
+    launch_position_followers(s, d_verts, d_normals, g, st);
     PRT_HIP_AS(who, hipGetLastError());
-    PRT_HIP_AS(who, hipEventRecord(R.ev1.get(), st));
+    PRT_HIP_AS(who, hipEventRecord(R.ev1.get(), st)); // (records_ms includes the fp32 re-derivation)
     PRT_HIP_AS(who, prt::launch_refit_boxes(const_cast<DNode*>(d.nodes), d.n_nodes, R.d_parent, R.d_cnt, R.d_tbox, n, step, st));
     if (s->d_nodes_shallow)
         PRT_HIP_AS(who, prt::launch_refit_boxes(const_cast<DNode*>(s->d_nodes_shallow), s->n_nodes_shallow, R.d_parent_sh, R.d_cnt_sh,
@@ -1699,18 +1734,7 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     PRT_HIP_AS(who, hipEventRecord(R.ev2.get(), st));
     PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
     ++R.count;
-    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) // the refitted tree
-        if (const int rc = dump_resident_bvh(s, who, path, st)) return rc;
-    return PRT_OK;
-}
-
-int prt_scene_refit_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
-    int rc = require_uploaded(s, "prt_scene_refit_device");
-    if (rc) return rc;
-    rc = refit_impl(s, "prt_scene_refit_device", static_cast<const double*>(d_vertices), static_cast<const double*>(d_normals),
-                    reinterpret_cast<hipStream_t>(stream));
-    if (rc == PRT_OK && !s->tris.empty()) s->host_stale = true; // the host triangles still hold the old positions
-    return rc;
+    return dump_resident_bvh(s, who, st);
 }
 
 // ---- prt_scene_rebuild: new positions for a resident scene and a NEW tree of them from the device builder; textures,
@@ -1719,11 +1743,9 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     DScene& d = s->k64.d;
     const uint32_t n = d.n_tris;
     if (n < 2) return refit_impl(s, who, d_verts, d_normals, st); // the builder needs two triangles: one triangle's tree has one shape
-    if (!d_verts) return fail(PRT_E_INVALID, who + ": null vertices");
     PrtScene::Refit& R = s->refit;
     RefitGridHost g;
-    bool lights_moved = false;
-    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g, &lights_moved)) return rc;
+    if (const int rc = refit_begin(s, who, d_verts, d_normals, st, g)) return rc;
     // Everything the new tree needs is made before anything resident is written: a failure up to the commit below frees
     // what this call made (the owners are locals) and leaves the scene as it was.
     // test hook (PRT_TEST_FAIL_REBUILD=k): the k-th allocation of the rebuild, the builder run counting as one, reports out-of-memory
@@ -1752,22 +1774,13 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     if ((rc = alloc((size_t)n * sizeof(DTriShade), shade)) || (rc = alloc((size_t)n * sizeof(uint32_t), inv)) ||
         (rc = alloc((size_t)db.n_nodes * sizeof(uint32_t), parent)) || (rc = alloc(round16((size_t)db.n_nodes * sizeof(uint32_t)), cnt)))
         return rc;
-    int need = PRT_STACK_DEPTH; // as at upload: the nodes come back once for the count (larger trees keep the bound)
-    if (db.n_nodes <= (1u << 21)) {
-        try {
-            std::vector<DNode> hn(db.n_nodes);
-            PRT_HIP_AS(who, hipMemcpy(hn.data(), db.d_nodes, hn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
-            need = prt::tree_stack_need(hn.data(), hn.size());
-        } catch (const std::bad_alloc&) {
-            return fail(PRT_E_OOM, who + ": out of host memory");
-        }
+    int need = PRT_STACK_DEPTH; // as at upload
+    try {
+        PRT_HIP_AS(who, device_tree_stack_need(db.d_nodes, db.n_nodes, &need));
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, who + ": out of host memory");
     }
-    if (lights_moved && (rc = light_stage(s, who, d_normals != nullptr, st))) return rc; // (the last thing that can refuse)
-    if ((rc = refit_wait_readers(s, who, st))) {
-        light_unstage(s);
-        return rc;
-    }
-    light_commit(s); // (before the kernels are sized below)
+    if ((rc = lights_then_readers(s, who, g.lights_moved, d_normals != nullptr, st))) return rc; // (before the kernels are sized below)
 
     // Commit.  From here on the refit's wording applies: the generation and the grid are the new ones.  The scene takes
     // the new arrays at once; the ones they replace stay alive in `old` until this call returns (freeing waits for the device).
@@ -1776,10 +1789,8 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     const uint32_t* const order_old = s->d_order;
     DevBuf<> old[8] = {s->take(d.nodes),  s->take(s->d_order),        s->take(d.shade),      s->take(R.d_parent),
                        s->take(R.d_cnt),  s->take(s->d_nodes_shallow), s->take(R.d_parent_sh), s->take(R.d_cnt_sh)};
-    d.nodes = static_cast<const DNode*>(nodes.get());
-    d.n_nodes = db.n_nodes;
+    s->adopt_device_tree(db); // (nodes and order)
     d.shade = static_cast<const DTriShade*>(shade.get());
-    s->d_order = static_cast<const uint32_t*>(order.get());
     R.d_parent = static_cast<uint32_t*>(parent.get());
     R.d_cnt = static_cast<uint32_t*>(cnt.get());
     R.d_parent_sh = R.d_cnt_sh = nullptr; // a device-built tree has no 32-entry collapse
@@ -1787,45 +1798,21 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     s->n_nodes_shallow = 0;
     for (DevBuf<>* b : {&nodes, &order, &shade, &parent, &cnt}) s->allocs.push_back(std::move(*b)); // (room for more than `old` took out)
     s->device_bvh = true; // a later upload builds on the device as well: the host tree is not this one
-    s->bvh.depth = db.depth;
-    s->last.bvh_nodes = s->bvh_info.n_nodes = db.n_nodes;
-    s->last.bvh_depth = s->bvh_info.depth = db.depth;
-    s->bvh_info.built_on_device = 1;
-    s->bvh_info.build_ms = db.ms_total;
-    s->bvh_info.sort_ms = db.ms_sort;
-    s->bvh_info.tree_ms = db.ms_tree;
-    s->bvh_info.split_ms = db.ms_split;
-    s->stack_need = std::min(std::max(need, 1), PRT_STACK_DEPTH);
-    s->k64.blocks_per_cu_rays = 0;
-    s->blocks_wanted = size_kernels(s, s->k64, true);
+    s->set_stack_need(need);
     if (s->f32_ready) {
-        KernelConfig<float>& k = s->k32;
-        k.d.nodes = d.nodes;
-        k.d.n_nodes = d.n_nodes;
-        k.stack_depth = f32_stack_depth(s->stack_need);
-        k.blocks_per_cu_rays = 0;
-        size_kernels(s, k, false);
+        s->share_with_f32(); // (the new nodes: no collapse is left)
+        s->k32.stack_depth = f32_stack_depth(s->stack_need);
     }
+    size_kernels_again(s);
+    // (a rebuild is no refit: none of the refit's timing events is recorded, and refit.count stays)
     prt::launch_permute_shade(shade_old, order_old, s->d_order, n, static_cast<uint32_t*>(inv.get()), const_cast<DTriShade*>(d.shade), st);
-    prt::launch_refit_tris(d_verts, d_normals, s->d_order, n, const_cast<DTri*>(d.tris), d.tri_stride, const_cast<DTriShade*>(d.shade),
-                           R.d_tbox, g.origin_d, g.delta, st);
-    if (s->d_corners) prt::launch_gather_corners(d_verts, s->d_order, n, s->d_corners, st); // distance queries: the corners follow
-    if (s->d_corners && s->sq.slot) prt::launch_pseudonormals(s->d_corners, s->sq, st);      // signed queries: the pseudonormals too
-    if (s->f32_ready) { // the float records follow the fp64 ones (same leaf order)
-        const DSceneT<float>& f = s->k32.d;
-        prt32::launch_convert_tris(d.tris, d.tri_stride, n, const_cast<DTriT<float>*>(f.tris), f.tri_stride, st);
-        prt32::launch_convert_shade(d.shade, n, const_cast<DTriShadeT<float>*>(f.shade), st);
-    }
-    // the refit state of the new topology: parents, and the SAH cost that sah_ratio is measured against from now on
-    prt::launch_refit_parents(d.nodes, d.n_nodes, R.d_parent, st);
-    prt::launch_refit_sah(d.nodes, d.n_nodes, d.grid_origin, d.grid_step, R.d_scratch, R.d_sah, st);
+    launch_position_followers(s, d_verts, d_normals, g, st);
+    // the refit state of the new topology
+    PRT_HIP_AS(who, refit_baseline(s, st));
     PRT_HIP_AS(who, hipGetLastError());
-    PRT_HIP_AS(who, hipMemcpyAsync(R.d_sah + 1, R.d_sah, sizeof(double), hipMemcpyDeviceToDevice, st));
     PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
     PRT_HIP_AS(who, hipStreamSynchronize(st)); // synchronous: the new tree is resident, what it replaced can go
-    if (const char* path = dev_env("PRT_TEST_DUMP_BVH")) // the rebuilt tree
-        if ((rc = dump_resident_bvh(s, who, path, st))) return rc;
-    return PRT_OK;
+    return dump_resident_bvh(s, who, st);
 }
 
 // The host-pointer forms of the refit and the rebuild: the caller's arrays go to the device, the host triangles follow.
@@ -1845,9 +1832,8 @@ static int host_positions(PrtScene* s, const char* name, const double* vertices,
     rc = (rebuild ? rebuild_impl : refit_impl)(s, who, dv, dn, nullptr);
     PRT_HIP_AS(who, s->refit_in.used(nullptr));
     if (rc != PRT_OK) {
-        const std::string keep = g_err;
+        KeepError keep;
         (void)hipStreamSynchronize(nullptr); // the caller's arrays are free again on every way out
-        g_err = keep;
         return rc;
     }
     // the host triangles follow, so that a later upload or update sees this geometry; the host tree does not (the boxes
@@ -1878,13 +1864,22 @@ int prt_scene_rebuild(PrtScene* s, const double* vertices, const double* normals
     return host_positions(s, "prt_scene_rebuild", vertices, normals, true);
 }
 
-int prt_scene_rebuild_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
-    int rc = require_uploaded(s, "prt_scene_rebuild_device");
+// The device-pointer forms: the caller's device arrays as they are, on the caller's stream.
+static int device_positions(PrtScene* s, const char* name, const void* d_vertices, const void* d_normals, void* stream, bool rebuild) {
+    int rc = require_uploaded(s, name);
     if (rc) return rc;
-    rc = rebuild_impl(s, "prt_scene_rebuild_device", static_cast<const double*>(d_vertices), static_cast<const double*>(d_normals),
-                      reinterpret_cast<hipStream_t>(stream));
+    rc = (rebuild ? rebuild_impl : refit_impl)(s, name, static_cast<const double*>(d_vertices), static_cast<const double*>(d_normals),
+                                               reinterpret_cast<hipStream_t>(stream));
     if (rc == PRT_OK && !s->tris.empty()) s->host_stale = true; // the host triangles still hold the old positions
     return rc;
+}
+
+int prt_scene_refit_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
+    return device_positions(s, "prt_scene_refit_device", d_vertices, d_normals, stream, false);
+}
+
+int prt_scene_rebuild_device(PrtScene* s, const void* d_vertices, const void* d_normals, void* stream) {
+    return device_positions(s, "prt_scene_rebuild_device", d_vertices, d_normals, stream, true);
 }
 
 int prt_scene_refit_info(const PrtScene* s, PrtRefitInfo* out) {
@@ -1926,6 +1921,23 @@ int prt_scene_get_dynamic_lights(const PrtScene* s, int* on) {
     return PRT_OK;
 }
 
+// Before a query switch (`what`: its name in the text) changes the tables of an uploaded scene.  On: they are made from the
+// host triangles, which must be current.  Off: the queries in flight, and a refit that may still be writing the tables, end.
+static int query_switch_ready(PrtScene* s, const char* who, bool want, const char* what) {
+    PRT_HIP(hipSetDevice(s->device));
+    if (want) {
+        if (s->host_stale)
+            return fail(PRT_E_INVALID, std::string(who) + ": the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device moved the "
+                                                          "resident geometry past it): switch " + what + " on before moving geometry, or call "
+                                                          "prt_scene_refit or prt_scene_update_vertices first");
+        return PRT_OK;
+    }
+    for (PrtScene::CallSlot& q : s->slots)
+        if (q.timed) PRT_HIP_AS(who, hipEventSynchronize(q.done.get()));
+    if (s->refit.pending) PRT_HIP_AS(who, hipEventSynchronize(s->refit.done.get()));
+    return PRT_OK;
+}
+
 int prt_scene_set_distance_queries(PrtScene* s, int on) {
     const char* who = "prt_scene_set_distance_queries";
     if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
@@ -1938,20 +1950,12 @@ int prt_scene_set_distance_queries(PrtScene* s, int on) {
         s->distance_queries = want;
         return PRT_OK;
     }
-    PRT_HIP(hipSetDevice(s->device));
+    if (const int rc = query_switch_ready(s, who, want, "distance queries")) return rc;
     if (want) {
-        if (s->host_stale)
-            return fail(PRT_E_INVALID, std::string(who) + ": the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device moved the "
-                                                          "resident geometry past it): switch distance queries on before moving geometry, or call "
-                                                          "prt_scene_refit or prt_scene_update_vertices first");
         if (const int rc = corners_from_host(s, who)) return rc; // (nothing is kept on a failure: the switch stays off)
         s->distance_queries = true;
         return PRT_OK;
     }
-    // off: the table goes once the queries in flight, and a refit that may still be writing it, have ended
-    for (PrtScene::CallSlot& q : s->slots)
-        if (q.timed) PRT_HIP_AS(who, hipEventSynchronize(q.done.get()));
-    if (s->refit.pending) PRT_HIP_AS(who, hipEventSynchronize(s->refit.done.get()));
     s->take(s->d_corners).reset();
     s->d_corners = nullptr;
     s->distance_queries = false;
@@ -1974,12 +1978,8 @@ int prt_scene_set_signed_queries(PrtScene* s, int on) {
         if (want) s->distance_queries = true;
         return PRT_OK;
     }
-    PRT_HIP(hipSetDevice(s->device));
+    if (const int rc = query_switch_ready(s, who, want, "signed queries")) return rc;
     if (want) {
-        if (s->host_stale)
-            return fail(PRT_E_INVALID, std::string(who) + ": the host geometry is stale (prt_scene_refit_device / prt_scene_rebuild_device moved the "
-                                                          "resident geometry past it): switch signed queries on before moving geometry, or call "
-                                                          "prt_scene_refit or prt_scene_update_vertices first");
         const bool had_corners = s->distance_queries;
         if (!had_corners)
             if (const int rc = corners_from_host(s, who)) return rc;
@@ -1993,10 +1993,6 @@ int prt_scene_set_signed_queries(PrtScene* s, int on) {
         s->distance_queries = s->signed_queries = true;
         return PRT_OK;
     }
-    // off: the tables go once the queries in flight, and a refit that may still be writing them, have ended
-    for (PrtScene::CallSlot& q : s->slots)
-        if (q.timed) PRT_HIP_AS(who, hipEventSynchronize(q.done.get()));
-    if (s->refit.pending) PRT_HIP_AS(who, hipEventSynchronize(s->refit.done.get()));
     signed_free(s);
     s->signed_queries = false;
     return PRT_OK;

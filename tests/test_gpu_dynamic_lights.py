@@ -283,6 +283,82 @@ def test_fp32_frames_follow_every_motion(gpu, name, entry, device_bvh, tables_fi
     sc.close()
 
 
+def chain_motions(data):
+    """The chain of test_every_follower_through_a_chain_of_motions: (entry point, tag, vertices), each motion from the start
+    positions and each a pure function of position within a mesh, so that bitwise-welded corners stay welded (the signed
+    tables' ids are made at upload and kept)."""
+    from tests.test_gpu_signed_distance import wobble
+    return [("refit_device", "translate", translate(data)), ("rebuild", "scale", scale(data)), ("refit", "wobble", wobble(data.vertices)),
+            ("rebuild_device", "rotate", rotate(data)), ("refit", "back", back(data))]
+
+
+def follower_scene(data, device_bvh):
+    """Every follower of the geometry resident at once: dynamic lights, signed (hence distance) queries, the fp32 tables."""
+    sc = api.Scene(data, device_bvh=device_bvh)
+    sc.dynamic_lights = True
+    sc.signed_queries = True
+    sc.upload(0)
+    sc.render(**F32)
+    assert sc.distance_queries is True and sc.bvh_info()["render_variant"] >> 8
+    return sc
+
+
+@pytest.mark.parametrize("device_bvh", BUILDERS)
+def test_every_follower_through_a_chain_of_motions(gpu, device_bvh):
+    """Case D with dynamic lights, signed queries and the fp32 tables resident, through refit_device -> rebuild -> refit ->
+    rebuild_device -> refit on ONE scene (each path inherits what the previous one left: the rebuild replaces the refit's
+    parents and counters, drops the shallow tree and sizes both kernel configs again).  After each step the scene is a fresh
+    scene's of the same vertices, builder and switches, each quantity by the comparison of its own per-feature test: light
+    order, table words, picks, pseudonormals, signed and closest-point records bit for bit; fp64 hits within the hit
+    tolerance; fp32 hits at tier 2; the fp64 frame within 1e-9 on every pixel; the fp32 frame at the second tier."""
+    from tests import signed_distance_model as SM
+    from tests.closest_point_model import queries
+    from tests.test_gpu_refit import assert_same_hits, assert_same_hits_tier2, trace_dev
+    from tests.test_gpu_signed_distance import check_contract
+    data = case("D")
+    org = origins("D")
+    welds = SM.topology(data.vertices)["info"]
+    q = queries(data.vertices, 1024, 77)
+    p = np.ascontiguousarray(np.concatenate([q["near"][0], q["box"][0]]))
+    assert p.shape[0] == 2048
+    sc = follower_scene(data, device_bvh)
+    refits = sc.refit_info()["refits"]
+    for step, (entry, tag, v) in enumerate(chain_motions(data)):
+        label = f"D {step} {entry} {tag}"
+        v = np.ascontiguousarray(v)
+        assert SM.topology(v)["info"] == welds, label  # the welds survived
+        move(sc, entry, v, data.normals)
+        refits += entry.startswith("refit")
+        info = sc.refit_info()
+        assert info["refits"] == refits, label
+        assert info["host_stale"] == (1 if entry.endswith("_device") else 0), label
+        assert sc.light_update_info()["updates"] == step + 1, label
+        assert sc.signed_queries is True and sc.distance_queries is True and sc.dynamic_lights is True
+        fresh = follower_scene(with_vertices(data, v), device_bvh)
+        assert np.array_equal(sc.light_order(), fresh.light_order()), label
+        assert np.array_equal(sc.light_table_words(), fresh.light_table_words()), label
+        assert_same_picks(sc.sample_lights(org, seed=9), fresh.sample_lights(org, seed=9), label, exact_positions=True)
+        P = fresh.pseudonormals()
+        assert sc.pseudonormals().tobytes() == P.tobytes(), label
+        signed, closest = sc.signed_distance(p), sc.closest_point(p)
+        assert signed.tobytes() == fresh.signed_distance(p).tobytes(), label
+        assert closest.tobytes() == fresh.closest_point(p).tobytes(), label
+        check_contract(signed, closest, p, v, P, label)
+        lo, hi = v.reshape(-1, 3).min(0), v.reshape(-1, 3).max(0)
+        pad = 0.25 * np.maximum(hi - lo, 1e-3)
+        rays = scenes.random_rays(2000, lo - pad, hi + pad, seed=6 + step)
+        (g, go), (r, ro) = trace_dev(sc, rays), trace_dev(fresh, rays)
+        assert np.array_equal(go, ro), label
+        assert_same_hits(g, r, rays, v, label)
+        (g, go), (r, ro) = trace_dev(sc, rays, precision=_abi.PRECISION_F32), trace_dev(fresh, rays, precision=_abi.PRECISION_F32)
+        assert_same_hits_tier2(g, r, rays, v, label, "D")
+        assert (go != ro).sum() <= 1e-4 * rays.shape[0], label
+        compare_images(sc.render(**RENDER), fresh.render(**RENDER), max_bad=0)
+        assert_f32_frame(sc.render(**F32), fresh.render(**F32), label)
+        fresh.close()
+    sc.close()
+
+
 def test_switch_off_refuses_a_moved_emitter_as_before(gpu):
     """The default: a moved emitter vertex is PRT_E_INVALID with today's message through all four entry points, and frames,
     picks and table words stay bit-equal."""
