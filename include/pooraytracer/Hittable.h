@@ -64,6 +64,11 @@ public:
     // welded topology and the pseudonormals on the device from the first use on (prt_scene_set_signed_queries).  Not virtual.
     std::vector<bool> SignedDistance(const std::vector<point3>& p, double maxDist, std::vector<point3>& closest,
                                      std::vector<double>& signedDistance) const;
+    // The generalized winding number of every p[i] with respect to this object - prt_winding_number (device): about 1 inside,
+    // about 0 outside, and still usable (threshold 0.5) where the object is open, has seams or duplicated faces, which
+    // SignedDistance's sign is not.  beta > 1 trades error for work (PRT_WINDING_BETA_DEFAULT; infinity: the exact sum).  The
+    // scene keeps the moments table on the device from the first use on (prt_scene_set_winding_queries).  Not virtual.
+    std::vector<double> WindingNumber(const std::vector<point3>& p, double beta = 2.0) const;
     virtual AABB BoundingBox() const = 0;
     // lights.Sample(origin, record, pdf): one sample through prt_sample_lights (device).
     virtual void Sample(const point3& origin, HitRecord& samplePointRecord, double& pdf) const;

@@ -649,6 +649,69 @@ int prt_signed_distance(PrtScene* scene, const PrtPointQuery* q, size_t n, PrtSi
 int prt_signed_distance_device(PrtScene* scene, const void* d_q, size_t n, void* d_out, int count_work, void* hip_stream);
 
 /*
+ * Winding-number queries: inside / outside that survives open meshes.  The sign of prt_signed_distance means something only
+ * where PrtTopologyInfo.closed == 1, and crossing parity from prt_trace_multi flips at every hole.  The generalized winding
+ * number (Jacobson, Kavan and Sorkine-Hornung, "Robust inside-outside segmentation using generalized winding numbers",
+ * SIGGRAPH 2013) is the signed solid angle the mesh subtends at the query point, over 4 pi: exactly 0 or 1 for a closed
+ * mesh, and it degrades smoothly across holes, seams, duplicated faces and self-intersections; w > 0.5 is a usable "inside".
+ * The exact sum costs O(triangles) per query; the fast form (Barill, Dickson, Schmidt, Levin and Jacobson, "Fast winding
+ * numbers for soups and clouds", SIGGRAPH 2018) replaces a far cluster of the BVH by its dipole and costs O(log n).  Only
+ * the dipole (first-order) term is used.
+ *
+ * The switch.  prt_scene_set_winding_queries(scene, 1) makes an uploaded scene keep, beside the corner table of the distance
+ * queries, one 64-byte fp64 record {N[3], c[3], r, A} for every child slot of every node of the resident tree: 256 bytes per
+ * node, indexed [node][slot], all zero for an unused slot.  The rules are those of prt_scene_set_signed_queries: any time;
+ * survives prt_scene_upload / prt_scene_update_vertices; switching on also switches distance queries on (a failure leaves
+ * both as they were), and prt_scene_set_distance_queries(scene, 0) while winding queries are on is PRT_E_INVALID; refused
+ * while the host geometry is stale; synchronous for an uploaded scene; switching off frees the table (distance queries stay
+ * on).  The table is made again wherever the tree or the corners change: by prt_scene_upload and
+ * prt_scene_update_vertices, by prt_scene_refit* on the call's stream behind the box refit (no new host synchronisation),
+ * and by prt_scene_rebuild* for the new node array (allocated before anything resident is written: all or nothing).
+ *
+ * Records (winding_number.hip; fp64, no fused multiply-adds; every sum starts from 0.0 and is taken in the stated order).
+ *   Leaf slot, its triangles in leaf order, resident corners v0, v1, v2:  av = 0.5 cross(v1 - v0, v2 - v0), a = sqrt(dot(av,
+ *   av)), g = ((v0 + v1) + v2) / 3; a triangle whose a is 0 or not finite contributes nothing;  A = sum a, N = sum av,
+ *   G = sum a g;  c = A > 0 ? G / A : v0 of the first triangle;  r = the largest sqrt(|v - c|^2) over all corners of the slot.
+ *   Inner slot that refers to node m, m's used slots s in slot order:  A = sum A_s, N = sum N_s, G = sum A_s c_s;
+ *   c = A > 0 ? G / A : c of m's first used slot;  r = max over s of (sqrt(|c_s - c|^2) + r_s).
+ * One tree and one corner table always give the same bits (a bottom-up pass without floating-point atomics).
+ *
+ * prt_scene_winding_moments (test hook): out[node][slot][0..7] = N, c, r, A as the device holds them; *n = the nodes of the
+ * resident tree, of which min(*n, cap_nodes) are written.  Synchronous.  PRT_E_INVALID while the switch is off,
+ * PRT_E_NO_DEVICE unless uploaded.
+ */
+int prt_scene_set_winding_queries(PrtScene* scene, int on);
+int prt_scene_get_winding_queries(const PrtScene* scene, int* on);
+int prt_scene_winding_moments(PrtScene* scene, double* out /* [n_nodes][4][8] */, uint64_t cap_nodes, uint64_t* n);
+
+#define PRT_WINDING_BETA_DEFAULT 2.0
+/* Contract:
+ *  1. out[i] = S / (4 pi), S from this walk, started at the root.  For each used slot of the node, with its record:
+ *     d = c - p, dd = dot(d, d), br = beta * r;  if dd > br * br (far): S += dot(N, d) / (dd * sqrt(dd));  else, for a leaf:
+ *     S += Omega of each of its triangles;  else: the child is walked.  Omega = 2 atan2(num, den) with a = v0 - p, b = v1 - p,
+ *     c = v2 - p, num = dot(a, cross(b, c)), den = |a||b||c| + dot(a,b)|c| + dot(b,c)|a| + dot(c,a)|b| (Van Oosterom and
+ *     Strackee 1983).  All of it in fp64 without contraction; dot(x, y) is x0 y0 + x1 y1 + x2 y2.  The ORDER in which the
+ *     terms of one query are added is fixed by the tree (a node's far terms in slot order, then its near slots in slot
+ *     order, depth first) and not part of the contract beyond that: the value is within a few ulps of |terms| of any order.
+ *     (A leaf slot whose ref equals that of the slot before it is skipped: the root of a one-triangle tree lists its leaf twice.)
+ *  2. Sign: +1 inside a closed mesh whose faces are counter-clockwise seen from outside.
+ *  3. beta = +inf takes no far term: the value is the exact sum over every triangle.  Larger beta: smaller error, more work.
+ *  4. The value is a pure function of the query, beta, the resident tree and the tables: batch order, batch splitting,
+ *     count_work and the refill schedule change no bit.
+ *  5. The value DOES depend on the tree, unlike the other point queries: the two builders, a refit and a rebuild give
+ *     values that differ by the approximation error (beta = +inf: by rounding only).
+ *  6. For a query on the surface the value is finite; nothing else is promised there.  max_dist is not read.
+ *  7. fp64 only: no fp32 form and no sorted form.
+ *  8. Errors, in this order: PRT_E_INVALID while the switch is off (the message names the function and
+ *     prt_scene_set_winding_queries; before PRT_E_NO_DEVICE); PRT_E_INVALID for beta NaN or <= 1; then items 6 to 8 of the
+ *     closest-point contract, with an output of n doubles that must be 8-byte aligned.
+ *  9. With count_work != 0 prt_get_counters reports node_fetches = nodes walked, tri_tests = Omega evaluations,
+ *     inner_rounds = far terms taken at inner slots, leaf_rounds = far terms taken at leaf slots. */
+int prt_winding_number(PrtScene* scene, const PrtPointQuery* q, size_t n, double beta, double* out, int count_work); /* host buffers, synchronous */
+/* d_q: n PrtPointQuery (one device buffer serves all three point queries), d_out: n doubles; stream may be NULL. */
+int prt_winding_number_device(PrtScene* scene, const void* d_q, size_t n, double beta, void* d_out, int count_work, void* hip_stream);
+
+/*
  * Multi-hit queries: for each of n rays, the first k surfaces along it, in order - thickness and X-ray measurements,
  * crossing parity, entry/exit pairs of closed shells, layered transparency done by the caller, depth layers.  K7
  * (multi_hit.hip): K1's persistent waves and box stepping with a leaf step that keeps a sorted per-lane list.  One

@@ -356,6 +356,11 @@ EXPORTS = [
     "prt_scene_pseudonormals",
     "prt_signed_distance",
     "prt_signed_distance_device",
+    "prt_scene_set_winding_queries",
+    "prt_scene_get_winding_queries",
+    "prt_scene_winding_moments",
+    "prt_winding_number",
+    "prt_winding_number_device",
     "prt_scene_light_update_info",
     "prt_scene_light_table_words",
     "prt_scene_bvh_info",

@@ -71,6 +71,11 @@ def load():
     L.prt_scene_pseudonormals.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.prt_signed_distance.argtypes = [vp, vp, sz, vp, i32]
     L.prt_signed_distance_device.argtypes = [vp, vp, sz, vp, i32, vp]
+    L.prt_scene_set_winding_queries.argtypes = [vp, i32]
+    L.prt_scene_get_winding_queries.argtypes = [vp, C.POINTER(C.c_int)]
+    L.prt_scene_winding_moments.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.prt_winding_number.argtypes = [vp, vp, sz, C.c_double, vp, i32]
+    L.prt_winding_number_device.argtypes = [vp, vp, sz, C.c_double, vp, i32, vp]
     L.prt_scene_light_table_words.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.prt_scene_light_count.argtypes = [vp, C.POINTER(u64)]
     L.prt_scene_light_order.argtypes = [vp, vp, u64]
@@ -506,6 +511,47 @@ class Scene:
         """prt_signed_distance_device: asynchronous, on device buffers (n PrtPointQuery, n PrtSignedDistance of 64 bytes,
         32-byte aligned).  The queries are not checked on the host."""
         _check(self._L.prt_signed_distance_device(self._h, d_q_ptr, int(n), d_out_ptr, int(count_work), stream), self._L)
+
+    @property
+    def winding_queries(self):
+        """Whether the scene answers winding_number* (prt_scene_set_winding_queries): off by default; switching on also
+        switches distance_queries on, and an uploaded scene then keeps four 64-byte moment records per tree node on the
+        device; refit* refresh them, rebuild* make the new tree's."""
+        on = C.c_int(0)
+        _check(self._L.prt_scene_get_winding_queries(self._h, C.byref(on)), self._L)
+        return bool(on.value)
+
+    @winding_queries.setter
+    def winding_queries(self, on):
+        _check(self._L.prt_scene_set_winding_queries(self._h, int(bool(on))), self._L)
+
+    def winding_moments(self):
+        """prt_scene_winding_moments: float64 [n_nodes, 4, 8] - per child slot of every node of the resident tree the record
+        N[3], c[3], r, A as the device holds it; zeros for an unused slot."""
+        n = C.c_uint64(0)
+        _check(self._L.prt_scene_winding_moments(self._h, None, 0, C.byref(n)), self._L)
+        out = np.zeros((int(n.value), 4, 8), dtype=np.float64)
+        _check(self._L.prt_scene_winding_moments(self._h, out.ctypes.data, out.shape[0], C.byref(n)), self._L)
+        assert n.value == out.shape[0]
+        return out
+
+    def winding_number(self, points, beta=2.0, count_work=False):
+        """Generalized winding number of each point (prt_winding_number): points float64 (n, 3).  Returns float64 [n]: ~1
+        inside a closed mesh whose faces are counter-clockwise seen from outside, ~0 outside, in between across holes.
+        beta > 1 trades error for work; beta = inf is the exact sum over every triangle.  The value depends on the tree."""
+        q = _point_queries("winding_number", points, 0.0)
+        out = np.zeros(q.shape[0], dtype=np.float64)
+        _check(self._L.prt_winding_number(self._h, q.ctypes.data, q.shape[0], float(beta), out.ctypes.data, int(count_work)), self._L)
+        return out
+
+    def winding_number_device(self, d_q_ptr, n, d_out_ptr, beta=2.0, count_work=False, stream=None):
+        """prt_winding_number_device: asynchronous, on device buffers (n PrtPointQuery, n doubles).  The queries are not
+        checked on the host."""
+        _check(self._L.prt_winding_number_device(self._h, d_q_ptr, int(n), float(beta), d_out_ptr, int(count_work), stream), self._L)
+
+    def inside(self, points, beta=2.0):
+        """winding_number(points, beta) > 0.5."""
+        return self.winding_number(points, beta) > 0.5
 
     def sample_lights(self, origins, seed=1):
         origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libprt_hip.so")
 DEV_LIB = os.path.join(HERE, "libprt_hip_dev.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["prt_api.cpp", "prt_kernels.hip", "prt_kernels_f32.hip", "bvh_build.cpp", "bvh_build_gpu.hip", "bvh_refit.hip", "light_tables.hip", "ray_sort.hip", "scene_setup.cpp", "prt_denoise.hip", "closest_point.hip", "pseudonormals.hip", "mesh_topology.cpp", "multi_hit.hip", "multi_hit_f32.hip"]
+SOURCES = ["prt_api.cpp", "prt_kernels.hip", "prt_kernels_f32.hip", "bvh_build.cpp", "bvh_build_gpu.hip", "bvh_refit.hip", "light_tables.hip", "ray_sort.hip", "scene_setup.cpp", "prt_denoise.hip", "closest_point.hip", "pseudonormals.hip", "winding_number.hip", "mesh_topology.cpp", "multi_hit.hip", "multi_hit_f32.hip"]
 HEADERS = ["prt_types.h", "prt_device.h", "prt_light_pick.h", "prt_host.h", "prt_launch.h", "mesh_topology.h", os.path.join("..", "..", "include", "prt.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-gpu-rdc"]

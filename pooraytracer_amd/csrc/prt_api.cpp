@@ -224,6 +224,12 @@ struct PrtScene {
     bool signed_queries = false; // survives upload / update_vertices
     prt::DSignedTables sq;
     size_t signed_bytes = 0;
+    // prt_scene_set_winding_queries: while it is on (distance queries are then on too), an uploaded scene also keeps the
+    // moments of winding_number.hip, four 64-byte records per node of k64.d.nodes (owned by `allocs`).  They belong to the
+    // tree and the corners: upload and switch-on make them, a refit refreshes them behind its boxes, a rebuild makes the new
+    // tree's in an array of its own.
+    bool winding_queries = false; // survives upload / update_vertices
+    prt::DWindingMoment* d_moments = nullptr;
     struct LightUpdate {
         double* d_gather = nullptr;    // per light triangle, resident CDF order: 9 doubles of new vertices, then (second half) of vertex normals
         std::vector<double> h_gather;  // ... read back with the refit's decision
@@ -413,6 +419,7 @@ struct PrtScene {
         d_corners = nullptr;
         sq = prt::DSignedTables();
         signed_bytes = 0;
+        d_moments = nullptr;
         refit = Refit();
         light_res = light_spare = LightArrays();
         lu = LightUpdate();
@@ -928,6 +935,33 @@ static void signed_free(PrtScene* s) {
     s->signed_bytes = 0;
 }
 
+// The moments table of a scene that answers winding-number queries (prt_scene_set_winding_queries), from the resident tree
+// and corner table, on the null stream, synchronous.  The scene is uploaded, its device is current, it has its corner table
+// and no moments table.  The refit's parent array and counters exist only after a first refit: this pass makes its own and
+// frees them when it returns.  All or nothing.
+static int winding_from_resident(PrtScene* s, const std::string& who) {
+    const DScene& d = s->k64.d;
+    const size_t nn = d.n_nodes;
+    DevBuf<> table, parent, cnt;
+    PRT_HIP_AS(who, dev_alloc(table, std::max<size_t>(nn * 4 * sizeof(prt::DWindingMoment), 256)));
+    PRT_HIP_AS(who, dev_alloc(parent, std::max<size_t>(nn * sizeof(uint32_t), 256)));
+    PRT_HIP_AS(who, dev_alloc(cnt, std::max<size_t>((nn * sizeof(uint32_t) + 15) & ~(size_t)15, 256)));
+    PRT_HIP_AS(who, s->after_refit(nullptr));
+    if (nn) prt::launch_refit_parents(d.nodes, d.n_nodes, static_cast<uint32_t*>(parent.get()), nullptr);
+    PRT_HIP_AS(who, prt::launch_winding_moments(d.nodes, d.n_nodes, static_cast<const uint32_t*>(parent.get()), static_cast<uint32_t*>(cnt.get()),
+                                                s->d_corners, d.n_tris, static_cast<prt::DWindingMoment*>(table.get()), nullptr));
+    PRT_HIP_AS(who, hipGetLastError());
+    PRT_HIP_AS(who, hipDeviceSynchronize());
+    try {
+        s->allocs.reserve(s->allocs.size() + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_E_OOM, who + ": out of host memory");
+    }
+    s->d_moments = static_cast<prt::DWindingMoment*>(table.get());
+    s->allocs.push_back(std::move(table));
+    return PRT_OK;
+}
+
 // Either the whole scene is resident afterwards, or nothing is: a failure anywhere (allocation, copy, device build)
 // releases what was uploaded so far and leaves the scene in the not-uploaded state (device = -1), so that no later
 // call can launch a kernel on a half-filled DScene.
@@ -1160,6 +1194,7 @@ static int upload_impl(PrtScene* s, int device) {
     s->blocks_wanted = size_kernels(s, s->k64, true);
     if (s->distance_queries && (rc = corners_from_host(s, "prt_scene_upload"))) return rc;
     if (s->signed_queries && (rc = signed_from_host(s, "prt_scene_upload"))) return rc;
+    if (s->winding_queries && (rc = winding_from_resident(s, "prt_scene_upload"))) return rc;
     return PRT_OK;
 }
 
@@ -1705,6 +1740,15 @@ static void launch_position_followers(PrtScene* s, const double* d_verts, const 
     }
 }
 
+// What follows the TREE as well as the positions, on `st` behind the corner gather, the boxes and the parents of the resident
+// topology: the moments of the winding-number queries, with the refit's parent array and counters.  For the refit and the
+// rebuild alike.
+static hipError_t launch_tree_followers(PrtScene* s, hipStream_t st) {
+    const DScene& d = s->k64.d;
+    if (!s->d_moments || !s->d_corners) return hipSuccess;
+    return prt::launch_winding_moments(d.nodes, d.n_nodes, s->refit.d_parent, s->refit.d_cnt, s->d_corners, d.n_tris, s->d_moments, st);
+}
+
 // d_verts / d_normals: device arrays [n_tris][3][xyz].  The scene is uploaded and its device is current.
 static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts, const double* d_normals, hipStream_t st) {
     DScene& d = s->k64.d;
@@ -1729,6 +1773,7 @@ static int refit_impl(PrtScene* s, const std::string& who, const double* d_verts
     if (s->d_nodes_shallow)
         PRT_HIP_AS(who, prt::launch_refit_boxes(const_cast<DNode*>(s->d_nodes_shallow), s->n_nodes_shallow, R.d_parent_sh, R.d_cnt_sh,
                                                 R.d_tbox, n, step, st));
+    PRT_HIP_AS(who, launch_tree_followers(s, st)); // (boxes_ms includes them)
     prt::launch_refit_sah(d.nodes, d.n_nodes, origin, step, R.d_scratch, R.d_sah + 1, st);
     PRT_HIP_AS(who, hipGetLastError());
     PRT_HIP_AS(who, hipEventRecord(R.ev2.get(), st));
@@ -1757,7 +1802,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
         PRT_HIP_AS(who, dev_alloc(out, std::max<size_t>(bytes, 256)));
         return PRT_OK;
     };
-    DevBuf<> boxes, nodes, order, shade, inv, parent, cnt;
+    DevBuf<> boxes, nodes, order, shade, inv, parent, cnt, moments;
     int rc;
     if ((rc = alloc((size_t)n * sizeof(prt::PrimBox), boxes))) return rc;
     prt::launch_prim_boxes(d_verts, n, static_cast<float*>(boxes.get()), g.origin_d, g.delta, st);
@@ -1774,6 +1819,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     if ((rc = alloc((size_t)n * sizeof(DTriShade), shade)) || (rc = alloc((size_t)n * sizeof(uint32_t), inv)) ||
         (rc = alloc((size_t)db.n_nodes * sizeof(uint32_t), parent)) || (rc = alloc(round16((size_t)db.n_nodes * sizeof(uint32_t)), cnt)))
         return rc;
+    if (s->d_moments && (rc = alloc((size_t)db.n_nodes * 4 * sizeof(prt::DWindingMoment), moments))) return rc; // winding queries: the new tree's table
     int need = PRT_STACK_DEPTH; // as at upload
     try {
         PRT_HIP_AS(who, device_tree_stack_need(db.d_nodes, db.n_nodes, &need));
@@ -1787,8 +1833,9 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     refit_commit_grid(s, db.grid_origin, db.grid_step, db.coord_scale);
     const DTriShade* const shade_old = d.shade;
     const uint32_t* const order_old = s->d_order;
-    DevBuf<> old[8] = {s->take(d.nodes),  s->take(s->d_order),        s->take(d.shade),      s->take(R.d_parent),
-                       s->take(R.d_cnt),  s->take(s->d_nodes_shallow), s->take(R.d_parent_sh), s->take(R.d_cnt_sh)};
+    DevBuf<> old[9] = {s->take(d.nodes),  s->take(s->d_order),        s->take(d.shade),      s->take(R.d_parent),
+                       s->take(R.d_cnt),  s->take(s->d_nodes_shallow), s->take(R.d_parent_sh), s->take(R.d_cnt_sh),
+                       s->take(moments ? s->d_moments : nullptr)};
     s->adopt_device_tree(db); // (nodes and order)
     d.shade = static_cast<const DTriShade*>(shade.get());
     R.d_parent = static_cast<uint32_t*>(parent.get());
@@ -1796,7 +1843,9 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     R.d_parent_sh = R.d_cnt_sh = nullptr; // a device-built tree has no 32-entry collapse
     s->d_nodes_shallow = nullptr;
     s->n_nodes_shallow = 0;
-    for (DevBuf<>* b : {&nodes, &order, &shade, &parent, &cnt}) s->allocs.push_back(std::move(*b)); // (room for more than `old` took out)
+    if (moments) s->d_moments = static_cast<prt::DWindingMoment*>(moments.get());
+    for (DevBuf<>* b : {&nodes, &order, &shade, &parent, &cnt, &moments})
+        if (*b) s->allocs.push_back(std::move(*b)); // (room for more than `old` took out)
     s->device_bvh = true; // a later upload builds on the device as well: the host tree is not this one
     s->set_stack_need(need);
     if (s->f32_ready) {
@@ -1809,6 +1858,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
     launch_position_followers(s, d_verts, d_normals, g, st);
     // the refit state of the new topology
     PRT_HIP_AS(who, refit_baseline(s, st));
+    PRT_HIP_AS(who, launch_tree_followers(s, st));
     PRT_HIP_AS(who, hipGetLastError());
     PRT_HIP_AS(who, hipEventRecord(R.done.get(), st));
     PRT_HIP_AS(who, hipStreamSynchronize(st)); // synchronous: the new tree is resident, what it replaced can go
@@ -1946,6 +1996,9 @@ int prt_scene_set_distance_queries(PrtScene* s, int on) {
     if (!want && s->signed_queries)
         return fail(PRT_E_INVALID, std::string(who) + ": signed distance queries are on and need the corner table "
                                                       "(call prt_scene_set_signed_queries(scene, 0) first)");
+    if (!want && s->winding_queries)
+        return fail(PRT_E_INVALID, std::string(who) + ": winding-number queries are on and need the corner table "
+                                                      "(call prt_scene_set_winding_queries(scene, 0) first)");
     if (s->device < 0) { // not uploaded: the next upload makes the table
         s->distance_queries = want;
         return PRT_OK;
@@ -1968,6 +2021,23 @@ int prt_scene_get_distance_queries(const PrtScene* s, int* on) {
     return PRT_OK;
 }
 
+// A switch whose tables need the corner table goes on for an uploaded scene: the corners first, where distance queries
+// are off, then `make` (signed_from_host, winding_from_resident); a failure leaves the corner table as it was.
+static int tables_beside_corners(PrtScene* s, const char* who, int (*make)(PrtScene*, const std::string&)) {
+    const bool had_corners = s->distance_queries;
+    if (!had_corners)
+        if (const int rc = corners_from_host(s, who)) return rc;
+    if (const int rc = make(s, who)) {
+        if (!had_corners) { // both switches as they were
+            s->take(s->d_corners).reset();
+            s->d_corners = nullptr;
+        }
+        return rc;
+    }
+    s->distance_queries = true;
+    return PRT_OK;
+}
+
 int prt_scene_set_signed_queries(PrtScene* s, int on) {
     const char* who = "prt_scene_set_signed_queries";
     if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
@@ -1980,21 +2050,55 @@ int prt_scene_set_signed_queries(PrtScene* s, int on) {
     }
     if (const int rc = query_switch_ready(s, who, want, "signed queries")) return rc;
     if (want) {
-        const bool had_corners = s->distance_queries;
-        if (!had_corners)
-            if (const int rc = corners_from_host(s, who)) return rc;
-        if (const int rc = signed_from_host(s, who)) {
-            if (!had_corners) { // both switches as they were
-                s->take(s->d_corners).reset();
-                s->d_corners = nullptr;
-            }
-            return rc;
-        }
-        s->distance_queries = s->signed_queries = true;
+        if (const int rc = tables_beside_corners(s, who, signed_from_host)) return rc;
+        s->signed_queries = true;
         return PRT_OK;
     }
     signed_free(s);
     s->signed_queries = false;
+    return PRT_OK;
+}
+
+int prt_scene_set_winding_queries(PrtScene* s, int on) {
+    const char* who = "prt_scene_set_winding_queries";
+    if (!s) return fail(PRT_E_INVALID, std::string(who) + ": null scene");
+    const bool want = on != 0;
+    if (want == s->winding_queries) return PRT_OK;
+    if (s->device < 0) { // not uploaded: the next upload makes the table
+        s->winding_queries = want;
+        if (want) s->distance_queries = true;
+        return PRT_OK;
+    }
+    if (const int rc = query_switch_ready(s, who, want, "winding queries")) return rc;
+    if (want) {
+        if (const int rc = tables_beside_corners(s, who, winding_from_resident)) return rc;
+        s->winding_queries = true;
+        return PRT_OK;
+    }
+    s->take(s->d_moments).reset(); // (distance queries stay on)
+    s->d_moments = nullptr;
+    s->winding_queries = false;
+    return PRT_OK;
+}
+
+int prt_scene_get_winding_queries(const PrtScene* s, int* on) {
+    if (!s || !on) return fail(PRT_E_INVALID, "prt_scene_get_winding_queries: null argument");
+    *on = s->winding_queries ? 1 : 0;
+    return PRT_OK;
+}
+
+int prt_scene_winding_moments(PrtScene* s, double* out, uint64_t cap_nodes, uint64_t* n) {
+    static_assert(sizeof(prt::DWindingMoment) == 8 * sizeof(double), "the hook copies the records as they are");
+    const char* who = "prt_scene_winding_moments";
+    if (!s || !n || (!out && cap_nodes)) return fail(PRT_E_INVALID, std::string(who) + ": null argument");
+    if (!s->winding_queries)
+        return fail(PRT_E_INVALID, std::string(who) + ": winding-number queries are off for this scene (prt_scene_set_winding_queries)");
+    if (const int rc = require_uploaded(s, who)) return rc;
+    *n = s->k64.d.n_nodes;
+    const size_t m = (size_t)std::min<uint64_t>(*n, cap_nodes);
+    if (m == 0 || !s->d_moments) return PRT_OK;
+    PRT_HIP_AS(who, hipDeviceSynchronize()); // a refit on any stream has written its moments
+    PRT_HIP_AS(who, hipMemcpy(out, s->d_moments, m * 4 * sizeof(prt::DWindingMoment), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -2191,6 +2295,48 @@ int prt_signed_distance(PrtScene* s, const PrtPointQuery* qs, size_t n, PrtSigne
     if (n == 0) return PRT_OK;
     return batch_host(who, qs, n * sizeof(PrtPointQuery), nullptr, 0, out, n * sizeof(PrtSignedDistance),
                       [&](void* dq, void*, void* dout) { return prt_signed_distance_device(s, dq, n, dout, count_work, nullptr); });
+}
+
+static int refuse_winding(const PrtScene* s, const std::string& w, double beta) {
+    if (!s->winding_queries || (s->device >= 0 && (!s->d_corners || !s->d_moments)))
+        return fail(PRT_E_INVALID, w + ": winding-number queries are off for this scene (prt_scene_set_winding_queries)");
+    if (!(beta > 1.0)) return fail(PRT_E_INVALID, w + ": beta must be greater than 1 (PRT_WINDING_BETA_DEFAULT is 2; +inf sums every triangle)");
+    return PRT_OK;
+}
+
+int prt_winding_number_device(PrtScene* s, const void* d_q, size_t n, double beta, void* d_out, int count_work, void* stream) {
+    if (!s) return fail(PRT_E_INVALID, "prt_winding_number_device: null scene");
+    if (const int rc = refuse_winding(s, "prt_winding_number_device", beta)) return rc; // (before the missing device)
+    return batch_device(
+        s, "prt_winding_number_device", nullptr, n, count_work, PRT_PRECISION_F64, stream, false,
+        [&](const std::string& w) {
+            if (n && (!d_q || !d_out)) return fail(PRT_E_INVALID, w + ": null buffer");
+            if (n > 0xffffffffull) return fail(PRT_E_INVALID, w + ": more than 2^32 - 1 queries in one batch");
+            if (reinterpret_cast<uintptr_t>(d_out) & 7u) // the kernel stores one double per query
+                return fail(PRT_E_INVALID, w + ": output buffer is not 8-byte aligned");
+            return PRT_OK;
+        },
+        [&](bool, DCounters* d_ctr, bool count, const uint32_t*, hipStream_t st) {
+            return prt::launch_winding_number(s->k64.d, s->d_corners, s->d_moments, static_cast<const PrtPointQuery*>(d_q), n, beta,
+                                              static_cast<double*>(d_out), d_ctr, count, s->stack_need, s->n_cu, st);
+        });
+}
+
+int prt_winding_number(PrtScene* s, const PrtPointQuery* qs, size_t n, double beta, double* out, int count_work) {
+    const char* who = "prt_winding_number";
+    if (!s) return fail(PRT_E_INVALID, "prt_winding_number: null scene");
+    if (const int rc = refuse_winding(s, who, beta)) return rc;
+    if (n && (!qs || !out)) return fail(PRT_E_INVALID, "prt_winding_number: null buffer");
+    if (n > 0xffffffffull) return fail(PRT_E_INVALID, "prt_winding_number: more than 2^32 - 1 queries in one batch");
+    for (size_t i = 0; i < n; ++i) { // (max_dist is not read)
+        const PrtPointQuery& q = qs[i];
+        if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2])))
+            return fail(PRT_E_INVALID, "prt_winding_number: query " + std::to_string(i) + " has a non-finite point");
+    }
+    if (const int rc = require_uploaded(s, who)) return rc;
+    if (n == 0) return PRT_OK;
+    return batch_host(who, qs, n * sizeof(PrtPointQuery), nullptr, 0, out, n * sizeof(double),
+                      [&](void* dq, void*, void* dout) { return prt_winding_number_device(s, dq, n, beta, dout, count_work, nullptr); });
 }
 
 int prt_scene_light_update_info(const PrtScene* s, PrtLightUpdateInfo* out) {

@@ -114,6 +114,20 @@ struct DSignedTables {
     uint32_t n_tris = 0, n_vertices = 0, n_edges = 0;
 };
 void launch_pseudonormals(const DTriCorners* d_corners, const DSignedTables& T, hipStream_t st);
+// winding_number.hip: the moments table of a scene that answers winding-number queries ([n_nodes][4], one record per child
+// slot, zeros for an unused slot; include/prt.h has the formulas), its bottom-up refresh with the refit's parent array and
+// counters, and K8
+struct alignas(64) DWindingMoment {
+    double N[3]; // the sum of the area vectors below the slot
+    double c[3]; // the area-weighted centroid
+    double r;    // every corner below the slot lies within r of c
+    double A;    // the area
+};
+hipError_t launch_winding_moments(const DNode* d_nodes, uint32_t n_nodes, const uint32_t* d_parent, uint32_t* d_cnt,
+                                  const DTriCorners* d_corners, uint32_t n_tris, DWindingMoment* d_mom, hipStream_t st);
+hipError_t launch_winding_number(const DSceneT<double>& S, const DTriCorners* d_corners, const DWindingMoment* d_mom, const PrtPointQuery* d_q,
+                                 size_t n, double beta, double* d_out, DCounters* d_ctr, bool count, int stack_depth, int n_cu,
+                                 hipStream_t st);
 // K7 (multi_hit.hip / multi_hit_f32.hip): one batch of rays, k records per ray into d_out (32-byte aligned), d_after null
 // or one cursor per ray, d_perm K4's order or null
 hipError_t launch_multi_hit(const DSceneT<double>& S, const PrtRay* d_rays, const PrtHitCursor* d_after, size_t n, int k, PrtHit* d_out,

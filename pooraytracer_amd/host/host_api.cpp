@@ -272,6 +272,20 @@ std::vector<bool> Hittable::SignedDistance(const std::vector<point3>& p, double 
     return found;
 }
 
+std::vector<double> Hittable::WindingNumber(const std::vector<point3>& p, double beta) const {
+    DeviceCache& dc = Device();
+    dc.Ensure(*this, dc.device < 0 ? 0 : dc.device);
+    check(prt_scene_set_winding_queries(dc.scene, 1), "prt_scene_set_winding_queries"); // (nothing to do when it is on already)
+    std::vector<PrtPointQuery> q(p.size());
+    for (size_t i = 0; i < p.size(); ++i) {
+        q[i].p[0] = p[i].x; q[i].p[1] = p[i].y; q[i].p[2] = p[i].z;
+        q[i].max_dist = 0.0; // (not read)
+    }
+    std::vector<double> w(p.size());
+    check(prt_winding_number(dc.scene, q.data(), q.size(), beta, w.data(), 0), "prt_winding_number");
+    return w;
+}
+
 bool Hittable::ClosestPoint(const point3& p, double maxDist, point3& closest, double& distance) const {
     std::vector<point3> c;
     std::vector<double> d;
