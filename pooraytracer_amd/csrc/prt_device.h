@@ -811,7 +811,15 @@ PRT_DEV real ct_D(const DMaterial& m, d3 wm) {
     if (isinf(t2)) return 0;
     real cos4 = sqr(cos2theta(wm));
     real e = t2 * (sqr(cosphi(wm) / m.alpha_x) + sqr(sinphi(wm) / m.alpha_y));
-    return 1 / (PRT_PI * m.alpha_x * m.alpha_y * cos4 * sqr(1 + e));
+    // Grazing micro-normals (mat_eval's wm = normalize(wi + wo) of a light and an eye that both graze the surface;
+    // ct_sample_wm keeps wm.z >= 1e-6 and never comes here): below wm.z ~ 2e-10 / alpha (fp32; ~1e-77 / alpha in fp64)
+    // sqr(1 + e) overflows while tan2theta is still finite, the product is inf and D = 0 — the value the isinf branch above
+    // returns a little further out; the exact D tends to ~alpha^2 / pi there, so D is an underestimate by then, not an
+    // error a frame could show.  Below wm.z ~ 1e-11 (fp32; 1e-81 in fp64) cos4 has underflowed to 0 as well and the product
+    // is 0 * inf: that NaN — and only it, every finite result is as it was — becomes the same 0.
+    // tests/test_gpu_device_math.py (ct_D, ct_Dv, mat_eval on the grazing strata) holds it.
+    const real D = 1 / (PRT_PI * m.alpha_x * m.alpha_y * cos4 * sqr(1 + e));
+    return D == D ? D : 0;
 }
 PRT_DEV real ct_lambda(const DMaterial& m, d3 w) {
     real t2 = tan2theta(w);

@@ -99,6 +99,91 @@ PROBE_REAL(disk_concentric, 2, 2, const d2 p = disk_concentric(d2{a[0], a[1]}); 
 PROBE_REAL(ct_sample_wm, 7, 3, DMaterial m = {}; m.alpha_x = a[0]; m.alpha_y = a[1];
            const d3 wm = ct_sample_wm(m, mk3(a[2], a[3], a[4]), d2{a[5], a[6]}); o[0] = wm.x; o[1] = wm.y; o[2] = wm.z;)
 
+// ------------------------------------------------------------------ the BSDF layer: CookTorrance terms
+PROBE_REAL(tan2theta, 3, 1, o[0] = tan2theta(mk3(a[0], a[1], a[2]));)
+PROBE_REAL(cosphi, 3, 1, o[0] = cosphi(mk3(a[0], a[1], a[2]));)
+PROBE_REAL(sinphi, 3, 1, o[0] = sinphi(mk3(a[0], a[1], a[2]));)
+// alpha_x, alpha_y, then the directions
+#define PROBE_ALPHA DMaterial m = {}; m.alpha_x = a[0]; m.alpha_y = a[1];
+PROBE_REAL(ct_D, 5, 1, PROBE_ALPHA o[0] = ct_D(m, mk3(a[2], a[3], a[4]));)
+PROBE_REAL(ct_lambda, 5, 1, PROBE_ALPHA o[0] = ct_lambda(m, mk3(a[2], a[3], a[4]));)
+PROBE_REAL(ct_G1, 5, 1, PROBE_ALPHA o[0] = ct_G1(m, mk3(a[2], a[3], a[4]));)
+PROBE_REAL(ct_G, 8, 1, PROBE_ALPHA o[0] = ct_G(m, mk3(a[2], a[3], a[4]), mk3(a[5], a[6], a[7]));)  // wo, wi
+PROBE_REAL(ct_Dv, 8, 1, PROBE_ALPHA o[0] = ct_Dv(m, mk3(a[2], a[3], a[4]), mk3(a[5], a[6], a[7]));) // w, wm
+// eta[3], k[3], wo, wm -> F per channel
+PROBE_REAL(ct_fresnel, 12, 3, DMaterial m = {}; for (int c = 0; c < 3; ++c) m.eta[c] = a[c], m.k[c] = a[3 + c];
+           const d3 F = ct_fresnel(m, mk3(a[6], a[7], a[8]), mk3(a[9], a[10], a[11])); o[0] = F.x; o[1] = F.y; o[2] = F.z;)
+
+// ------------------------------------------------------------------ the BSDF layer: Material::Eval and Material::Scatter
+// An untextured material from its RAW fields, 17 reals: type, kd[3], ks[3], ns, eta[3], k[3], alpha_x, alpha_y, pkd.  The
+// derived fields are filled as scene_setup.cpp:setup_materials fills them — in double, from the double ns — and then rounded
+// to `real` as prt_api.cpp makes the fp32 material table.  pkd >= 0 overrides the lobe probabilities (pkd, 1 - pkd): 0 and 1
+// force a lobe; a negative value keeps SetProbabilitiesByNs' 1 / 0 or 0.6 / 0.4.
+#define PROBE_MAT_NI 17
+namespace {
+__device__ __forceinline__ DMaterial probe_material(const real* a) {
+    DMaterial m = {};
+    m.type = (int32_t)a[0];
+    m.texture = -1;
+    for (int c = 0; c < 3; ++c) m.kd[c] = a[1 + c], m.ks[c] = a[4 + c], m.eta[c] = a[8 + c], m.k[c] = a[11 + c];
+    const double ns = (double)a[7];
+    m.ns = a[7];
+    m.inv_ns1 = (real)(1.0 / (ns + 1.0));
+    m.spec_scale = (real)((ns + 2.0) / (ns + 1.0));
+    m.pkd = (real)(ns <= 9. ? 1.0 : 0.6);
+    m.pks = (real)(ns <= 9. ? 0.0 : 0.4);
+    if (a[16] >= 0) m.pkd = a[16], m.pks = RL(1.) - a[16];
+    m.alpha_x = a[14];
+    m.alpha_y = a[15];
+    return m;
+}
+// The all-zero state is xoroshiro's fixed point (every draw 0, and the sampling loops `while (wi.z <= 0)` would never end);
+// Rng::seed_keyed never produces it, and this replaces it the same way.
+__device__ __forceinline__ uint64_t probe_state(uint64_t s) { return s ? s : 0x9E3779B97F4A7C15ULL; }
+} // namespace
+// in[i] = material (17), wi.xyz, wo.xyz (local frame, z the shading normal); state[i]; out[i] = f.xyz; state_out[i]
+extern "C" int PROBE_SYM(mat_eval)(const void* in_, const void* state_, void* out_, void* state_out_, size_t n, hipStream_t stream) {
+    const real* in = static_cast<const real*>(in_);
+    const uint64_t* state = static_cast<const uint64_t*>(state_);
+    real* out = static_cast<real*>(out_);
+    uint64_t* state_out = static_cast<uint64_t*>(state_out_);
+    return launch_each(n, stream, [=] __device__(size_t i) {
+        const real* a = in + i * (PROBE_MAT_NI + 6);
+        const DMaterial m = probe_material(a);
+        DScene S = {};
+        Rng g;
+        g.s = probe_state(state[i]);
+        const d3 f = mat_eval<PRT_FEAT_PHONG | PRT_FEAT_CT>(S, m, mk3(a[17], a[18], a[19]), mk3(a[20], a[21], a[22]), d2{RL(0.), RL(0.)}, g);
+        out[i * 3] = f.x, out[i * 3 + 1] = f.y, out[i * 3 + 2] = f.z;
+        state_out[i] = g.s;
+    });
+}
+// in[i] = material (17), rd.xyz, frame normal.xyz, frame tangent.xyz; out[i] = ok, wi_world.xyz, att.xyz (zeros where the
+// function leaves them unassigned)
+extern "C" int PROBE_SYM(mat_scatter)(const void* in_, const void* state_, void* out_, void* state_out_, size_t n, hipStream_t stream) {
+    const real* in = static_cast<const real*>(in_);
+    const uint64_t* state = static_cast<const uint64_t*>(state_);
+    real* out = static_cast<real*>(out_);
+    uint64_t* state_out = static_cast<uint64_t*>(state_out_);
+    return launch_each(n, stream, [=] __device__(size_t i) {
+        const real* a = in + i * (PROBE_MAT_NI + 9);
+        const DMaterial m = probe_material(a);
+        DScene S = {};
+        Rng g;
+        g.s = probe_state(state[i]);
+        Frame f;
+        f.n = mk3(a[20], a[21], a[22]);
+        f.t = mk3(a[23], a[24], a[25]);
+        d3 att = mk3(0, 0, 0), wi = mk3(0, 0, 0);
+        const bool ok = mat_scatter<PRT_FEAT_PHONG | PRT_FEAT_CT>(S, m, mk3(a[17], a[18], a[19]), f, d2{RL(0.), RL(0.)}, g, att, wi);
+        real* o = out + i * 7;
+        o[0] = ok ? RL(1.) : RL(0.);
+        o[1] = wi.x, o[2] = wi.y, o[3] = wi.z;
+        o[4] = att.x, o[5] = att.y, o[6] = att.z;
+        state_out[i] = g.s;
+    });
+}
+
 // ------------------------------------------------------------------ RNG (raw 64-bit states in, reals out)
 #define PROBE_RNG_DRAWS 4
 extern "C" int PROBE_SYM(rng_next)(const void* in_, void* out_, size_t n, hipStream_t stream) {
@@ -164,6 +249,9 @@ extern "C" int PROBE_SYM(box4)(const void* ray_, const void* grid_, const void* 
 }
 
 #if PRT_PROBE_F32
+// the two instructions of the fp32 pow_pos on their own (base 2), for the CPU-side recheck against longdouble
+PROBE_REAL(v_log, 1, 1, o[0] = __builtin_amdgcn_logf(a[0]);)
+PROBE_REAL(v_exp, 1, 1, o[0] = __builtin_amdgcn_exp2f(a[0]);)
 // ------------------------------------------------------------------ exhaustive fp32 checks (reduced on the device)
 // Float bit patterns first .. first + count - 1 go through op OP; each result is compared with the correctly rounded
 // fp64 operation rounded to float (1 / sqrt: an fp64 sqrt and an fp64 division, so two fp64 roundings before the one to
@@ -181,7 +269,9 @@ __device__ __forceinline__ float x_op(float x) {
     case 3: return fast_rcp(x);
     case 4: return fast_rsqrt(x);
     case 5: return fast_sqrt(x);
-    default: return ieee_sqrt(x);
+    case 6: return ieee_sqrt(x);
+    case 7: return __builtin_amdgcn_logf(x);  // v_log_f32: log2
+    default: return __builtin_amdgcn_exp2f(x); // v_exp_f32: 2^x
     }
 }
 template <int OP>
@@ -190,6 +280,8 @@ __device__ __forceinline__ float x_ref(float x) {
     switch (OP) {
     case 0: case 3: return (float)(1.0 / d);
     case 1: case 4: return (float)(1.0 / sqrt(d));
+    case 7: return (float)log2(d);
+    case 8: return (float)exp2(d);
     default: return (float)sqrt(d);
     }
 }
@@ -237,7 +329,8 @@ int launch_exhaust(uint32_t first, unsigned long long count, unsigned long long*
 }
 } // namespace
 // op: 0 v_rcp_f32, 1 v_rsq_f32, 2 v_sqrt_f32 (the raw instructions), 3 fast_rcp, 4 fast_rsqrt, 5 fast_sqrt, 6 ieee_sqrt
-// (the fp32 overloads of prt_device.h).  `res`: four zeroed 64-bit words on the device.
+// (the fp32 overloads of prt_device.h), 7 v_log_f32, 8 v_exp_f32 (base 2: the two instructions of the fp32 pow_pos, against
+// the fp64 library log2 / exp2 rounded to float).  `res`: four zeroed 64-bit words on the device.
 extern "C" int prtprobe_exhaust_f32(int op, uint32_t first, unsigned long long count, void* res_, hipStream_t stream) {
     unsigned long long* res = static_cast<unsigned long long*>(res_);
     switch (op) {
@@ -248,6 +341,8 @@ extern "C" int prtprobe_exhaust_f32(int op, uint32_t first, unsigned long long c
     case 4: return launch_exhaust<4>(first, count, res, stream);
     case 5: return launch_exhaust<5>(first, count, res, stream);
     case 6: return launch_exhaust<6>(first, count, res, stream);
+    case 7: return launch_exhaust<7>(first, count, res, stream);
+    case 8: return launch_exhaust<8>(first, count, res, stream);
     default: return -1;
     }
 }
