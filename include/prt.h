@@ -61,7 +61,7 @@ extern "C" {
 #define PRT_E_NO_DEVICE (-2)  /* no HIP device visible */
 #define PRT_E_HIP (-3)        /* a HIP runtime call failed (message has the HIP error string) */
 #define PRT_E_OOM (-4)        /* host or device allocation failed */
-#define PRT_E_LIMIT (-5)      /* scene exceeds a compiled-in limit (BVH depth, leaf encoding) */
+#define PRT_E_LIMIT (-5)      /* scene exceeds a compiled-in limit (BVH depth, leaf encoding, 2^26 BVH nodes) */
 
 /* Material kinds — reference enum MaterialType, Source/Material.h:48-51 */
 #define PRT_MAT_LAMBERTIAN 0    /* Source/Material.h:101-155 */

@@ -241,6 +241,15 @@ void quant_grid(const float root_lo[3], const float root_hi[3], bool empty, floa
     }
 }
 
+// The traversal reaches a node by a 32-bit byte offset from the tree's base (Trav::inner_step: index << 6), so a tree of
+// either builder may have PRT_MAX_NODES nodes at most.  No scene the builders have seen comes near (3.8M nodes for 8M
+// triangles); a larger tree is refused where it is made, before anything of it is traversed.
+bool node_count_ok(size_t n_nodes, std::string* err) {
+    if (n_nodes <= (size_t)PRT_MAX_NODES) return true;
+    if (err) *err = "the BVH has " + std::to_string(n_nodes) + " nodes, more than the 2^26 (67108864) a traversal can address";
+    return false;
+}
+
 // Structural check of a flattened tree (either builder, either width): every reference in range, every triangle
 // in exactly one leaf, no traversal able to need more than PRT_STACK_DEPTH stack entries.  Used on device-built
 // trees when PRT_VALIDATE_BVH is set (tests): a bad node index would be a GPU memory fault, not a wrong pixel.
@@ -250,6 +259,7 @@ bool validate_nodes(const DNode* nodes, size_t n_nodes, size_t n_tris, std::stri
         return false;
     };
     if (n_nodes == 0) return bad("no nodes");
+    if (!node_count_ok(n_nodes, err)) return false;
     std::vector<uint8_t> seen(n_tris, 0);
     std::vector<int> need(n_nodes, -1);
     // iterative post-order over node indices (children may have any index in a device-built tree)
@@ -654,7 +664,8 @@ bool build_bvh(const std::vector<HostTri>& tris, BuiltBVH& out, std::string* err
     for (int a = 0; a < 3; ++a)
         gm = std::max(gm, std::fabs((float)(g0[a] + 65535.0 * gs[a])));
     out.coord_scale = std::nextafter(std::max(out.coord_scale, gm), std::numeric_limits<float>::infinity());
-    return true;
+    // (both collapses of the binary tree are traversed: the larger one decides)
+    return node_count_ok(std::max(out.nodes.size(), out.nodes_shallow.size()), err);
 }
 
 } // namespace prt

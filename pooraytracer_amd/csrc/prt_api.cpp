@@ -435,6 +435,17 @@ struct PrtScene {
     }
 };
 
+// A tree of `n_nodes` nodes may become a scene's: PRT_E_LIMIT beyond PRT_MAX_NODES (prt::node_count_ok).  Asked where a tree
+// is made, by either builder, before anything is allocated for it or traverses it.
+// Test hook PRT_TEST_CLAIM_NODES=<n> (dev-hooks build only): the tree in question claims n nodes, whatever it has — the limit
+// is tested without a tree of 4 GB.
+static int check_node_count(const std::string& who, size_t n_nodes) {
+    if (const char* e = dev_env("PRT_TEST_CLAIM_NODES")) n_nodes = (size_t)std::strtoull(e, nullptr, 10);
+    std::string err;
+    if (!prt::node_count_ok(n_nodes, &err)) return fail(PRT_E_LIMIT, who + ": " + err);
+    return PRT_OK;
+}
+
 // Test hook PRT_TEST_DUMP_BVH=<file> (dev-hooks build only): the traversal tree of a scene, as the kernels get it, for the
 // fp64 tree model of the tests (tests/bvh_model.py).  Little-endian: a 72-byte header
 //   u32 magic 'PBVH', u32 version 1, u64 n_tris, u64 n_nodes, u32 built_on_device, u32 depth, i32 stack_need, u32 node_bytes,
@@ -761,6 +772,12 @@ int prt_scene_create(const PrtSceneDesc* desc, PrtScene** out) {
                 delete s;
                 return fail(PRT_E_LIMIT, "prt_scene_create: " + err);
             }
+            // For the test hook only: build_bvh has just decided for the real tree (the larger of its two collapses), and a
+            // tree it let through passes here as well.  PRT_TEST_CLAIM_NODES makes this the CPU-side refusal the tests can reach.
+            if (const int rc = check_node_count("prt_scene_create", s->bvh.nodes.size())) {
+                delete s;
+                return rc;
+            }
             s->bvh_info.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     } catch (const std::bad_alloc&) {
@@ -1055,6 +1072,7 @@ static int upload_impl(PrtScene* s, int device) {
         if (!prt::build_bvh_device(pb.data(), box_origin, n, db, &err)) return fail(PRT_E_HIP, "prt_scene_upload: " + err);
         s->allocs.emplace_back(db.d_nodes);
         s->allocs.emplace_back(db.d_order); // the leaf order: the gather below, and prt_scene_refit later
+        if ((rc = check_node_count("prt_scene_upload", db.n_nodes))) return rc;
         if (dev_env("PRT_VALIDATE_BVH")) { // tests: check the device-built tree on the host before any ray visits it
             std::vector<DNode> hn(db.n_nodes);
             PRT_HIP(hipMemcpy(hn.data(), db.d_nodes, (size_t)db.n_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
@@ -1816,6 +1834,7 @@ static int rebuild_impl(PrtScene* s, const std::string& who, const double* d_ver
         nodes.reset(db.d_nodes);
         order.reset(db.d_order);
     }
+    if ((rc = check_node_count(who, db.n_nodes))) return rc;
     if ((rc = alloc((size_t)n * sizeof(DTriShade), shade)) || (rc = alloc((size_t)n * sizeof(uint32_t), inv)) ||
         (rc = alloc((size_t)db.n_nodes * sizeof(uint32_t), parent)) || (rc = alloc(round16((size_t)db.n_nodes * sizeof(uint32_t)), cnt)))
         return rc;

@@ -362,7 +362,9 @@ struct Trav {
     // the stack cannot overflow (bvh_build.cpp).
     template <bool COUNT>
     PRT_DEV void inner_step(const DScene& S, uint32_t* stk, WorkCount& wc) {
-        const uint4* np = reinterpret_cast<const uint4*>(S.nodes + cur);
+        // The node's byte offset in 32 bits, unsigned (n_nodes <= PRT_MAX_NODES, refused beyond at upload and rebuild): the
+        // four loads take the tree's base from scalar registers and no 64-bit address is formed per visit.
+        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(S.nodes) + ((uint32_t)cur << 6));
         const uint4 bx = np[0], by = np[1], bz = np[2], rf = np[3];
         if (COUNT) wc.nodes++;
         float n0, f0, n1, f1, n2, f2, n3, f3;
@@ -398,18 +400,15 @@ struct Trav {
         PRT_CE(k1, r1, k3, r3)
         PRT_CE(k1, r1, k2, r2)
 #undef PRT_CE
-        if (k3 != 0xffffffffu) {
-            stk[sp * 64] = r3;
-            sp++;
-        }
-        if (k2 != 0xffffffffu) {
-            stk[sp * 64] = r2;
-            sp++;
-        }
-        if (k1 != 0xffffffffu) {
-            stk[sp * 64] = r1;
-            sp++;
-        }
+        // After the sort the children that are hit are a prefix of k0..k3, so the new top of the stack is known before
+        // anything is pushed: one count, one address, and r3, r2, r1 go to fixed distances below it under their own
+        // conditions — the slots, in the far-to-near order, that three pushes with an increment each would fill.
+        const bool h1 = k1 != 0xffffffffu, h2 = k2 != 0xffffffffu, h3 = k3 != 0xffffffffu;
+        sp += (int32_t)h1 + (int32_t)h2 + (int32_t)h3;
+        uint32_t* const top = stk + sp * 64;
+        if (h3) top[-3 * 64] = r3;
+        if (h2) top[-2 * 64] = r2;
+        if (h1) top[-1 * 64] = r1;
         if (k0 != 0xffffffffu) {
             cur = (int32_t)r0;
         } else if (sp == 0) {

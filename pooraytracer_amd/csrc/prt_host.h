@@ -96,7 +96,9 @@ void setup_materials(const PrtSceneDesc& d, std::vector<DMaterial>& out);
 // Binned-SAH BVH2, depth-bounded to PRT_STACK_DEPTH, child boxes rounded outward to fp32.
 // Returns false (with *err set) if a compiled-in limit is exceeded.
 bool build_bvh(const std::vector<HostTri>& tris, BuiltBVH& out, std::string* err);
-// Structural check of a flattened tree (refs in range, every triangle in exactly one leaf, stack bound).
+// False (with *err set) for a tree of more than PRT_MAX_NODES nodes: the traversal's 32-bit node offset ends there.
+bool node_count_ok(size_t n_nodes, std::string* err);
+// Structural check of a flattened tree (node count, refs in range, every triangle in exactly one leaf, stack bound).
 bool validate_nodes(const DNode* nodes, size_t n_nodes, size_t n_tris, std::string* err);
 // Largest number of stack entries a traversal of this tree can need (<= PRT_STACK_DEPTH for a builder's tree).
 int tree_stack_need(const DNode* nodes, size_t n_nodes);

@@ -609,10 +609,10 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     // (Two blocks the pass uses at two places, as macros: as lambdas they changed the code of the two-pass permutations.)
     // A sample has ended: the item's next one is due (`next`: how it is marked), or the item's sum is written and the lane fetches
 #define END_OF_SAMPLE(next) do {                                                                                                                                          \
-        const d3 acc = PST_LD(S_ACC);                                                                                                                                     \
         s++;                                                                                                                                                              \
         if (s < s_end) state = (next);                                                                                                                                     \
         else {                                                                                                                                                            \
+            const d3 acc = PST_LD(S_ACC); /* read here, at the item's end: a sample that merely ends carries no copy of the sum */                                        \
             double* o = cold_args()->partial + (size_t)item * 3;                                                                                                          \
             o[0] = (double)acc.x; /* the partial sums are fp64 in either mode (K5 adds them in fp64) */                                                                   \
             o[1] = (double)acc.y;                                                                                                                                         \
@@ -725,6 +725,11 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 }
                 state = ST_NEW_SAMPLE; // two-pass: set up at the bottom of this pass, consumed by the next one; TURN: set up right below
             }
+            // WAVE_DIET: the lane's next ray is the continuation ray of a vertex already shaded.  Both places that find this out
+            // (a returned shadow ray at the top of the pass, a vertex without a light point below) only say so; the direction
+            // is taken once, where the traversal is set up, so tr.d has one assignment in the pass instead of a copy of all
+            // three components in every branch of the turnover block (six v_mov_b64 four times over, tools/isa_sections.py).
+            bool take_next = false;
             bool hit_ready = false; // TURN: the lane holds a closest hit to consume in this pass (else, in ST_CLOSEST, a ray to trace)
             if (TURN) {
                 // ---- ends that need no shading, then the turnover: a fresh sample's camera hit is consumed below, in this pass
@@ -737,7 +742,8 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                         TRACE_FLAG_AT(nee_v, PRT_TRACE_VISIBLE);
                     }
                     if (cont) {
-                        tr.d = next_d;
+                        if (WAVE_DIET) take_next = true;
+                        else tr.d = next_d;
                         state = ST_CLOSEST;
                     } else {
                         ended = true;
@@ -944,7 +950,8 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     end_sample = false;
                     state = ST_SHADOW;
                 } else if (!end_sample) {
-                    tr.d = next_d;
+                    if (WAVE_DIET) take_next = true;
+                    else tr.d = next_d;
                 }
             } else if (do_scatter) {
                 // ---- Russian roulette + Scatter, Camera.cpp:176-202
@@ -1065,6 +1072,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 // boxes beyond the light are culled from the start and traversal stops at the first accepted triangle.
                 const bool sh_ray = state == ST_SHADOW;
                 started = sh_ray ? 2 : 1;
+                if (WAVE_DIET && take_next) tr.d = next_d;
                 if (COUNT && ctr->ray_dump != nullptr) { // developer experiment: K3's own ray stream, for K1 to replay
                     const unsigned long long k = atomicAdd(&ctr->ray_dump_n, 1ULL);
                     if (k < ctr->ray_dump_cap) {

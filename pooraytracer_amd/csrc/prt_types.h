@@ -49,6 +49,9 @@ struct alignas(64) DNode {
     int32_t ref[4]; // >=0: inner node index; <0: leaf, ~ref = (first_tri << 3) | (count-1)
 };
 static_assert(sizeof(DNode) == 64, "DNode must be 64 bytes");
+// Nodes a resident tree may have: the traversal forms a node's byte offset, index << 6, in 32 bits (Trav::inner_step).
+// A scene whose tree is larger is refused where the tree is made (PRT_E_LIMIT); the 8M-triangle soup has 3.8M.
+#define PRT_MAX_NODES (1u << 26)
 
 // 96 bytes: the plane (n, D) for the interval test, then IsInterior as two edge functions.  With w = n/(n.n):
 //   alpha = w . ((p - v0) x e1) = (p - v0) . (e1 x w) = p . A - a0,   A = e1 x w, a0 = v0 . A

@@ -2,7 +2,7 @@
 """Vector-instruction counts of one k_render instantiation, section by section (offline: hipcc cross-compiles, no GPU).
 
     python tools/isa_sections.py                       # k_render<false, 0, true, false>, the headline kernel
-    python tools/isa_sections.py "k_render<false, 4, true, false>" [-DPRT_X=1 ...] [--json] [--list] [--show=SECTION]
+    python tools/isa_sections.py "k_render<false, 4, true, false>" [-DPRT_X=1 ...] [--json] [--list] [--show=SECTION] [--opcodes]
     python tools/isa_sections.py --csrc=DIR [--asm=FILE]   # another checkout's csrc/ (and an assembly already made from it)
 
 The kernel file is compiled to assembly with line tables (-gline-tables-only: the instruction stream is the product's, each
@@ -23,8 +23,10 @@ the section whose source it was inlined from:
   prologue         before the pass loop
 
 It counts instruction classes, nothing else: VALU (v_*), vector memory (global_ / flat_ / scratch_ / buffer_) and LDS (ds_)
-make up "vector"; scalar instructions are listed beside them.  Registers, spills and occupancy are read from the kernel's
-metadata in the same assembly.
+make up "vector"; scalar instructions are listed beside them.  `moves` are the register copies among the VALU instructions
+(v_mov_b32 + v_mov_b64: what the register allocator adds at block joins, and constants).  --opcodes prints, below the table,
+every section's instructions by opcode, most frequent first (with --json: under "opcodes").  Registers, spills and occupancy
+are read from the kernel's metadata in the same assembly.
 """
 import json
 import os
@@ -38,6 +40,7 @@ CSRC = os.path.join(ROOT, "pooraytracer_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-function", "-fno-gpu-rdc"]  # build.py's CFLAGS
 SECTIONS = ("node visit", "round control", "leaf entry/exit", "leaf iteration", "chain step", "set-up", "hoisted", "pass", "prologue")
+MOVES = ("v_mov_b32", "v_mov_b64")
 WAVE_LOOP = ("node visit", "round control", "leaf entry/exit", "leaf iteration", "chain step")  # sections that live at loop depth >= 2
 
 
@@ -173,6 +176,7 @@ def main():
     C = Classifier()
     counts = {s: {"valu": 0, "vmem": 0, "lds": 0, "scalar": 0} for s in SECTIONS}
     marks = {s: {} for s in SECTIONS}
+    opcodes = {s: {} for s in SECTIONS}
     cur = "prologue"
     show = next((a.split("=", 1)[1] for a in args if a.startswith("--show=")), None)  # print that section's instructions
     depth, in_head, from_device = 0, False, False
@@ -204,17 +208,20 @@ def main():
         if show == sec:
             print(l)
         op = re.sub(r"_e(32|64)$", "", m.group(1))
+        opcodes[sec][op] = opcodes[sec].get(op, 0) + 1
         if op in ("v_rcp_f32", "v_div_fmas_f64", "v_div_fmas_f32", "v_pk_fma_f32", "v_cvt_f32_u32", "v_alignbit_b32", "v_mov_b64", "v_max_f64"):
             marks[sec][op] = marks[sec].get(op, 0) + 1
     entry = next((e for e in re.split(r"\n  - (?=\.agpr_count:)", "\n".join(text)) if re.search(r"\.name:\s+" + re.escape(sym) + r"\s", e)), "")
     meta = {k: int(v) for k, v in re.findall(r"\.(agpr_count|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s*(\d+)", entry)}
     occ = re.search(r"; Occupancy:\s*(\d+)", "\n".join(text[end:end + 80]))
     vec = {s: c["valu"] + c["vmem"] + c["lds"] for s, c in counts.items()}
+    moves = {s: sum(opcodes[s].get(op, 0) for op in MOVES) for s in SECTIONS}
+    by_count = {s: sorted(opcodes[s].items(), key=lambda kv: (-kv[1], kv[0])) for s in SECTIONS}
     copies = max(1, marks["leaf iteration"].get("v_div_fmas_f64", 0) + marks["leaf iteration"].get("v_div_fmas_f32", 0))
     sites = sum(marks[x].get("v_rcp_f32", 0) for x in SECTIONS if x != "prologue") // 3
     report = {
         "kernel": want, "flags": extra,
-        "vector": vec, "scalar": {s: c["scalar"] for s, c in counts.items()}, "detail": counts,
+        "vector": vec, "scalar": {s: c["scalar"] for s, c in counts.items()}, "detail": counts, "moves": moves,
         "leaf_loop_copies": copies, "leaf_iteration_vector": vec["leaf iteration"] / copies,
         "setup_sites": sites, "pass_static_vector": vec["pass"] + vec["set-up"] + vec["hoisted"],
         "total_vector": sum(vec.values()),
@@ -225,11 +232,13 @@ def main():
         "vgpr_spill": meta.get("vgpr_spill_count"), "sgpr_spill": meta.get("sgpr_spill_count"),
         "occupancy": int(occ.group(1)) if occ else None,
     }
+    if "--opcodes" in args:
+        report["opcodes"] = {s: dict(by_count[s]) for s in SECTIONS}
     if "--json" in args:
         print(json.dumps(report, indent=1))
         return
     print(f"{want}" + (f"  [{' '.join(extra)}]" if extra else ""))
-    print(f"{'section':18s} {'vector':>7s} {'VALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'scalar':>7s}")
+    print(f"{'section':18s} {'vector':>7s} {'VALU':>6s} {'VMEM':>5s} {'LDS':>4s} {'moves':>6s} {'scalar':>7s}")
     for s in SECTIONS:
         c = counts[s]
         note = ""
@@ -237,10 +246,14 @@ def main():
             note = f"   {copies} cop{'ies' if copies > 1 else 'y'} of the loop body: {vec[s] / copies:.1f} per iteration"
         if s == "set-up":
             note = f"   {sites} site{'s' if sites != 1 else ''} in the whole pass (v_rcp_f32 / 3, wherever they are booked)"
-        print(f"{s:18s} {vec[s]:7d} {c['valu']:6d} {c['vmem']:5d} {c['lds']:4d} {c['scalar']:7d}{note}")
+        print(f"{s:18s} {vec[s]:7d} {c['valu']:6d} {c['vmem']:5d} {c['lds']:4d} {moves[s]:6d} {c['scalar']:7d}{note}")
     print(f"{'whole kernel':18s} {sum(vec.values()):7d}")
     print(f"VGPR {report['vgprs']} AGPR {report['agprs']} SGPR {report['sgprs']} spilled VGPR {report['vgpr_spill']} SGPR {report['sgpr_spill']} "
           f"scratch {report['scratch_bytes_per_lane']} B/lane occupancy {report['occupancy']}")
+    if "--opcodes" in args:
+        for s in SECTIONS:
+            if by_count[s]:
+                print(f"\n{s}: " + "  ".join(f"{op} {n}" for op, n in by_count[s]))
 
 
 if __name__ == "__main__":
