@@ -235,6 +235,16 @@ int prt_abi_version(void);
 /* 1 when this build reads the developer / test environment hooks (PRT_TUNE_*, PRT_TEST_*; -DPRT_DEV_HOOKS=1 builds only —
  * libprt_hip_dev.so of the test suite).  The shipped libprt_hip.so returns 0 and reads no environment variable. */
 int prt_dev_hooks(void);
+/* Developer query (dev-hooks build): the form of the render kernel (K3) that this library's most recent launch used, in any
+ * scene and precision — PRT_RENDER_FORM_PLAIN: the instantiation compiled for a frame with default settings (no pixel
+ * jitter, light sampling on, a scene with emitters whose light triangles are staged in LDS, no pixel list, no counting,
+ * no ray batch); PRT_RENDER_FORM_GENERIC: every other launch, and every launch under PRT_TUNE_GENERIC=1.  The two forms
+ * compute the same frame bit for bit.  The shipped libprt_hip.so keeps no record and returns PRT_RENDER_FORM_UNKNOWN, as
+ * does the dev-hooks build before its first launch. */
+#define PRT_RENDER_FORM_UNKNOWN 0
+#define PRT_RENDER_FORM_GENERIC 1
+#define PRT_RENDER_FORM_PLAIN 2
+int prt_last_render_form(void);
 const char* prt_last_error(void);
 int prt_device_count(int* n);
 

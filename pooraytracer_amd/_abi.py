@@ -130,6 +130,8 @@ class PrtLightUpdateInfo(C.Structure):
 
 # PrtBvhInfo.render_variant, per precision byte (prt.h PRT_VARIANT_*)
 VARIANT_PERM_MASK, VARIANT_LLDS, VARIANT_PAD, VARIANT_EXTRA, VARIANT_VALID = 0x07, 0x08, 0x10, 0x20, 0x80
+# prt_last_render_form (prt.h PRT_RENDER_FORM_*)
+RENDER_FORM_UNKNOWN, RENDER_FORM_GENERIC, RENDER_FORM_PLAIN = 0, 1, 2
 
 
 class PrtCamera(C.Structure):
@@ -330,6 +332,7 @@ assert LIGHT_SAMPLE_DTYPE.itemsize == C.sizeof(PrtLightSample) == 64
 EXPORTS = [
     "prt_abi_version",
     "prt_dev_hooks",
+    "prt_last_render_form",
     "prt_shutdown",
     "prt_render_samples",
     "prt_render_multi",

@@ -185,6 +185,13 @@ class dev_hooks:
         return False
 
 
+def last_render_form(L=None):
+    """prt_last_render_form of `L` (default: the current library): which form of the render kernel the library's last K3
+    launch used — _abi.RENDER_FORM_PLAIN or RENDER_FORM_GENERIC; RENDER_FORM_UNKNOWN from the shipped library, which keeps no
+    record, and before the first launch."""
+    return int((L or load()).prt_last_render_form())
+
+
 def shutdown():
     """prt_shutdown of every library loaded so far (cached RCCL communicators)."""
     for L in _libs.values():

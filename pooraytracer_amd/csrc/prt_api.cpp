@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -130,13 +131,13 @@ struct Staging {
     int status(const std::string& who) const { return e == hipSuccess ? PRT_OK : hip_fail(who, e); }
 };
 
-// What the render kernels of one precision get: the scene tables, resident blocks per CU of the plain and the counting
-// instantiation, the light-tree nodes / light triangles / materials staged in LDS (all 0 = the kernels without LDS
-// tables), and the traversal stack entries per lane.
+// What the render kernels of one precision get: the scene tables, resident blocks per CU of the production, the counting
+// and the PLAIN instantiation (k_render; 0: the scene's frames have no PLAIN form), the light-tree nodes / light triangles /
+// materials staged in LDS (all 0 = the kernels without LDS tables), and the traversal stack entries per lane.
 template <typename R>
 struct KernelConfig {
     DSceneT<R> d{};
-    int blocks_per_cu[2] = {0, 0};
+    int blocks_per_cu[3] = {0, 0, 0};
     int blocks_per_cu_rays = 0; // ... and of the ray-batch instantiation (prt_ray_color), queried by its first call
     int light_lds = 0, ltri_lds = 0, mat_lds = 0;
     int stack_depth = PRT_STACK_DEPTH;
@@ -144,6 +145,16 @@ struct KernelConfig {
 } // namespace
 
 extern "C" int prt_dev_hooks(void) { return PRT_DEV_HOOKS; }
+
+// The form of the last K3 launch (prt.h, prt_last_render_form): kept by the dev-hooks build only.
+#if PRT_DEV_HOOKS
+static std::atomic<int> g_render_form{PRT_RENDER_FORM_UNKNOWN};
+static void note_render_form(bool plain) { g_render_form = plain ? PRT_RENDER_FORM_PLAIN : PRT_RENDER_FORM_GENERIC; }
+extern "C" int prt_last_render_form(void) { return g_render_form; }
+#else
+static void note_render_form(bool) {}
+extern "C" int prt_last_render_form(void) { return PRT_RENDER_FORM_UNKNOWN; }
+#endif
 
 #define PRT_HIP_AS(who, call)                                                                           \
     do {                                                                                                \
@@ -510,6 +521,19 @@ static void size_tables(const PrtScene* s, int budget, size_t mat_bytes, size_t 
     if (const char* e = dev_env("PRT_TUNE_LTRI_LDS")) if (!std::atoi(e)) *ltri = 0;
 }
 
+// Whether a K3 launch of the scene's kernels of precision R with these launch values uses the PLAIN form (k_render): the
+// launchers' render_plain decides, here for the occupancy query and for the launch alike.  PRT_TUNE_GENERIC=1 (developer): every
+// launch keeps its generic kernel.
+template <typename R>
+static bool frame_plain(const PrtScene* s, const KernelConfig<R>& k, bool count, bool rays, int jitter, int scramble, int sample_lights) {
+    const auto plain = std::is_same<R, double>::value ? prt::render_plain : prt32::render_plain;
+    return plain(s->feat, count, rays, k.d.n_lights, k.ltri_lds, jitter, scramble, sample_lights);
+}
+static bool generic_forced() {
+    const char* e = dev_env("PRT_TUNE_GENERIC");
+    return e && std::atoi(e);
+}
+
 // LDS tables and resident blocks per CU of the render kernels of one precision, for stacks of k.stack_depth entries.
 // drop_tables: render without the tables when they would cost the production kernel a resident block (the budget is an
 // estimate; the occupancy query is the truth).  Returns the blocks per CU without the tables (with drop_tables; else
@@ -524,13 +548,16 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
                 &k.mat_lds, &k.ltri_lds, &k.light_lds);
     const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
     const bool extra = !s->lights.tab.empty() || k.d.tex_compact != 0;
-    auto blocks = [&](bool count, size_t tables) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra, false); };
+    auto blocks = [&](bool count, size_t tables, bool plain = false) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra, false, plain); };
     const size_t tables = table_bytes(k.light_lds, k.mat_lds, k.ltri_lds);
     k.blocks_per_cu[0] = blocks(false, tables);
+    // a frame with default settings launches the PLAIN form where the scene has one: a function of its own, asked about on its own
+    k.blocks_per_cu[2] = frame_plain(s, k, false, false, 0, 0, 1) ? blocks(false, tables, true) : 0;
     const int wanted = drop_tables && tables != 0 ? blocks(false, 0) : k.blocks_per_cu[0];
-    if (k.blocks_per_cu[0] < wanted) { // a block per CU is worth far more than the tables
+    if (k.blocks_per_cu[0] < wanted || (k.blocks_per_cu[2] && k.blocks_per_cu[2] < wanted)) { // a block per CU is worth far more than the tables
         k.mat_lds = k.ltri_lds = k.light_lds = 0;
         k.blocks_per_cu[0] = wanted;
+        k.blocks_per_cu[2] = 0; // (no light triangles in LDS: no PLAIN form)
     }
     k.blocks_per_cu[1] = blocks(true, table_bytes(k.light_lds, k.mat_lds, k.ltri_lds));
     if (dev_env("PRT_TUNE_VERBOSE")) {
@@ -563,7 +590,7 @@ static int rays_blocks_per_cu(const PrtScene* s, KernelConfig<R>& k) {
         constexpr bool f64 = std::is_same<R, double>::value;
         const size_t tables = (f64 ? prt::render_table_bytes : prt32::render_table_bytes)(k.light_lds, k.mat_lds, k.ltri_lds);
         const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
-        k.blocks_per_cu_rays = (f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu)(false, s->feat, tables, k.stack_depth, pad, true, true);
+        k.blocks_per_cu_rays = (f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu)(false, s->feat, tables, k.stack_depth, pad, true, true, false);
     }
     return k.blocks_per_cu_rays;
 }
@@ -2701,7 +2728,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
         P.items_per_chunk = pass.list_n;
     }
     const bool count = count_work != 0;
-    int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : 0];
+    const bool plain = !generic_forced() && (f32 ? frame_plain(s, s->k32, count, pass.rays, P.jitter, P.scramble, P.sample_lights)
+                                                 : frame_plain(s, s->k64, count, pass.rays, P.jitter, P.scramble, P.sample_lights));
+    int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : plain ? 2 : 0];
     if (pass.rays) bpc = f32 ? rays_blocks_per_cu(s, s->k32) : rays_blocks_per_cu(s, s->k64);
     const uint64_t lanes = (uint64_t)s->n_cu * bpc * PRT_BLOCK;
     // Work item = (pixel, chunk of samples), dealt chunk-major from PRT_ITEM_QUEUES counters (prt_types.h).
@@ -2793,8 +2822,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
             }
         }
         // fp32: the same camera and parameters rounded to float (K5 below works from the fp64 originals: it only maps pixels)
-        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays);
-        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays);
+        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain);
+        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain);
+        note_render_form(plain);
         PRT_HIP(hipGetLastError());
     }
     PRT_HIP(q.stop(st));
@@ -2874,7 +2904,8 @@ int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams*
     P.tile = 8; P.tiles_x = P.tiles_y = P.n_tiles = 1; P.rank = 0; P.nranks = 1; P.owned_tiles = 1; // (the items come from the list)
     P.items_per_chunk = n_pixels;
     const bool count = trace != nullptr;
-    const int bpc = s->k64.blocks_per_cu[count ? 1 : 0];
+    const bool plain = !generic_forced() && frame_plain(s, s->k64, count, false, P.jitter, P.scramble, P.sample_lights); // (false: the items come from a list)
+    const int bpc = s->k64.blocks_per_cu[count ? 1 : plain ? 2 : 0];
     const size_t per_launch = n_pixels * (size_t)std::min<int>(sample_count, PRT_MAX_CHUNKS);
     Staging b;
     const int32_t* d_pix = static_cast<const int32_t*>(b.in(pix.data(), n_pixels * sizeof(int32_t)));
@@ -2896,8 +2927,10 @@ int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams*
         if (d_trace) PRT_HIP_AS(who, hipMemset(d_trace, 0, (size_t)P.n_items * PRT_TRACE_WORDS * sizeof(int32_t)));
         PRT_HIP_AS(who, q.start(nullptr));
         PRT_HIP_AS(who, q.set_pointers(nullptr, d_pix, d_trace));
-        if (P.max_depth >= 0) prt::launch_render(s->k64.d, C, P, d_part, q.d_ctr.get(), count, s->feat, grid, nullptr);
-        else PRT_HIP_AS(who, hipMemset(d_part, 0, (size_t)P.n_items * 3 * sizeof(double)));
+        if (P.max_depth >= 0) {
+            prt::launch_render(s->k64.d, C, P, d_part, q.d_ctr.get(), count, s->feat, grid, nullptr, false, plain);
+            note_render_form(plain);
+        } else PRT_HIP_AS(who, hipMemset(d_part, 0, (size_t)P.n_items * 3 * sizeof(double)));
         PRT_HIP_AS(who, hipGetLastError());
         PRT_HIP_AS(who, q.stop(nullptr));
         PRT_HIP_AS(who, q.finish(nullptr, count, P.max_depth >= 0 ? P.n_items : 0));

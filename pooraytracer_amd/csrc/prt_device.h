@@ -878,6 +878,7 @@ PRT_DEV d3 ct_sample_wm(const DMaterial& m, d3 w, d2 u) { // Material.h:412-435
 #define PRT_FEAT_EXTRA 8
 #define PRT_FEAT_NARROW 16 // not a material feature either: texture lookups of this caller fetch their footprint a row at a time (tex_value)
 #define PRT_FEAT_RAYS 32   // not a material feature either: K3 takes its primary rays from DCounters::ray_list instead of a camera (prt_ray_color)
+#define PRT_FEAT_PLAIN 64  // not a material feature either: K3 for a frame with default settings — what such a launch never does is compiled out (k_render, PLAIN)
 template <int FEAT>
 PRT_DEV d3 mat_kd(const DScene& S, const DMaterial& m, d2 uv) {
     if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0, (FEAT & PRT_FEAT_NARROW) != 0>(S, m.texture, uv.x, uv.y);

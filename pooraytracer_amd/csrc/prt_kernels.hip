@@ -463,6 +463,18 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
     // direction and taking the block's one camera centre, so the park layout and the LDS budget are the frame kernels'.
     // `px` carries oi across the item; no pixel, no jitter.
     constexpr bool RAYS = (FEAT & PRT_FEAT_RAYS) != 0;
+    // PLAIN (PRT_FEAT_PLAIN; render_plain() on the host decides, from the same values): the launch renders a frame with default
+    // settings — no pixel jitter, items from the tiles, light sampling on, a scene with emitters whose light triangles are all
+    // staged in LDS.  What the generic kernel tests per pass as launch-uniform values are constants here, so the branches
+    // such a frame never takes (and the scalar registers that keep their conditions across the pass) are not compiled.
+    // Only the conditions differ: every expression, every draw and the order of terms into acc are the generic kernel's.
+    constexpr bool PLAIN = (FEAT & PRT_FEAT_PLAIN) != 0;
+    static_assert(!PLAIN || (!COUNT && !RAYS && LLDS), "PLAIN: production frame kernels with LDS tables only");
+#define JITTER (!PLAIN && P.jitter)                                // a camera ray of its own per sample
+#define FROM_LIST (!PLAIN && P.scramble == PRT_ITEMS_FROM_LIST)    // prt_render_samples, adaptive rounds
+#define SAMPLE_LIGHTS (PLAIN || P.sample_lights)                   // bSampleLights
+#define HAS_LIGHTS (PLAIN || S.n_lights > 0)
+#define LTRI_LDS (PLAIN ? 1 : P.ltri_lds)                          // > 0: the light triangles are read from LDS (all or none are staged)
     __shared__ uint32_t s_qoff[PRT_BLOCK / 64];
     __shared__ unsigned long long s_rays[PRT_BLOCK / 64];
     __shared__ real s_center[4]; // Camera::center, the origin of every camera ray
@@ -625,7 +637,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
 #define NEW_SAMPLE(parked) do {                                                                                                                                           \
         /* per-sample stream keyed (seed, j*W+i, s) */                                                                                                                    \
         rng.seed_keyed(P.seed_key, (uint64_t)pixel, (uint64_t)s);                                                                                                         \
-        if (!RAYS && P.jitter) {                                                                                                                                          \
+        if (!RAYS && JITTER) {                                                                                                                                            \
             /* the disabled SampleSquare() offset of Camera.cpp:110-111, drawn per sample: y first (g++ argument order); */                                               \
             /* a camera ray of its own, traced like any other */                                                                                                          \
             const ColdRenderArgs q = cold_args();                                                                                                                         \
@@ -690,7 +702,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 d3 x = mk3(0, 0, 0);
                 // (Measured: veach-mis -2.0 %, where many pixels look at a light or past the scene; cornell +0.7 %, bathroom2 +-0 —
                 // so only the permutations with glossy materials carry it.  prt_render_samples keeps the per-sample flow.)
-                if ((FEAT & (PRT_FEAT_PHONG | PRT_FEAT_CT)) && P.scramble != PRT_ITEMS_FROM_LIST) {
+                if ((FEAT & (PRT_FEAT_PHONG | PRT_FEAT_CT)) && !FROM_LIST) {
                     if (tr.hit.tri < 0) {
                         const ColdRenderArgs q = cold_args();
                         x = mk3(q->P.background[0], q->P.background[1], q->P.background[2]);
@@ -751,7 +763,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 } else if (state == ST_CLOSEST) {
                     if (tr.hit.tri < 0) {
                         // a traced ray left the scene: background for the camera ray (Camera.cpp:127); with bSampleLights a bounce miss adds 0 (:187)
-                        if (first || !P.sample_lights) {
+                        if (first || !SAMPLE_LIGHTS) {
                             const ColdRenderArgs q = cold_args();
                             ADD_RADIANCE(mk3(q->P.background[0], q->P.background[1], q->P.background[2]));
                         }
@@ -764,7 +776,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                 if (ended) END_OF_SAMPLE(ST_NEW_SAMPLE);
                 if (state == ST_NEW_SAMPLE) {
                     NEW_SAMPLE(ST_CLOSEST);
-                    hit_ready = RAYS || !P.jitter; // (a jittered sample's camera ray is traced first: the set-up at the bottom starts it)
+                    hit_ready = RAYS || !JITTER; // (a jittered sample's camera ray is traced first: the set-up at the bottom starts it)
                 }
                 PROF_MARK(3); // cheap ends + sample turnover: booked with the end of sample / fetch section below
             } else {
@@ -773,7 +785,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
             if (TURN ? hit_ready : state == ST_CLOSEST) {
                 if (tr.hit.tri < 0) {
                     // miss: background for the camera ray (Camera.cpp:127); with bSampleLights a bounce miss adds 0 (:187)
-                    if (first || !P.sample_lights) {
+                    if (first || !SAMPLE_LIGHTS) {
                         const ColdRenderArgs q = cold_args();
                         ADD_RADIANCE(mk3(q->P.background[0], q->P.background[1], q->P.background[2]));
                     }
@@ -784,18 +796,18 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     TRACE_VERTEX(S.shade[tr.hit.tri].prim);
                     if (m.has_emission) {
                         // Camera.cpp:129-132; via a bounce only after SkipLightSampling materials (:191-195)
-                        if (first || !P.sample_lights || prev_skip) ADD_RADIANCE(ld3(m.emission));
+                        if (first || !SAMPLE_LIGHTS || prev_skip) ADD_RADIANCE(ld3(m.emission));
                         end_sample = true;
                     } else {
                         rd = tr.d;
                         sh_tri = tr.hit.tri;
                         tr.o = tr.o + tr.d * tr.hit.t; // record.position = ray(t): from here on the origin of whatever comes next
                         do_scatter = true;
-                        if (P.sample_lights && S.n_lights > 0 && !m.skip_light_sampling) {
+                        if (SAMPLE_LIGHTS && HAS_LIGHTS && !m.skip_light_sampling) {
                             // next-event estimation, Camera.cpp:137-155: pick the light point now (4 draws)
                             const d3 gn = ld3(tri_at<PAD>(S, (uint32_t)sh_tri)->n);
                             const d3 fn = dot(rd, gn) < RL(0.) ? gn : -gn;
-                            const LightPick lp = sample_lights<LLDS, (FEAT & PRT_FEAT_EXTRA) != 0>(S, tr.o, rng, lds_lights, P.light_lds, lds_ltris, P.ltri_lds);
+                            const LightPick lp = sample_lights<LLDS, (FEAT & PRT_FEAT_EXTRA) != 0>(S, tr.o, rng, lds_lights, P.light_lds, lds_ltris, LTRI_LDS);
                             real dist;
                             const d3 ldir = normalize_len(lp.pos - tr.o, dist);
                             if (dot(fn, ldir) > RL(0.0) && lp.front) {
@@ -813,7 +825,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                                         d3 ln0;
                                         real pdf;
                                         int32_t lmat;
-                                        if (LLDS && P.ltri_lds > 0) {
+                                        if (LLDS && LTRI_LDS > 0) {
                                             const DLightTri* lt = lds_ltris + lp.tri;
                                             ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
                                         } else {
@@ -864,7 +876,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     d3 ln0;
                     real pdf;
                     int32_t lmat;
-                    if (LLDS && P.ltri_lds > 0) {
+                    if (LLDS && LTRI_LDS > 0) {
                         const DLightTri* lt = lds_ltris + ltri;
                         ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
                     } else {
@@ -910,7 +922,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                         d3 ln0;
                         real pdf;
                         int32_t lmat;
-                        if (LLDS && P.ltri_lds > 0) {
+                        if (LLDS && LTRI_LDS > 0) {
                             const DLightTri* lt = lds_ltris + ltri;
                             ln0 = ld3(lt->n); pdf = lt->pdf; lmat = lt->material;
                         } else {
@@ -1016,7 +1028,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     if (RAYS) { // prt_ray_color: item oi of a chunk is ray oi of the batch
                         px = (int)oi;
                         valid = true;
-                    } else if (P.scramble == PRT_ITEMS_FROM_LIST) { // prt_render_samples: the pixels of a list
+                    } else if (FROM_LIST) { // prt_render_samples: the pixels of a list
                         const int32_t pix = ctr->pixel_list[oi];
                         py = pix / W;
                         px = pix - py * W;
@@ -1041,7 +1053,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                         } else if (RAYS) {
                             load_ray(ctr->ray_list, oi, tr.o, tr.d);
                             state = ST_PRIMARY;
-                        } else if (P.jitter) {
+                        } else if (JITTER) {
                             state = TURN ? ST_CACHED : ST_NEW_SAMPLE; // a camera ray of its own per sample (below; TURN: the next pass's turnover)
                         } else {
                             // Camera::GetRay (Camera.cpp:108-117), once per work item: the pixel's one camera ray.  Its direction
@@ -1607,7 +1619,7 @@ namespace PRT_NS {
 // The compiled permutations: lean, textures only, Phong only, CookTorrance only, everything.  A scene gets the smallest one
 // that covers its materials.
 int render_permutation(int feat) {
-    feat &= ~PRT_FEAT_RAYS; // (not a material feature: the ray source of prt_ray_color)
+    feat &= ~(PRT_FEAT_RAYS | PRT_FEAT_PLAIN); // (not material features: the ray source of prt_ray_color, the PLAIN form)
     if (feat == 0 || feat == PRT_FEAT_TEX || feat == PRT_FEAT_PHONG || feat == PRT_FEAT_CT) return feat;
     return PRT_FEAT_ALL;
 }
@@ -1625,11 +1637,24 @@ size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds) {
 }
 
 typedef void (*RenderKernel)(RenderArgs);
+// The permutations that have a PLAIN form of k_render: the fp64 ones except the textured one, whose PLAIN form measured 1.4 %
+// SLOWER than its generic kernel on bathroom2; no fp32 kernel gained from it (all bit-identical).
+constexpr bool plain_permutation(int perm) { return !PRT_F32_TU && perm != PRT_FEAT_TEX; }
+// THE decision between the two forms of a launch's kernel, from the values the generic kernel tests at run time (k_render,
+// PLAIN): prt_api.cpp asks here, for the occupancy query and for the launch, and hands the answer to both as `plain`.
+bool render_plain(int feat, bool count, bool rays, int n_lights, int ltri_lds, int jitter, int scramble, int sample_lights) {
+    return plain_permutation(render_permutation(feat)) && !count && !rays && n_lights > 0 && ltri_lds > 0 && !jitter &&
+           scramble != PRT_ITEMS_FROM_LIST && sample_lights;
+}
 // COUNT instantiations exist only with PRT_FEAT_EXTRA (statistics runs: speed is not what they are for); so do the
-// PRT_FEAT_RAYS ones (prt_ray_color: one kernel per permutation and layout, no counting form)
+// PRT_FEAT_RAYS ones (prt_ray_color: one kernel per permutation and layout, no counting form).  PLAIN ones exist with LDS
+// tables only (render_plain asks for the light triangles there), with and without PRT_FEAT_EXTRA.
 template <int FEAT, bool PAD>
-static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool rays) {
+static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool rays, bool plain) {
     constexpr int X = FEAT | PRT_FEAT_EXTRA;
+    if constexpr (plain_permutation(FEAT)) {
+        if (plain) return extra ? k_render<false, X | PRT_FEAT_PLAIN, true, PAD> : k_render<false, FEAT | PRT_FEAT_PLAIN, true, PAD>;
+    }
     if (rays) return llds ? k_render<false, X | PRT_FEAT_RAYS, true, PAD> : k_render<false, X | PRT_FEAT_RAYS, false, PAD>;
     if (count) return llds ? k_render<true, X, true, PAD> : k_render<true, X, false, PAD>;
     if (extra) return llds ? k_render<false, X, true, PAD> : k_render<false, X, false, PAD>;
@@ -1638,16 +1663,18 @@ static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool r
 template <bool PAD>
 static RenderKernel render_kernel_pad(bool count, int feat, bool llds, bool extra) {
     const bool rays = (feat & PRT_FEAT_RAYS) != 0;
+    const bool plain = (feat & PRT_FEAT_PLAIN) != 0 && llds && !count && !rays; // (what render_plain implies: said again for the instantiations' sake)
     switch (render_permutation(feat)) {
-    case 0: return render_kernel_feat<0, PAD>(count, llds, extra, rays);
-    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra, rays);
-    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra, rays);
-    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra, rays);
-    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra, rays);
+    case 0: return render_kernel_feat<0, PAD>(count, llds, extra, rays, plain);
+    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra, rays, plain);
+    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra, rays, plain);
+    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra, rays, plain);
+    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra, rays, plain);
     }
 }
 // `pad`: the scene's intersection records sit 128 bytes apart (DScene::tri_stride); `extra`: the scene has light tables or
-// plain texel arrays (PRT_FEAT_EXTRA kernels); `feat` with PRT_FEAT_RAYS: the kernel of prt_ray_color
+// plain texel arrays (PRT_FEAT_EXTRA kernels); `feat` with PRT_FEAT_RAYS: the kernel of prt_ray_color; with PRT_FEAT_PLAIN: the
+// PLAIN form (render_plain said so)
 static RenderKernel render_kernel(bool count, int feat, bool llds, bool pad, bool extra) {
     return pad ? render_kernel_pad<true>(count, feat, llds, extra) : render_kernel_pad<false>(count, feat, llds, extra);
 }
@@ -1656,9 +1683,10 @@ static size_t stack_bytes(int stack_depth) { return PRT_DYN_STACK ? (size_t)PRT_
 
 // Resident blocks per CU of the instantiation a launch will use (`pad`: the scene's records sit at the padded stride —
 // a different function with its own register count).
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays) {
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain) {
     int nb = 0;
     if (rays) feat |= PRT_FEAT_RAYS;
+    if (plain) feat |= PRT_FEAT_PLAIN;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel(count, feat, table_bytes != 0, pad, extra), PRT_BLOCK,
                                                                 table_bytes + stack_bytes(stack_depth));
     if (e != hipSuccess || nb < 1) nb = 1;
@@ -1706,7 +1734,7 @@ hipError_t launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d
 
 // `rays`: the ray-batch kernels (prt_ray_color; DCounters::ray_list / key_list are set, C is not read)
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,
-                   bool count, int feat, unsigned grid, hipStream_t st, bool rays) {
+                   bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain) {
     static_assert(sizeof(DMaterial) % 16 == 0, "materials are staged in 16-byte pieces");
     const size_t tables = render_table_bytes(P.light_lds, P.mat_lds, P.ltri_lds);
     const size_t dyn_lds = tables + stack_bytes(P.stack_depth);
@@ -1718,6 +1746,7 @@ void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, do
     A.partial = d_partial;
     A.ctr = d_ctr;
     if (rays) feat |= PRT_FEAT_RAYS;
+    if (plain) feat |= PRT_FEAT_PLAIN;
     hipLaunchKernelGGL(render_kernel(count, feat, tables != 0, pad, S.light_tab != nullptr || S.tex_compact != 0), dim3(grid), dim3(PRT_BLOCK), dyn_lds, st, A);
 }
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Vector-instruction counts of one k_render instantiation, section by section (offline: hipcc cross-compiles, no GPU).
 
-    python tools/isa_sections.py                       # k_render<false, 0, true, false>, the headline kernel
+    python tools/isa_sections.py                       # k_render<false, 64, true, false>, the headline kernel (lean, PLAIN form;
+                                                       # its generic form is k_render<false, 0, true, false>)
     python tools/isa_sections.py "k_render<false, 4, true, false>" [-DPRT_X=1 ...] [--json] [--list] [--show=SECTION] [--opcodes]
     python tools/isa_sections.py --csrc=DIR [--asm=FILE]   # another checkout's csrc/ (and an assembly already made from it)
 
@@ -161,7 +162,7 @@ def main():
     args = sys.argv[1:]
     CSRC = next((a.split("=", 1)[1] for a in args if a.startswith("--csrc=")), CSRC)  # the sources of another checkout
     extra = [a for a in args if a.startswith("-D")]
-    want = next((a for a in args if not a.startswith("-")), "k_render<false, 0, true, false>")
+    want = next((a for a in args if not a.startswith("-")), "k_render<false, 64, true, false>")
     text = assembly(extra, next((a.split("=", 1)[1] for a in args if a.startswith("--asm=")), None))
     funcs = [m.group(1) for l in text for m in [re.match(r"\s*\.type\s+(\S+),@function", l)] if m]
     names = demangle(funcs)
