@@ -22,7 +22,8 @@ LIB = os.path.join(HERE, "libprt_hip.so")
 DEV_LIB = os.path.join(HERE, "libprt_hip_dev.so")
 OBJ = os.path.join(HERE, "_obj")
 SOURCES = ["prt_api.cpp", "prt_kernels.hip", "prt_kernels_f32.hip", "bvh_build.cpp", "bvh_build_gpu.hip", "bvh_refit.hip", "light_tables.hip", "ray_sort.hip", "scene_setup.cpp", "prt_denoise.hip", "closest_point.hip", "pseudonormals.hip", "winding_number.hip", "mesh_topology.cpp", "multi_hit.hip", "multi_hit_f32.hip"]
-HEADERS = ["prt_types.h", "prt_device.h", "prt_light_pick.h", "prt_host.h", "prt_launch.h", "mesh_topology.h", os.path.join("..", "..", "include", "prt.h")]
+HEADERS = ["prt_types.h", "prt_device.h", "prt_light_pick.h", "prt_wave.h", "prt_vec64.h", "prt_host.h", "prt_launch.h", "mesh_topology.h", os.path.join("..", "..", "include", "prt.h")]
+PROBE_HEADERS = ["prt_types.h", "prt_device.h", "prt_light_pick.h", "prt_wave.h", "prt_host.h"]  # what tests/probe/*.hip can reach
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-gpu-rdc"]
 DEV_FLAGS = ["-DPRT_DEV_HOOKS=1"]
@@ -95,7 +96,7 @@ def build_probe(force=False, verbose=False):
     """tests/probe/libprt_probe.so: the TEST-ONLY element-wise wrappers of prt_device.h's primitives (fp64 + fp32 twin).
     Same flags as the product, same freshness rule on the headers; linked on its own, never into the product libraries."""
     lib = PROBE_LIB
-    deps = [os.path.join(PROBE_DIR, s) for s in PROBE_SOURCES] + [os.path.join(CSRC, h) for h in HEADERS[:4]] + [os.path.abspath(__file__)]
+    deps = [os.path.join(PROBE_DIR, s) for s in PROBE_SOURCES] + [os.path.join(CSRC, h) for h in PROBE_HEADERS] + [os.path.abspath(__file__)]
     if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(d) for d in deps):
         return lib
     cmd = [HIPCC, "-shared"] + CFLAGS + ["-o", lib] + [os.path.join(PROBE_DIR, s) for s in PROBE_SOURCES]

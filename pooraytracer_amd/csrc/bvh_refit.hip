@@ -26,6 +26,7 @@
 #pragma clang fp contract(off)
 
 #include "prt_launch.h"
+#include "prt_vec64.h"
 
 namespace prt {
 
@@ -40,14 +41,6 @@ constexpr unsigned kMaxBlocks = 1024; // partials of the two reductions (prt_api
 constexpr int32_t kUnused = (int32_t)0x80000000;
 constexpr uint32_t kNoParent = 0xffffffffu;
 
-struct V {
-    double x, y, z;
-};
-__device__ inline V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline V add(V a, V b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ inline V scale(V a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ inline double dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ inline V cross(V a, V b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 __device__ inline V unit(V a) { return scale(a, 1.0 / sqrt(dot(a, a))); }
 __device__ inline bool has_nan(V a) { return a.x != a.x || a.y != a.y || a.z != a.z; }
 __device__ inline V load3(const double* p) { return {p[0], p[1], p[2]}; }
@@ -90,6 +83,8 @@ __device__ inline double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     return v;
 }
+// (a butterfly like the two above, the sum in every lane: prt_wave.h's wave_sum, valid in lane 0 only, gives k_refit_sah the
+// same bits through other vector instructions, so this one stays)
 __device__ inline double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;

@@ -37,6 +37,8 @@
 #pragma clang fp contract(off)
 
 #include "prt_launch.h"
+#include "prt_vec64.h"
+#include "prt_wave.h"
 
 namespace prt {
 namespace {
@@ -44,12 +46,6 @@ namespace {
 constexpr uint32_t kUnusedRef = 0x80000000u;
 constexpr uint32_t kNoKey = 0xffffffffu;
 
-struct V {
-    double x, y, z;
-};
-__device__ __forceinline__ V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V cross(V a, V b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 // v0 + alpha (v1 - v0) + beta (v2 - v0), per component ((v0 + alpha ab) + beta ac): contract 2's `point`
 __device__ __forceinline__ V bary_point(V a, V ab, V ac, double al, double be) {
     return {a.x + al * ab.x + be * ac.x, a.y + al * ab.y + be * ac.y, a.z + al * ab.z + be * ac.z};
@@ -140,12 +136,6 @@ __device__ __forceinline__ float f32_above(double x) {
     return f + fabsf(f) * 2.4e-7f;
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 struct ClosestArgs {
     const DNode* nodes;
     const DTriCorners* corners;
@@ -162,17 +152,6 @@ struct SignedArgs : ClosestArgs { // the SIGNED instantiations' (the others keep
     const double* normal;
     uint32_t n_normals; // edges + vertices
 };
-
-__device__ __forceinline__ V corner(const double4 c0, const double4 c1, const double2 c2, int k) {
-    return k == 0 ? V{c0.x, c0.y, c0.z} : k == 1 ? V{c0.w, c1.x, c1.y} : V{c1.z, c1.w, c2.x};
-}
-
-// The stepping loop of a wave runs while MORE than this many of its lanes are still descending; below it the finished
-// lanes write their records and take the next queries (K1's scheme, prt_kernels.hip).
-#ifndef PRT_K6_KEEP
-#define PRT_K6_KEEP 48
-#endif
-#define PRT_K6_CHUNK 256 // queries a wave takes from the global counter at a time (one atomic per chunk)
 
 // REFILL: persistent waves; a lane takes its next query the moment its descent ends (a wave-local pool refilled by one
 // atomic per PRT_K6_CHUNK queries), so that no lane waits for the slowest query of its wave.  !REFILL: the plain form, one
@@ -201,17 +180,14 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional
     uint32_t cur = kUnusedRef; // an inner node, a leaf ref, or kUnusedRef: nothing left
     size_t qi = 0;             // the query this lane is answering
     bool have = false, active = false;
-    unsigned long long pool_next = 0, pool_end = 0; // the wave's pool of queries [pool_next, pool_end)
-    bool exhausted = false;                         // wave-uniform
+    WavePool<PRT_K6_CHUNK> pool; // the wave's queries (prt_wave.h); !REFILL uses only its `exhausted`
     for (;;) {
         if (!active && have) { // the lane's descent has ended: its record
             double4 o0 = make_double4(__builtin_huge_val(), 0.0, 0.0, 0.0), o1 = make_double4(0.0, 0.0, 0.0, 0.0);
             int32_t prim = -1, feature = -1, side = 0, sign = 0; // sign: PrtClosestPoint.reserved = 0 unless SIGNED
             if (best_prim != INT32_MAX) {
-                const double4* rec = reinterpret_cast<const double4*>(A.corners + best_at);
-                const double4 c0 = rec[0], c1 = rec[1];
-                const double2 c2 = *reinterpret_cast<const double2*>(rec + 2);
-                const V a = corner(c0, c1, c2, 0), ab = sub(corner(c0, c1, c2, 1), a), ac = sub(corner(c0, c1, c2, 2), a);
+                const Corners t = load_corners(A.corners + best_at);
+                const V a = t.v0, ab = sub(t.v1, a), ac = sub(t.v2, a);
                 const V pt = bary_point(a, ab, ac, best_al, best_be); // the same expression on the same values as in the test
                 const double s = dot(cross(ab, ac), sub(p, pt));
                 o0 = make_double4(sqrt(best_d2), pt.x, pt.y, pt.z);
@@ -245,29 +221,19 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional
         size_t next = 0;
         if (REFILL) {
             const unsigned long long need = __ballot(!active);
-            if (need != 0ULL && !exhausted) {
-                if (pool_next >= pool_end) {
-                    unsigned long long base = 0;
-                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&A.ctr->next_item, (unsigned long long)PRT_K6_CHUNK);
-                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                    pool_next = base;
-                    pool_end = base + PRT_K6_CHUNK < (unsigned long long)A.n ? base + PRT_K6_CHUNK : (unsigned long long)A.n;
-                    if (base >= (unsigned long long)A.n) exhausted = true;
-                }
-                if (!exhausted && !active) {
-                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(need & ((1ULL << lane) - 1ULL));
-                    take = idx < pool_end;
+            if (pool.wants(need)) {
+                pool.refill(need, lane, A.n, &A.ctr->next_item);
+                if (!pool.exhausted && !active) {
+                    const unsigned long long idx = pool.index(need, lane);
+                    take = idx < pool.end;
                     next = (size_t)idx;
                 }
-                if (!exhausted) {
-                    const unsigned long long taken = (unsigned long long)__popcll(need);
-                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-                }
+                pool.advance(need);
             }
-        } else if (!exhausted) {
+        } else if (!pool.exhausted) {
             next = (size_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
             take = next < A.n;
-            exhausted = true;
+            pool.exhausted = true;
         }
         if (take) { // the lane starts query `next`
             const PrtPointQuery* q = A.q + next;
@@ -284,7 +250,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional
             have = true;
             active = A.n_tris != 0 && lim == lim; // (no triangles, or a NaN radius: the miss record)
         }
-        if (__ballot(active || have) == 0ULL && exhausted) break;
+        if (__ballot(active || have) == 0ULL && pool.exhausted) break;
         do {
             if (active) {
                 if ((int32_t)cur >= 0) {
@@ -338,12 +304,10 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional
                     const uint32_t enc = ~cur;
                     const uint32_t first = enc >> 3, cnt = (enc & 7u) + 1u;
                     for (uint32_t i = 0; i < cnt; ++i) {
-                        const double4* rec = reinterpret_cast<const double4*>(A.corners + first + i);
-                        const double4 c0 = rec[0], c1 = rec[1];
-                        const double2 c2 = *reinterpret_cast<const double2*>(rec + 2);
-                        const int32_t prim = (int32_t)(uint32_t)__double_as_longlong(c2.y);
+                        int32_t prim;
+                        const Corners t = load_corners(A.corners + first + i, &prim);
                         if (COUNT) n_tests++;
-                        const V a = corner(c0, c1, c2, 0), b = corner(c0, c1, c2, 1), c = corner(c0, c1, c2, 2);
+                        const V a = t.v0, b = t.v1, c = t.v2;
                         double al, be;
                         int32_t feature;
                         point_triangle(p, a, b, c, al, be, feature);
@@ -370,16 +334,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_closest_point(std::conditional
             }
         } while (__popcll(__ballot(active)) > (REFILL ? PRT_K6_KEEP : 0));
     }
-    if (COUNT) {
-        const unsigned long long a = wave_sum((unsigned long long)n_nodes), b = wave_sum((unsigned long long)n_tests);
-        const unsigned long long c = wave_sum((unsigned long long)n_drop_inner), d = wave_sum((unsigned long long)n_drop_leaf);
-        if (lane == 0) {
-            atomicAdd(&A.ctr->node_fetches, a);
-            atomicAdd(&A.ctr->tri_tests, b);
-            atomicAdd(&A.ctr->inner_rounds, c);
-            atomicAdd(&A.ctr->leaf_rounds, d);
-        }
-    }
+    flush_query_counts<COUNT>(A.ctr, lane, n_nodes, n_tests, n_drop_inner, n_drop_leaf);
 }
 
 __global__ void __launch_bounds__(256) k_gather_corners(const double* __restrict__ verts, const uint32_t* __restrict__ order, uint32_t n,
@@ -421,16 +376,10 @@ void fill_args(ClosestArgs& A, const DScene& S, const DTriCorners* d_corners, co
 }
 template <typename Kernel, typename Args>
 hipError_t launch_k6(Kernel k, const Args& A, int n_cu, bool plain, hipStream_t st) {
-    const size_t lds = (size_t)2 * PRT_BLOCK * A.stack_depth * sizeof(uint32_t);
-    if (lds > 64u * 1024u) { // more dynamic LDS than a launch may ask for by default
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    // the plain form: a block per 256 queries; persistent waves: as many blocks as can be resident (LDS: 160 KB per CU;
-    // registers: four waves per SIMD)
-    const size_t want = (A.n + PRT_BLOCK - 1) / PRT_BLOCK;
-    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / lds));
-    const unsigned grid = (unsigned)(plain ? want : std::min<size_t>(want, (size_t)std::max(n_cu, 1) * per_cu));
+    const size_t lds = (size_t)2 * PRT_BLOCK * A.stack_depth * sizeof(uint32_t); // refs and bounds: at most 80 KB
+    unsigned grid = 0;
+    const hipError_t e = point_query_grid(reinterpret_cast<const void*>(k), A.n, lds, n_cu, plain, grid);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), lds, st, A);
     return hipGetLastError();
 }

@@ -52,13 +52,6 @@
 #define PRT_NS prt
 #endif
 
-// K1's scheduling constants (prt_kernels.hip)
-#ifndef PRT_K1_KEEP
-#define PRT_K1_KEEP 48
-#endif
-#ifndef PRT_K1_CHUNK
-#define PRT_K1_CHUNK 1024
-#endif
 // Resident waves per SIMD the register allocator must leave room for.  Three, not K1's four: with that freedom the plain
 // fp64 instantiations come out at 126 registers without scratch and are resident four to a SIMD all the same (what the 40 KB
 // of stacks per block allow); asked for four, the padded-record one spills 12 bytes per lane.  The counting instantiations
@@ -70,12 +63,6 @@
 namespace {
 
 constexpr int CAP = PRT_MULTI_HIT_MAX;
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 template <bool COUNT, bool PAD>
 __global__ __launch_bounds__(PRT_BLOCK, PRT_K7_WAVES) void k_trace_multi(DScene S, const PrtRay* __restrict__ rays,
@@ -98,8 +85,7 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K7_WAVES) void k_trace_multi(DScene 
     int32_t cur_prim = -1;
     bool have = false;
     size_t my = 0;
-    unsigned long long pool_next = 0, pool_end = 0; // the wave's pool of rays, as in K1
-    bool exhausted = false;                         // wave-uniform
+    WavePool<PRT_K1_CHUNK> pool; // the wave's rays, K1's chunk and keep (prt_wave.h)
     for (;;) {
         if (!tr.active && have) { // the lane's traversal has ended: its k records, 32 bytes at a time
             double4* o = reinterpret_cast<double4*>(out + my * (size_t)k);
@@ -123,19 +109,11 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K7_WAVES) void k_trace_multi(DScene 
         }
         {
             const unsigned long long need = __ballot(!tr.active);
-            if (need != 0ULL && !exhausted) {
-                if (pool_next >= pool_end) {
-                    unsigned long long base = 0;
-                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
-                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                    pool_next = base;
-                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
-                    if (base >= (unsigned long long)n) exhausted = true;
-                }
-                if (!exhausted && !tr.active) {
-                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
-                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
-                    if (idx < pool_end) {
+            if (pool.wants(need)) {
+                pool.refill(need, lane, n, &ctr->next_item);
+                if (!pool.exhausted && !tr.active) {
+                    const unsigned long long idx = pool.index(need, lane);
+                    if (idx < pool.end) {
                         const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
                         const double4* rp = reinterpret_cast<const double4*>(rays + ri);
                         const double4 r0 = rp[0], r1 = rp[1];
@@ -158,13 +136,10 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K7_WAVES) void k_trace_multi(DScene 
                         nrays++;
                     }
                 }
-                if (!exhausted) {
-                    const unsigned long long taken = (unsigned long long)__popcll(need);
-                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-                }
+                pool.advance(need);
             }
         }
-        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
+        if (__ballot(tr.active || have) == 0ULL && pool.exhausted) break;
         do { // Trav::round with this kernel's leaf step
             if (COUNT && __ballot(tr.active && tr.cur >= 0) != 0ULL) wc.inner_rounds++;
             if (tr.active && tr.cur >= 0) tr.template inner_step<COUNT>(S, stk, wc);
@@ -221,18 +196,7 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K7_WAVES) void k_trace_multi(DScene 
             }
         } while (wave_count(tr.active) > PRT_K1_KEEP);
     }
-    const unsigned long long a = wave_sum((unsigned long long)nrays);
-    const unsigned long long b = wave_sum((unsigned long long)wc.nodes);
-    const unsigned long long c = wave_sum((unsigned long long)wc.tris);
-    const unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
-    if (lane == 0) {
-        atomicAdd(&ctr->rays_closest, a);
-        if (COUNT) {
-            atomicAdd(&ctr->node_fetches, b);
-            atomicAdd(&ctr->tri_tests, c);
-            atomicAdd(&ctr->tri_full, f);
-        }
-    }
+    flush_trace_counts<COUNT>(ctr, lane, &ctr->rays_closest, nrays, wc);
 }
 
 } // namespace

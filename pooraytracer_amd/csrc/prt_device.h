@@ -12,6 +12,7 @@
 
 #include "prt_types.h"
 #include "prt_light_pick.h"
+#include "prt_wave.h"
 
 #define PRT_DEV __device__ __forceinline__
 // The scalar type of everything that is a real number in the reference (glm::dvec3 arithmetic): double, or float in the
@@ -179,6 +180,23 @@ struct WorkCount {
     uint32_t tris_full; // COUNT builds: triangle tests that went past the plane / interval check (second 64 bytes fetched)
     uint32_t inner_rounds, leaf_rounds; // COUNT builds: wave-level executions of inner_step / leaf_step (lane 0 counts)
 };
+// K1 / K1s / K7 after their loop: the wave's rays into `rays_counter` (rays_closest or rays_shadow of `ctr`) and, in the COUNT
+// instantiations, its traversal work into the call's counters
+template <bool COUNT>
+__device__ __forceinline__ void flush_trace_counts(DCounters* ctr, int lane, unsigned long long* rays_counter, uint32_t nrays, const WorkCount& wc) {
+    const unsigned long long a = wave_sum((unsigned long long)nrays);
+    const unsigned long long b = wave_sum((unsigned long long)wc.nodes);
+    const unsigned long long c = wave_sum((unsigned long long)wc.tris);
+    const unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
+    if (lane == 0) {
+        atomicAdd(rays_counter, a);
+        if (COUNT) {
+            atomicAdd(&ctr->node_fetches, b);
+            atomicAdd(&ctr->tri_tests, c);
+            atomicAdd(&ctr->tri_full, f);
+        }
+    }
+}
 
 // Record i of the intersection array.  PAD: the records sit 128 bytes apart (one per line; scenes that stream from
 // HBM) instead of sizeof(DTri) — a kernel template parameter, so the stride is a constant of each instantiation

@@ -71,26 +71,15 @@ constexpr int render_waves(int feat_with_extra) {
 }
 // The stepping loop of a wave runs while MORE than this many lanes are still traversing; below it the
 // finished lanes are handed new rays (K1) / shaded and re-armed (K3).
-#ifndef PRT_K1_KEEP
-#define PRT_K1_KEEP 48
-#endif
+// (PRT_K1_KEEP and PRT_K1_CHUNK: prt_wave.h)
 #ifndef PRT_K3_KEEP
 #define PRT_K3_KEEP 24
 #endif
 #ifndef PRT_K1_WAVES
 #define PRT_K1_WAVES 4 // resident waves per SIMD the K1 register allocation leaves room for
 #endif
-#ifndef PRT_K1_CHUNK
-#define PRT_K1_CHUNK 1024
-#endif
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 #ifndef PRT_K3_PROFILE
 #define PRT_K3_PROFILE 0 // developer diagnostic (COUNT instantiation): shader-clock cycles per section of the wave loop, folded into the counters
@@ -121,6 +110,18 @@ __device__ __forceinline__ T wave_sum(T v) {
 // PrtSurface.  A sibling kernel, not a third mode of k_trace: as a mode (the loop as a device function under two wrappers)
 // the any-hit instantiations compiled to other multiply-add contractions than before, and their bytes left the closest-hit
 // kernel's on edge-grazing rays (2 of 400,000 on the 2M-triangle soup in fp32).
+// What the two kernels (and K7, K6, K8) do share is the integer scheduling code around the loop: the wave's ray pool
+// (WavePool, prt_wave.h) and the counter flush (flush_trace_counts, prt_device.h).  How much of the pool can be a function was
+// settled on the compiled instructions, per kernel against the text that carried the block itself ("Shared
+// scheduling code of the batch kernels"):
+//   - one take(idle, lane, n, counter, idx&) doing refill, index and advance: the ray set-up after it contracts differently
+//     (fp64 k_trace: v_fma_f32 28 -> 30, v_pk_fma_f32 5 -> 4, v_pk_mul_f32 5 -> 4, v_add_f32 1 -> 0) - the hazard above;
+//   - deal(idle, ..., set-up as a lambda): ~25 more instructions per kernel, and again another fp32 mix;
+//   - open() / index() / advance() with open() refilling and returning `need != 0 && !exhausted`: fp32 mix intact, but
+//     written with an early return or as nested ifs the any-hit fp64 kernels lose a v_cmp / v_cndmask pair and K6 / K8 gain
+//     a v_mov_b64; with the result computed before the refill the two counting any-hit fp64 kernels still lose the pair;
+//   - wants() / refill() / index() / advance(), the condition tested by the kernel: every vector opcode count of every
+//     kernel is the former one, registers, scratch and occupancy too.  That is the form in use; tr.init() stays in the kernel.
 #ifndef PRT_K1S_WAVES
 #define PRT_K1S_WAVES PRT_K1_WAVES // the 40 KB of stacks allow four blocks per CU; the surface write-out fits their 128 registers without scratch
 #endif
@@ -139,10 +140,7 @@ __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void
     tr.active = false;
     bool have = false;
     size_t my = 0;
-    // wave-local ray pool [pool_next, pool_end): refilled PRT_K1_CHUNK rays at a time by ONE atomic per
-    // wave (a single global counter saturates at ~90 dequeues/us on this chip)
-    unsigned long long pool_next = 0, pool_end = 0;
-    bool exhausted = false; // wave-uniform
+    WavePool<PRT_K1_CHUNK> pool; // the wave's rays (prt_wave.h)
     for (;;) {
         if (!tr.active && have) {
             if constexpr (ANY) {
@@ -169,19 +167,11 @@ __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void
         }
         {
             const unsigned long long need = __ballot(!tr.active);
-            if (need != 0ULL && !exhausted) {
-                if (pool_next >= pool_end) {
-                    unsigned long long base = 0;
-                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
-                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                    pool_next = base;
-                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
-                    if (base >= (unsigned long long)n) exhausted = true;
-                }
-                if (!exhausted && !tr.active) {
-                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
-                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
-                    if (idx < pool_end) {
+            if (pool.wants(need)) {
+                pool.refill(need, lane, n, &ctr->next_item);
+                if (!pool.exhausted && !tr.active) {
+                    const unsigned long long idx = pool.index(need, lane);
+                    if (idx < pool.end) {
                         const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
                         const double4* rp = reinterpret_cast<const double4*>(rays + ri);
                         const double4 r0 = rp[0], r1 = rp[1];
@@ -191,29 +181,15 @@ __global__ __launch_bounds__(PRT_BLOCK, ANY ? PRT_K1O_WAVES : PRT_K1_WAVES) void
                         nrays++;
                     }
                 }
-                if (!exhausted) {
-                    const unsigned long long taken = (unsigned long long)__popcll(need);
-                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-                }
+                pool.advance(need);
             }
         }
-        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
+        if (__ballot(tr.active || have) == 0ULL && pool.exhausted) break;
         do {
             tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, ANY);
         } while (wave_count(tr.active) > (ANY ? PRT_K1O_KEEP : PRT_K1_KEEP));
     }
-    unsigned long long a = wave_sum((unsigned long long)nrays);
-    unsigned long long b = wave_sum((unsigned long long)wc.nodes);
-    unsigned long long c = wave_sum((unsigned long long)wc.tris);
-    unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
-    if (lane == 0) {
-        atomicAdd(ANY ? &ctr->rays_shadow : &ctr->rays_closest, a);
-        if (COUNT) {
-            atomicAdd(&ctr->node_fetches, b);
-            atomicAdd(&ctr->tri_tests, c);
-            atomicAdd(&ctr->tri_full, f);
-        }
-    }
+    flush_trace_counts<COUNT>(ctr, lane, ANY ? &ctr->rays_shadow : &ctr->rays_closest, nrays, wc);
 }
 
 // ------------------------------------------------------------------------------------------- K3
@@ -336,10 +312,7 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1S_WAVES) void k_trace_surface(DSce
     tr.active = false;
     bool have = false;
     size_t my = 0;
-    // wave-local ray pool [pool_next, pool_end): refilled PRT_K1_CHUNK rays at a time by ONE atomic per
-    // wave (a single global counter saturates at ~90 dequeues/us on this chip)
-    unsigned long long pool_next = 0, pool_end = 0;
-    bool exhausted = false; // wave-uniform
+    WavePool<PRT_K1_CHUNK> pool; // the wave's rays (prt_wave.h)
     for (;;) {
         if (!tr.active && have) {
             surface_record<PAD>(S, tr.o, tr.d, tr.hit, out + my);
@@ -347,19 +320,11 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1S_WAVES) void k_trace_surface(DSce
         }
         {
             const unsigned long long need = __ballot(!tr.active);
-            if (need != 0ULL && !exhausted) {
-                if (pool_next >= pool_end) {
-                    unsigned long long base = 0;
-                    if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&ctr->next_item, (unsigned long long)PRT_K1_CHUNK);
-                    base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                    pool_next = base;
-                    pool_end = base + PRT_K1_CHUNK < (unsigned long long)n ? base + PRT_K1_CHUNK : (unsigned long long)n;
-                    if (base >= (unsigned long long)n) exhausted = true;
-                }
-                if (!exhausted && !tr.active) {
-                    const unsigned long long below = need & ((1ULL << lane) - 1ULL);
-                    const unsigned long long idx = pool_next + (unsigned long long)__popcll(below);
-                    if (idx < pool_end) {
+            if (pool.wants(need)) {
+                pool.refill(need, lane, n, &ctr->next_item);
+                if (!pool.exhausted && !tr.active) {
+                    const unsigned long long idx = pool.index(need, lane);
+                    if (idx < pool.end) {
                         const size_t ri = perm ? (size_t)perm[idx] : (size_t)idx; // the idx-th ray of the sorted order
                         const double4* rp = reinterpret_cast<const double4*>(rays + ri);
                         const double4 r0 = rp[0], r1 = rp[1];
@@ -369,29 +334,15 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_K1S_WAVES) void k_trace_surface(DSce
                         nrays++;
                     }
                 }
-                if (!exhausted) {
-                    const unsigned long long taken = (unsigned long long)__popcll(need);
-                    pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-                }
+                pool.advance(need);
             }
         }
-        if (__ballot(tr.active || have) == 0ULL && exhausted) break;
+        if (__ballot(tr.active || have) == 0ULL && pool.exhausted) break;
         do {
             tr.template round<COUNT>(S, stk, wc, PRT_LEAF_BATCH, PRT_INNER_MIN, tr.tmin, false);
         } while (wave_count(tr.active) > PRT_K1_KEEP);
     }
-    unsigned long long a = wave_sum((unsigned long long)nrays);
-    unsigned long long b = wave_sum((unsigned long long)wc.nodes);
-    unsigned long long c = wave_sum((unsigned long long)wc.tris);
-    unsigned long long f = wave_sum((unsigned long long)wc.tris_full);
-    if (lane == 0) {
-        atomicAdd(&ctr->rays_closest, a);
-        if (COUNT) {
-            atomicAdd(&ctr->node_fetches, b);
-            atomicAdd(&ctr->tri_tests, c);
-            atomicAdd(&ctr->tri_full, f);
-        }
-    }
+    flush_trace_counts<COUNT>(ctr, lane, &ctr->rays_closest, nrays, wc);
 }
 
 // A real number parked in / fetched from a lane's LDS column (`base` = the lane's slot of word 0, words PRT_BLOCK apart)

@@ -1,10 +1,11 @@
-// prt_launch.h — every launcher and device-side helper that prt_api.cpp calls, declared once.  Declarations only: the
-// file that defines a function includes this header too, so a definition that drifts from its declaration (a default
-// argument, a struct passed by value) does not compile.  Scene types are spelled with their precision, so the fp64 and the
+// prt_launch.h — every launcher and device-side helper that prt_api.cpp calls, declared once.  Declarations only (but for
+// point_query_grid, the launch sizing K6 and K8 share): the file that defines a function includes this header too, so a
+// definition that drifts from its declaration (a default argument, a struct passed by value) does not compile.  Scene types are spelled with their precision, so the fp64 and the
 // fp32 translation units read the same text.  Default arguments live here and nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string> // ray_sort's and the device builder's `std::string* err`
 
 #include "../../include/prt.h"
@@ -93,6 +94,20 @@ bool build_bvh_device_boxes(const PrimBox* d_boxes, const float box_origin[3], s
                             hipStream_t st);
 void launch_gather_tris(const DTriT<double>* tri_in, const DTriShadeT<double>* shade_in, const uint32_t* order, uint32_t n,
                         void* tri_out, uint32_t tri_out_stride, DTriShadeT<double>* shade_out, hipStream_t st);
+// The grid of a point-query launch (K6, K8) with `lds` bytes of dynamic LDS for the lanes' stacks; the kernel `k` is allowed
+// that much where it is more than a launch may ask for by default.  plain: a block per PRT_BLOCK queries; otherwise
+// persistent waves, as many blocks as can be resident (LDS: 160 KB per CU; registers: at most four waves per SIMD).
+// (The one definition in this header: both files size their launch by it.)
+inline hipError_t point_query_grid(const void* k, size_t n, size_t lds, int n_cu, bool plain, unsigned& grid) {
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
+    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / lds));
+    grid = (unsigned)(plain ? want : std::min<size_t>(want, (size_t)std::max(n_cu, 1) * per_cu));
+    return hipSuccess;
+}
 // closest_point.hip: the corner table of a scene that answers distance queries, and K6
 void launch_gather_corners(const double* d_verts, const uint32_t* d_order, uint32_t n, DTriCorners* d_out, hipStream_t st);
 hipError_t launch_closest_point(const DSceneT<double>& S, const DTriCorners* d_corners, const PrtPointQuery* d_q, size_t n,

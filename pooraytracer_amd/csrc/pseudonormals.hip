@@ -22,18 +22,13 @@
 #pragma clang fp contract(off)
 
 #include "prt_launch.h"
+#include "prt_vec64.h"
 
 namespace prt {
 namespace {
 
 constexpr uint32_t kNoSlot = 0xffffffffu;
 
-struct V {
-    double x, y, z;
-};
-__device__ __forceinline__ V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V cross(V a, V b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 __device__ __forceinline__ double angle(V e1, V e2) {
     const V c = cross(e1, e2);
     return atan2(sqrt(dot(c, c)), dot(e1, e2));
@@ -43,10 +38,10 @@ __global__ void __launch_bounds__(256) k_face_terms(const DTriCorners* __restric
                                                     double* __restrict__ face) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const DTriCorners& c = corners[i];
-    const uint32_t t = (uint32_t)c.prim;
+    const uint32_t t = (uint32_t)corners[i].prim;
     if (t >= n) return; // (the leaf order is a permutation; never write out of the table)
-    const V a{c.v0[0], c.v0[1], c.v0[2]}, b{c.v1[0], c.v1[1], c.v1[2]}, d{c.v2[0], c.v2[1], c.v2[2]};
+    const Corners c = load_corners(corners + i);
+    const V a = c.v0, b = c.v1, d = c.v2;
     const V nrm = cross(sub(b, a), sub(d, a));
     const double nn = dot(nrm, nrm);
     const uint32_t* s = slot + (size_t)t * 6;

@@ -39,6 +39,8 @@
 #pragma clang fp contract(off)
 
 #include "prt_launch.h"
+#include "prt_vec64.h"
+#include "prt_wave.h"
 
 namespace prt {
 namespace {
@@ -46,25 +48,6 @@ namespace {
 constexpr uint32_t kUnusedRef = 0x80000000u;
 constexpr uint32_t kNoParent = 0xffffffffu;
 constexpr unsigned kBlock = 256;
-
-struct V {
-    double x, y, z;
-};
-__device__ __forceinline__ V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V add(V a, V b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V scale(V a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ double dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V cross(V a, V b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-
-struct Corners {
-    V v0, v1, v2;
-};
-__device__ __forceinline__ Corners load_corners(const DTriCorners* t) {
-    const double4* rec = reinterpret_cast<const double4*>(t);
-    const double4 c0 = rec[0], c1 = rec[1];
-    const double c2 = *reinterpret_cast<const double*>(rec + 2);
-    return {V{c0.x, c0.y, c0.z}, V{c0.w, c1.x, c1.y}, V{c1.z, c1.w, c2}};
-}
 
 struct Moment {
     V N, c;
@@ -197,12 +180,6 @@ __global__ void __launch_bounds__(kBlock) k_winding_moments(const DNode* __restr
     }
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 struct WindingArgs {
     const DNode* nodes;
     const DTriCorners* corners;
@@ -226,9 +203,6 @@ __device__ __forceinline__ double solid_angle(V p, const Corners& t) {
     return 2.0 * atan2(num, den);
 }
 
-#define PRT_K8_KEEP 48   // as PRT_K6_KEEP: the stepping loop runs while more than this many lanes are still walking
-#define PRT_K8_CHUNK 256 // queries a wave takes from the global counter at a time
-
 template <bool COUNT>
 __global__ __launch_bounds__(PRT_BLOCK, 2) void k_winding_number(WindingArgs A) {
     extern __shared__ uint32_t s_stack[]; // [PRT_BLOCK / 64][stack_depth][64] refs
@@ -241,8 +215,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_winding_number(WindingArgs A) 
     uint32_t cur = kUnusedRef; // an inner node, a leaf ref, or kUnusedRef: nothing left
     size_t qi = 0;
     bool have = false, active = false;
-    unsigned long long pool_next = 0, pool_end = 0; // the wave's pool of queries [pool_next, pool_end)
-    bool exhausted = false;                         // wave-uniform
+    WavePool<PRT_K8_CHUNK> pool; // the wave's queries (prt_wave.h)
     for (;;) {
         if (!active && have) { // the lane's walk has ended: its value
             A.out[qi] = S / (4.0 * 3.14159265358979323846);
@@ -251,24 +224,14 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_winding_number(WindingArgs A) 
         bool take = false;
         size_t next = 0;
         const unsigned long long need = __ballot(!active);
-        if (need != 0ULL && !exhausted) {
-            if (pool_next >= pool_end) {
-                unsigned long long base = 0;
-                if (lane == (int)__builtin_ctzll(need)) base = atomicAdd(&A.ctr->next_item, (unsigned long long)PRT_K8_CHUNK);
-                base = __shfl(base, (int)__builtin_ctzll(need), 64);
-                pool_next = base;
-                pool_end = base + PRT_K8_CHUNK < (unsigned long long)A.n ? base + PRT_K8_CHUNK : (unsigned long long)A.n;
-                if (base >= (unsigned long long)A.n) exhausted = true;
-            }
-            if (!exhausted && !active) {
-                const unsigned long long idx = pool_next + (unsigned long long)__popcll(need & ((1ULL << lane) - 1ULL));
-                take = idx < pool_end;
+        if (pool.wants(need)) {
+            pool.refill(need, lane, A.n, &A.ctr->next_item);
+            if (!pool.exhausted && !active) {
+                const unsigned long long idx = pool.index(need, lane);
+                take = idx < pool.end;
                 next = (size_t)idx;
             }
-            if (!exhausted) {
-                const unsigned long long taken = (unsigned long long)__popcll(need);
-                pool_next = pool_next + taken < pool_end ? pool_next + taken : pool_end;
-            }
+            pool.advance(need);
         }
         if (take) { // the lane starts query `next` (max_dist is not read)
             const PrtPointQuery* q = A.q + next;
@@ -280,7 +243,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_winding_number(WindingArgs A) 
             have = true;
             active = A.n_tris != 0 && A.n_nodes != 0; // (no triangles: the value is 0)
         }
-        if (__ballot(active || have) == 0ULL && exhausted) break;
+        if (__ballot(active || have) == 0ULL && pool.exhausted) break;
         do {
             if (active) {
                 if ((int32_t)cur >= 0) {
@@ -328,16 +291,7 @@ __global__ __launch_bounds__(PRT_BLOCK, 2) void k_winding_number(WindingArgs A) 
             }
         } while (__popcll(__ballot(active)) > PRT_K8_KEEP);
     }
-    if (COUNT) {
-        const unsigned long long a = wave_sum((unsigned long long)n_nodes), b = wave_sum((unsigned long long)n_tests);
-        const unsigned long long c = wave_sum((unsigned long long)n_far_inner), d = wave_sum((unsigned long long)n_far_leaf);
-        if (lane == 0) {
-            atomicAdd(&A.ctr->node_fetches, a);
-            atomicAdd(&A.ctr->tri_tests, b);
-            atomicAdd(&A.ctr->inner_rounds, c);
-            atomicAdd(&A.ctr->leaf_rounds, d);
-        }
-    }
+    flush_query_counts<COUNT>(A.ctr, lane, n_nodes, n_tests, n_far_inner, n_far_leaf);
 }
 
 } // namespace
@@ -374,12 +328,11 @@ hipError_t launch_winding_number(const DScene& S, const DTriCorners* d_corners, 
     A.n_nodes = S.n_nodes;
     A.stack_depth = std::min(std::max(stack_depth, 1), PRT_STACK_DEPTH);
     const size_t lds = (size_t)PRT_BLOCK * A.stack_depth * sizeof(uint32_t); // at most 40 KB
-    // persistent waves: as many blocks as can be resident (LDS: 160 KB per CU; registers: two to four waves per SIMD)
-    const size_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
-    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / lds));
-    const unsigned grid = (unsigned)std::min<size_t>(want, (size_t)std::max(n_cu, 1) * per_cu);
-    if (count) hipLaunchKernelGGL(k_winding_number<true>, dim3(grid), dim3(PRT_BLOCK), lds, st, A);
-    else hipLaunchKernelGGL(k_winding_number<false>, dim3(grid), dim3(PRT_BLOCK), lds, st, A);
+    const auto k = count ? k_winding_number<true> : k_winding_number<false>;
+    unsigned grid = 0;
+    const hipError_t e = point_query_grid(reinterpret_cast<const void*>(k), n, lds, n_cu, false, grid);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(PRT_BLOCK), lds, st, A);
     return hipGetLastError();
 }
 
