@@ -16,20 +16,12 @@ relMSE = mean over pixels and channels of (x - ref)^2 / (ref^2 + 1e-2).  Nothing
 """
 import argparse
 import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing_common import load, rel_mse, write_result
 
-WORKLOADS = {"cornell-box": ("cornell_box", 20), "veach-mis": ("veach_mis", 100)}
-
-
-def rel_mse(x, ref):
-    import numpy as np
-    return float(np.mean((x - ref) ** 2 / (ref ** 2 + 1e-2)))
+DEPTH = {"cornell-box": 20, "veach-mis": 100}  # bench.py's path depths
 
 
 def main():
@@ -48,12 +40,12 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import torch
-    from pooraytracer_amd import api, build, scenes
+    from pooraytracer_amd import api, build
     build.build()
     out = {"ref_spp": args.ref_spp, "min_spp": args.min_spp, "max_spp": args.max_spp, "round": args.round, "scenes": {}}
     for name in args.scenes.split(","):
-        factory, depth = WORKLOADS[name]
-        data = getattr(scenes, factory)()
+        depth = DEPTH[name]
+        data, _ = load(name)
         cam = data.camera
         npx = cam.width * cam.height
         sc = api.Scene(data).upload(0)
@@ -122,12 +114,7 @@ def main():
         out["scenes"][name] = res
         sc.close()
         print(json.dumps({name: res}), file=sys.stderr, flush=True)
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    write_result(out, args.out)
 
 
 if __name__ == "__main__":

@@ -15,26 +15,18 @@ fp64):
                defaults were chosen by): what prt_denoise_guided_defaults should be
   timing       hipEvent medians at 1024^2 (cornell-box): the guided filter by levels, the plain filter at the same levels,
                and k_accum_variance
-relMSE = mean over pixels and channels of (x - ref)^2 / (ref^2 + 1e-2) (as tools/adaptive_timing.py).
+relMSE = mean over pixels and channels of (x - ref)^2 / (ref^2 + 1e-2) (timing_common.rel_mse).
 """
 import argparse
 import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing_common import event as ev, load, rel_mse, write_result
 
-WORKLOADS = {"cornell-box": ("cornell_box", 20), "veach-mis": ("veach_mis", 100), "bathroom2": ("bathroom", 50)}
+DEPTH = {"cornell-box": 20, "veach-mis": 100, "bathroom2": 50}  # bench.py's path depths
 SWEEP = [dict(iterations=it, sigma_color=sc) for it in (4, 5) for sc in (1.0, 2.0, 4.0, 8.0)]
 BATCH = 4
-
-
-def rel_mse(x, ref):
-    import numpy as np
-    return float(np.mean((x - ref) ** 2 / (ref ** 2 + 1e-2)))
 
 
 def main():
@@ -46,16 +38,15 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import torch
-    from pooraytracer_amd import api, build, scenes
+    from pooraytracer_amd import api, build
     build.build()
     out = {"ref_spp": args.ref_spp, "batch": BATCH, "plain_defaults": api.denoise_defaults(),
            "guided_defaults": api.denoise_guided_defaults(), "scenes": {}}
     dev = torch.device("cuda", 0)
-    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
     spps = [int(s) for s in args.spps.split(",")]
     for name in args.scenes.split(","):
-        factory, depth = WORKLOADS[name]
-        data = getattr(scenes, factory)()
+        depth = DEPTH[name]
+        data, _ = load(name)
         cam = data.camera
         H, W = cam.height, cam.width
         sc = api.Scene(data).upload(0)
@@ -108,7 +99,7 @@ def main():
     out["sweep_mean_log_rel_mse"] = [dict(p, score=round(s, 5)) for p, s in zip(SWEEP, score)]
     out["sweep_best"] = SWEEP[int(np.argmin(score))]
     # cost at 1024^2: cornell-box, a 16-spp frame and its variance
-    data = scenes.cornell_box()
+    data, _ = load("cornell-box")
     sc = api.Scene(data).upload(0)
     feat = {k: torch.from_numpy(v).to(dev) for k, v in sc.features(max_depth=20, seed=1).items() if k != "prim"}
     x = torch.empty((1024, 1024, 3), dtype=torch.float32, device=dev)
@@ -138,12 +129,7 @@ def main():
                                     for it in range(1, 6)}
     out["timing_1024"] = timing
     sc.close()
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    write_result(out, args.out)
 
 
 if __name__ == "__main__":

@@ -14,37 +14,29 @@ fp64):
   levels       hipEvent time of the filter at 1024^2 with 1..5 levels (per-level cost = the differences)
   kernels      with profiling (default): a separate child run under `rocprofv3 --kernel-trace --stats` of the feature pass and
                the filter at 1024^2, and the per-kernel average times from its stats file
-relMSE = mean over pixels and channels of (x - ref)^2 / (ref^2 + 1e-2) (as tools/adaptive_timing.py).
+relMSE = mean over pixels and channels of (x - ref)^2 / (ref^2 + 1e-2) (timing_common.rel_mse).
 """
 import argparse
 import csv
 import glob
 import json
 import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing_common import event as ev, load, rel_mse, spawn, write_result
 
-WORKLOADS = {"cornell-box": ("cornell_box", 20), "veach-mis": ("veach_mis", 100), "bathroom2": ("bathroom", 50)}
+DEPTH = {"cornell-box": 20, "veach-mis": 100, "bathroom2": 50}  # bench.py's path depths
 SWEEP = [dict(iterations=it, sigma_color=sc, sigma_normal=sn) for it in (4, 5) for sc in (0.5, 1.0, 2.0, 4.0) for sn in (0.2, 0.5)]
-
-
-def rel_mse(x, ref):
-    import numpy as np
-    return float(np.mean((x - ref) ** 2 / (ref ** 2 + 1e-2)))
 
 
 def kernels_only():
     """The work the profiled child runs: features + filter on cornell-box 1024^2, a few times each."""
     import numpy as np
     import torch
-    from pooraytracer_amd import api, scenes
-    data = scenes.cornell_box()
+    from pooraytracer_amd import api
+    data, _ = load("cornell-box")
     cam = data.camera
     sc = api.Scene(data).upload(0)
     H, W = cam.height, cam.width
@@ -61,13 +53,12 @@ def kernels_only():
 
 def profile_kernels():
     d = tempfile.mkdtemp(prefix="dn_prof_")
-    cmd = ["timeout", "-k", "10", "600", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "dn", "--",
-           sys.executable, os.path.abspath(__file__), "--kernels-only"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    res = {"returncode": r.returncode}
+    rc, _ = spawn([os.path.abspath(__file__), "--kernels-only"], 600,
+                  wrap=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "dn", "--"])
+    res = {"returncode": rc}
     stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
     if not stats:
-        res["error"] = (r.stderr or "")[-400:]
+        res["error"] = "no kernel_stats.csv under " + d
         return res
     with open(stats[0]) as f:
         for row in csv.DictReader(f):
@@ -91,14 +82,13 @@ def main():
         return kernels_only()
     import numpy as np
     import torch
-    from pooraytracer_amd import api, build, scenes
+    from pooraytracer_amd import api, build
     build.build()
     defaults = api.denoise_defaults()
     out = {"ref_spp": args.ref_spp, "defaults": defaults, "scenes": {}}
-    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
     for name in args.scenes.split(","):
-        factory, depth = WORKLOADS[name]
-        data = getattr(scenes, factory)()
+        depth = DEPTH[name]
+        data, _ = load(name)
         cam = data.camera
         H, W = cam.height, cam.width
         sc = api.Scene(data).upload(0)
@@ -161,7 +151,7 @@ def main():
         sc.close()
         print(json.dumps({name: res}), file=sys.stderr, flush=True)
     # per-level cost at 1024^2 (cornell-box features, a 4-spp frame)
-    data = scenes.cornell_box()
+    data, _ = load("cornell-box")
     sc = api.Scene(data).upload(0)
     rgb = sc.render(spp=4, max_depth=20, seed=1).astype(np.float32)
     feat = {k: torch.from_numpy(v).cuda() for k, v in sc.features(max_depth=20, seed=1).items() if k != "prim"}
@@ -188,12 +178,7 @@ def main():
     out["sweep_best"] = dict(min(score, key=score.get))
     if not args.no_profile:
         out["kernels"] = profile_kernels()
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    write_result(out, args.out)
 
 
 if __name__ == "__main__":

@@ -5,8 +5,9 @@
 
 Every scene is one child process under its own `timeout` (the scene is built and uploaded once per child); the first
 child that fails ends the run (nothing more is started on the GPU after a fault).  A child prints each figure as one JSON
-line as soon as it has it, so what a failed child had measured is kept.  Per scene, on one device-resident batch of
-2^log2-rays S0 rays (origin uniform in the scene's box, direction uniform on the sphere, tmax = inf), in fp64 and fp32:
+line as soon as it has it, so what a failed child had measured is kept (tools/timing_common.py).  Per scene, on one
+device-resident batch of 2^log2-rays S0 rays (origin uniform in the scene's box, direction uniform on the sphere,
+tmax = inf), in fp64 and fp32:
   closest      trace_closest_device: one hit per ray
   multi[k]     trace_multi_device, k = 1, 2, 4, 8: ONE call
   peel[k]      the only way to the first k hits without the multi-hit call: k calls of trace_closest_device, tmin of
@@ -21,40 +22,24 @@ counting launch of closest and of multi[8] gives the node fetches and triangle t
 number of non-miss records of multi[8].
 """
 import argparse
-import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import timing_common as tc
 
-# name -> (scenes factory, keywords, tree built on the GPU)
-WORKLOADS = {
-    "cornell-box": ("cornell_box", {}, False),
-    "bathroom2": ("bathroom", {}, False),
-    "soup1m": ("triangle_soup", {"n_tris": 1_000_000}, True),
-}
+SCENES = ("cornell-box", "bathroom2", "soup1m")
+GROUPS = {"variant": "variants"}
 KS = (1, 2, 4, 8)
-CHILD_TIMEOUT_S = 900
 
 
-def stats(ms):
-    s = sorted(ms)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4)}
-
-
-def child(name, log2_rays, launches, warmup):
+def child(name, args):
     import numpy as np
     import torch
     from pooraytracer_amd import api, scenes
-    factory, kw, device_bvh = WORKLOADS[name]
-    data = getattr(scenes, factory)(**kw)
+    data, device_bvh = tc.load(name)
     sc = api.Scene(data, device_bvh=device_bvh).upload(0)
-    n = 1 << log2_rays
+    n = 1 << args.log2_rays
     lo, hi = data.bounds()
-    print(json.dumps({"n_tris": int(data.n_tris), "launches": launches, "rays": n}), flush=True)
+    tc.emit(n_tris=int(data.n_tris), launches=args.launches, rays=n)
     rays = scenes.random_rays(n, lo, hi, seed=12345)
     d_r = torch.from_numpy(rays.view(np.float64).reshape(-1, 8)).cuda()
     del rays
@@ -67,15 +52,9 @@ def child(name, log2_rays, launches, warmup):
         return buf.view(torch.int32).reshape(-1, 8)[:rows * k, 6].reshape(rows, k)
 
     for prec, pname in ((0, "f64"), (1, "f32")):
-        def closest(d_rays=d_r, count=False):
-            sc.trace_closest_device(d_rays.data_ptr(), n, d_h.data_ptr(), count_work=count, precision=prec)
-            torch.cuda.synchronize()
-            return sc.counters()
-
-        def multi(k, count=False):
-            sc.trace_multi_device(d_r.data_ptr(), n, k, d_m.data_ptr(), count_work=count, precision=prec)
-            torch.cuda.synchronize()
-            return sc.counters()
+        closest = tc.launcher(sc, sc.trace_closest_device, d_r.data_ptr(), n, d_h.data_ptr(), precision=prec)
+        peel_step = tc.launcher(sc, sc.trace_closest_device, d_p.data_ptr(), n, d_h.data_ptr(), precision=prec)
+        multi = {k: tc.launcher(sc, sc.trace_multi_device, d_r.data_ptr(), n, k, d_m.data_ptr(), precision=prec) for k in KS}
 
         def peel():
             """kernel_ms of each of the KS[-1] steps, and the number of hits every ray has after each."""
@@ -83,96 +62,50 @@ def child(name, log2_rays, launches, warmup):
             ms, found = [], torch.zeros(n, dtype=torch.int32, device="cuda")
             counts = []
             for _ in range(KS[-1]):
-                ms.append(closest(d_p)["kernel_ms"])
+                ms.append(peel_step()["kernel_ms"])
                 hit = prims(d_h, n, 1)[:, 0] >= 0
                 found += hit.to(torch.int32)
                 counts.append(found.clone())
                 t = d_h[:, 0]
                 past = torch.nextafter(t.float(), inf.float()).double() if prec else torch.nextafter(t, inf)  # the next t of the kernel's format
                 d_p[:, 3] = torch.where(hit, past, inf)
-            return ms, counts
+            return {"kernel_ms": ms, "counts": counts}
 
-        for _ in range(warmup):
-            closest()
-            for k in KS:
-                multi(k)
-            peel()
-        t_c, t_m, t_p = [], {k: [] for k in KS}, {k: [] for k in KS}
-        for _ in range(launches):  # the forms take turns, so that a drift of the box hits all alike
-            t_c.append(closest()["kernel_ms"])
-            for k in KS:
-                t_m[k].append(multi(k)["kernel_ms"])
-            ms, counts = peel()
-            for k in KS:
-                t_p[k].append(sum(ms[:k]))
-        r = {"closest": stats(t_c), "multi": {}, "peel": {}, "multi_over_closest": {}, "peel_over_multi": {}, "peel_short": {}}
+        # the forms take turns: closest, multi[1..8], the peel
+        t, last = tc.interleaved([("closest", closest)] + [(k, multi[k]) for k in KS] + [("peel", peel)], args.launches, args.warmup)
+        counts = last["peel"]["counts"]
+        r = {"closest": tc.stats(t["closest"]), "multi": {}, "peel": {}, "multi_over_closest": {}, "peel_over_multi": {}, "peel_short": {}}
         for k in KS:
-            multi(k)
+            multi[k]()
             listed = (prims(d_m, n, k) >= 0).sum(1).to(torch.int32)
-            r["multi"][k], r["peel"][k] = stats(t_m[k]), stats(t_p[k])
+            r["multi"][k], r["peel"][k] = tc.stats(t[k]), tc.stats([sum(ms[:k]) for ms in t["peel"]])
             r["multi_over_closest"][k] = round(r["multi"][k]["median_ms"] / r["closest"]["median_ms"], 4)
             r["peel_over_multi"][k] = round(r["peel"][k]["median_ms"] / r["multi"][k]["median_ms"], 4)
             r["peel_short"][k] = round(float((counts[k - 1] < listed).float().mean().item()), 6)
             if k == KS[-1]:
                 r["hits_per_ray"] = round(float(listed.float().mean().item()), 3)
-        cc, cm = closest(count=True), multi(KS[-1], count=True)
+        cc, cm = closest(count_work=True), multi[KS[-1]](count_work=True)
         r["per_ray"] = {"closest": {"node_fetches": round(cc["node_fetches"] / n, 3), "tri_tests": round(cc["tri_tests"] / n, 3)},
                         "multi8": {"node_fetches": round(cm["node_fetches"] / n, 3), "tri_tests": round(cm["tri_tests"] / n, 3)}}
-        print(json.dumps({"variant": pname, "result": r}), flush=True)
-        print(f"{name} {pname}: multi/closest {r['multi_over_closest']}, peel/multi {r['peel_over_multi']}", file=sys.stderr, flush=True)
+        tc.emit(f"{name} {pname}: multi/closest {r['multi_over_closest']}, peel/multi {r['peel_over_multi']}", variant=pname, result=r)
     sc.close()
-
-
-def collect(stdout):
-    """A child's JSON lines as one scene entry: the header, then variants[precision]."""
-    res = {"variants": {}}
-    for line in stdout.splitlines():
-        try:
-            rec = json.loads(line)
-        except ValueError:
-            continue
-        if "variant" in rec:
-            res["variants"][rec["variant"]] = rec["result"]
-        else:
-            res.update(rec)
-    return res
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="cornell-box,bathroom2,soup1m")
+    ap.add_argument("--scenes", default=",".join(SCENES))
     ap.add_argument("--log2-rays", type=int, default=24)
-    ap.add_argument("--launches", type=int, default=11)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--child", default="")
-    ap.add_argument("--out", default="")
+    tc.common_args(ap)
     args = ap.parse_args()
-    if args.launches < 10:
-        ap.error("--launches: the median of at least 10 launches")
     if args.child:
-        return child(args.child, args.log2_rays, args.launches, args.warmup)
+        return child(args.child, args)
+    names = tc.scene_names(ap, args.scenes, SCENES)
     from pooraytracer_amd import build
     build.build()
     out = {"log2_rays": args.log2_rays,
-           "method": "median kernel_ms of alternating launches after warm-up; peel[k] = sum of k closest-hit launches with tmin advanced",
-           "scenes": {}}
-    for name in args.scenes.split(","):
-        if name not in WORKLOADS:
-            ap.error(f"unknown scene {name}")
-        cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT_S), sys.executable, os.path.abspath(__file__), "--child", name,
-               "--log2-rays", str(args.log2_rays), "--launches", str(args.launches), "--warmup", str(args.warmup)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        out["scenes"][name] = collect(r.stdout)
-        if r.returncode != 0:
-            out["failed"] = {"scene": name, "returncode": r.returncode}
-            break  # nothing more is started after a failure
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 1 if "failed" in out else 0
+           "method": "median kernel_ms of alternating launches after warm-up; peel[k] = sum of k closest-hit launches with tmin advanced"}
+    out.update(tc.run_children(__file__, names, tc.flags(args, "log2_rays", "launches", "warmup"), None, GROUPS))
+    return tc.write_result(out, args.out)
 
 
 if __name__ == "__main__":

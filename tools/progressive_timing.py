@@ -14,14 +14,9 @@ On the bench's cornell-box frame (bench.py WORKLOADS["cornell-box"]: 1024^2, dep
 Nothing is written; bench.py is not involved.
 """
 import argparse
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from timing_common import event, load, write_result
 
 
 def main():
@@ -32,10 +27,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     import torch
-    from pooraytracer_amd import api, build, scenes
+    from pooraytracer_amd import api, build
     build.build()
     ladder = [int(x) for x in args.ladder.split(",")]
-    data = scenes.cornell_box(width=args.width, height=args.width)
+    data, _ = load("cornell-box", width=args.width, height=args.width)
     cam = data.camera
     sc = api.Scene(data).upload(0)
     kw = dict(max_depth=args.depth, seed=1)
@@ -48,7 +43,7 @@ def main():
     st = stream.cuda_stream
 
     def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a, b = event(), event()
         torch.cuda.synchronize()
         a.record(stream)
         fn()
@@ -120,7 +115,7 @@ def main():
         "preview": preview,
         "last_pass_counters": {k: c[k] for k in ("samples", "rays_closest", "rays_shadow", "kernel_ms")},
     }
-    print(json.dumps(out))
+    write_result(out, "")  # nothing is written: the line is the result
 
 
 if __name__ == "__main__":

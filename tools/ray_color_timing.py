@@ -4,7 +4,8 @@
                                    [--out profiles/ray_color_timing.json]
 
 The work runs in one child process under its own `timeout`; the child prints each figure as one JSON line as soon as it has
-it, so what a failed child had measured is kept, and nothing more is started on the GPU after a failure.  On the cornell box:
+it, so what a failed child had measured is kept, and nothing more is started on the GPU after a failure
+(tools/timing_common.py).  On the cornell box:
   A  camera   the size x size pinhole frame's own rays (pixel centres, Camera::Initialize / GetRay arithmetic in numpy) as a
               device-resident batch keyed j*W+i, through ray_color_device, against render_device of the same camera at the same
               spp and the same explicit sample_chunks, in fp64 and fp32.  The two calls alternate launch by launch after a
@@ -15,21 +16,12 @@ it, so what a failed child had measured is kept, and nothing more is started on 
               sphere) at the same spp, automatic chunking: median kernel_ms, rays and samples per second.
 """
 import argparse
-import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import timing_common as tc
 
-CHILD_TIMEOUT_S = 600
-
-
-def stats(ms):
-    s = sorted(ms)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4)}
+SCENE = "cornell-box"  # the one child's scene
+GROUPS = {"workload": ("workloads", "variant")}
 
 
 def pixel_centre_rays(cam):
@@ -56,14 +48,14 @@ def pixel_centre_rays(cam):
     return rays
 
 
-def child(args):
+def child(name, args):
     import numpy as np
     import torch
     from pooraytracer_amd import api, scenes
-    data = scenes.cornell_box(width=args.size, height=args.size)
+    data, _ = tc.load(name, width=args.size, height=args.size)
     cam = data.camera
     sc = api.Scene(data).upload(0)
-    print(json.dumps({"scene": data.name, "n_tris": int(data.n_tris), "size": args.size, "spp": args.spp, "launches": args.launches}), flush=True)
+    tc.emit(scene=data.name, n_tris=int(data.n_tris), size=args.size, spp=args.spp, launches=args.launches)
 
     def upload_rays(rays):
         return torch.from_numpy(rays.view(np.float64).reshape(-1, 8)).cuda()
@@ -77,33 +69,17 @@ def child(args):
     d_frame = torch.zeros((cam.height, cam.width, 3), dtype=torch.float64, device="cuda")
     for prec, pname in ((0, "f64"), (1, "f32")):
         kw = dict(spp=args.spp, max_depth=10, seed=1, sample_chunks=args.chunks, precision=prec)
-
-        def batch():
-            sc.ray_color_device(d_r.data_ptr(), n, d_batch.data_ptr(), None, d_keys_ptr=d_k.data_ptr(), **kw)
-            torch.cuda.synchronize()
-            return sc.counters()
-
-        def frame():
-            sc.render_device(d_frame.data_ptr(), None, **kw)
-            torch.cuda.synchronize()
-            return sc.counters()
-
-        for _ in range(args.warmup):
-            frame()
-            batch()
-        t_f, t_b = [], []
-        for _ in range(args.launches):  # alternating, so that a drift of the machine hits both alike
-            cf, cb = frame(), batch()
-            t_f.append(cf["kernel_ms"])
-            t_b.append(cb["kernel_ms"])
-        r = {"rays": n, "frame": stats(t_f), "batch": stats(t_b), "sample_chunks": args.chunks,
+        frame = tc.launcher(sc, sc.render_device, d_frame.data_ptr(), None, **kw)
+        batch = tc.launcher(sc, sc.ray_color_device, d_r.data_ptr(), n, d_batch.data_ptr(), None, d_keys_ptr=d_k.data_ptr(), **kw)
+        t, c = tc.interleaved([("frame", frame), ("batch", batch)], args.launches, args.warmup)
+        cf, cb = c["frame"], c["batch"]
+        r = {"rays": n, "frame": tc.stats(t["frame"]), "batch": tc.stats(t["batch"]), "sample_chunks": args.chunks,
              "frame_rays_traced": int(cf["rays_closest"] + cf["rays_shadow"]), "batch_rays_traced": int(cb["rays_closest"] + cb["rays_shadow"]),
              "max_abs_diff": float((d_batch.reshape(-1) - d_frame.reshape(-1)).abs().max().item())}
         r["ratio"] = round(r["batch"]["median_ms"] / r["frame"]["median_ms"], 4)
         r["batch"]["msamples_s"] = round(n * args.spp / r["batch"]["median_ms"] / 1e3, 1)
         r["frame"]["msamples_s"] = round(n * args.spp / r["frame"]["median_ms"] / 1e3, 1)
-        print(json.dumps({"workload": "camera", "variant": pname, "result": r}), flush=True)
-        print(f"camera {pname}: x{r['ratio']}", file=sys.stderr, flush=True)
+        tc.emit(f"camera {pname}: x{r['ratio']}", workload="camera", variant=pname, result=r)
     del d_r, d_k, d_batch, d_frame
 
     # ---- B: incoherent interior probes
@@ -112,40 +88,16 @@ def child(args):
     d_r = upload_rays(scenes.random_rays(n, lo, hi, seed=12345))
     d_out = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
     for prec, pname in ((0, "f64"), (1, "f32")):
-        kw = dict(spp=args.spp, max_depth=10, seed=1, precision=prec)
-
-        def probes():
-            sc.ray_color_device(d_r.data_ptr(), n, d_out.data_ptr(), None, **kw)
-            torch.cuda.synchronize()
-            return sc.counters()
-
-        for _ in range(args.warmup):
-            probes()
-        t, c = [], None
-        for _ in range(args.launches):
-            c = probes()
-            t.append(c["kernel_ms"])
-        r = {"rays": n, "probes": stats(t), "rays_traced": int(c["rays_closest"] + c["rays_shadow"]),
+        probes = tc.launcher(sc, sc.ray_color_device, d_r.data_ptr(), n, d_out.data_ptr(), None, spp=args.spp, max_depth=10, seed=1,
+                             precision=prec)
+        t, c = tc.interleaved([("probes", probes)], args.launches, args.warmup)
+        c = c["probes"]
+        r = {"rays": n, "probes": tc.stats(t["probes"]), "rays_traced": int(c["rays_closest"] + c["rays_shadow"]),
              "mean_radiance": float(d_out.mean().item())}
         r["probes"]["msamples_s"] = round(n * args.spp / r["probes"]["median_ms"] / 1e3, 1)
         r["probes"]["mrays_traced_s"] = round(r["rays_traced"] / r["probes"]["median_ms"] / 1e3, 1)
-        print(json.dumps({"workload": "probes", "variant": pname, "result": r}), flush=True)
-        print(f"probes {pname}: {r['probes']['median_ms']} ms", file=sys.stderr, flush=True)
+        tc.emit(f"probes {pname}: {r['probes']['median_ms']} ms", workload="probes", variant=pname, result=r)
     sc.close()
-
-
-def collect(stdout):
-    res = {"workloads": {}}
-    for line in stdout.splitlines():
-        try:
-            rec = json.loads(line)
-        except ValueError:
-            continue
-        if "workload" in rec:
-            res["workloads"].setdefault(rec["workload"], {})[rec["variant"]] = rec["result"]
-        else:
-            res.update(rec)
-    return res
 
 
 def main():
@@ -154,34 +106,17 @@ def main():
     ap.add_argument("--chunks", type=int, default=2)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--log2-probes", type=int, default=20)
-    ap.add_argument("--launches", type=int, default=11)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--child", action="store_true")
-    ap.add_argument("--out", default="")
+    tc.common_args(ap)
     args = ap.parse_args()
-    if args.launches < 10:
-        ap.error("--launches: the median of at least 10 launches")
     if args.chunks < 1:
         ap.error("--chunks: explicit sample chunks, at least 1")
     if args.child:
-        return child(args)
+        return child(args.child, args)
     from pooraytracer_amd import build
     build.build()
-    cmd = ["timeout", "-k", "10", str(CHILD_TIMEOUT_S), sys.executable, os.path.abspath(__file__), "--child", "--spp", str(args.spp),
-           "--chunks", str(args.chunks), "--size", str(args.size), "--log2-probes", str(args.log2_probes), "--launches", str(args.launches),
-           "--warmup", str(args.warmup)]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-    out = {"method": "median kernel_ms of alternating launches after warm-up; ratio = ray batch / frame"}
-    out.update(collect(r.stdout))
-    if r.returncode != 0:
-        out["failed"] = {"returncode": r.returncode}
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 1 if "failed" in out else 0
+    res = tc.run_children(__file__, [SCENE], tc.flags(args, "spp", "chunks", "size", "log2_probes", "launches", "warmup"), None, GROUPS)
+    out = {"method": "median kernel_ms of alternating launches after warm-up; ratio = ray batch / frame", **res.pop("scenes")[SCENE], **res}
+    return tc.write_result(out, args.out)
 
 
 if __name__ == "__main__":
