@@ -245,6 +245,16 @@ int prt_dev_hooks(void);
 #define PRT_RENDER_FORM_GENERIC 1
 #define PRT_RENDER_FORM_PLAIN 2
 int prt_last_render_form(void);
+/* Developer query (dev-hooks build): the sub-form of that launch.  PRT_RENDER_SUBFORM_DIFFUSE: a PLAIN launch (prt_last_render_form
+ * says PLAIN) of the lean fp64 kernel in a scene whose material table holds nothing but untextured Lambertians and emitters,
+ * none of which skips light sampling: the material tests of Eval and Scatter are compiled out as well.  PRT_RENDER_SUBFORM_NONE:
+ * every other launch, every launch under PRT_TUNE_NO_DIFFUSE=1 (a qualifying launch then uses the PLAIN kernel) and under
+ * PRT_TUNE_GENERIC=1.  All forms compute the same frame bit for bit.  The shipped libprt_hip.so returns
+ * PRT_RENDER_SUBFORM_UNKNOWN, as does the dev-hooks build before its first launch. */
+#define PRT_RENDER_SUBFORM_UNKNOWN 0
+#define PRT_RENDER_SUBFORM_NONE 1
+#define PRT_RENDER_SUBFORM_DIFFUSE 2
+int prt_last_render_subform(void);
 const char* prt_last_error(void);
 int prt_device_count(int* n);
 

@@ -132,6 +132,8 @@ class PrtLightUpdateInfo(C.Structure):
 VARIANT_PERM_MASK, VARIANT_LLDS, VARIANT_PAD, VARIANT_EXTRA, VARIANT_VALID = 0x07, 0x08, 0x10, 0x20, 0x80
 # prt_last_render_form (prt.h PRT_RENDER_FORM_*)
 RENDER_FORM_UNKNOWN, RENDER_FORM_GENERIC, RENDER_FORM_PLAIN = 0, 1, 2
+# prt_last_render_subform (prt.h PRT_RENDER_SUBFORM_*)
+RENDER_SUBFORM_UNKNOWN, RENDER_SUBFORM_NONE, RENDER_SUBFORM_DIFFUSE = 0, 1, 2
 
 
 class PrtCamera(C.Structure):
@@ -333,6 +335,7 @@ EXPORTS = [
     "prt_abi_version",
     "prt_dev_hooks",
     "prt_last_render_form",
+    "prt_last_render_subform",
     "prt_shutdown",
     "prt_render_samples",
     "prt_render_multi",

@@ -192,6 +192,13 @@ def last_render_form(L=None):
     return int((L or load()).prt_last_render_form())
 
 
+def last_render_subform(L=None):
+    """prt_last_render_subform of `L` (default: the current library): _abi.RENDER_SUBFORM_DIFFUSE when the last K3 launch was the
+    DIFFUSE form of the PLAIN kernel (an all-Lambertian scene), RENDER_SUBFORM_NONE for every other launch; RENDER_SUBFORM_UNKNOWN
+    from the shipped library and before the first launch."""
+    return int((L or load()).prt_last_render_subform())
+
+
 def shutdown():
     """prt_shutdown of every library loaded so far (cached RCCL communicators)."""
     for L in _libs.values():

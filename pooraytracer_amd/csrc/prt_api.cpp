@@ -132,12 +132,12 @@ struct Staging {
 };
 
 // What the render kernels of one precision get: the scene tables, resident blocks per CU of the production, the counting
-// and the PLAIN instantiation (k_render; 0: the scene's frames have no PLAIN form), the light-tree nodes / light triangles /
-// materials staged in LDS (all 0 = the kernels without LDS tables), and the traversal stack entries per lane.
+// and the PLAIN instantiation (k_render; 0: the scene's frames have no PLAIN form) and of its DIFFUSE form (0: none), the
+// light-tree nodes / light triangles / materials staged in LDS (all 0 = the kernels without LDS tables), and the traversal stack entries per lane.
 template <typename R>
 struct KernelConfig {
     DSceneT<R> d{};
-    int blocks_per_cu[3] = {0, 0, 0};
+    int blocks_per_cu[4] = {0, 0, 0, 0};
     int blocks_per_cu_rays = 0; // ... and of the ray-batch instantiation (prt_ray_color), queried by its first call
     int light_lds = 0, ltri_lds = 0, mat_lds = 0;
     int stack_depth = PRT_STACK_DEPTH;
@@ -147,13 +147,19 @@ struct KernelConfig {
 extern "C" int prt_dev_hooks(void) { return PRT_DEV_HOOKS; }
 
 // The form of the last K3 launch (prt.h, prt_last_render_form): kept by the dev-hooks build only.
+// A DIFFUSE launch is a PLAIN launch to prt_last_render_form; prt_last_render_subform tells the two apart.
 #if PRT_DEV_HOOKS
-static std::atomic<int> g_render_form{PRT_RENDER_FORM_UNKNOWN};
-static void note_render_form(bool plain) { g_render_form = plain ? PRT_RENDER_FORM_PLAIN : PRT_RENDER_FORM_GENERIC; }
+static std::atomic<int> g_render_form{PRT_RENDER_FORM_UNKNOWN}, g_render_subform{PRT_RENDER_SUBFORM_UNKNOWN};
+static void note_render_form(bool plain, bool diffuse) {
+    g_render_form = plain ? PRT_RENDER_FORM_PLAIN : PRT_RENDER_FORM_GENERIC;
+    g_render_subform = plain && diffuse ? PRT_RENDER_SUBFORM_DIFFUSE : PRT_RENDER_SUBFORM_NONE;
+}
 extern "C" int prt_last_render_form(void) { return g_render_form; }
+extern "C" int prt_last_render_subform(void) { return g_render_subform; }
 #else
-static void note_render_form(bool) {}
+static void note_render_form(bool, bool) {}
 extern "C" int prt_last_render_form(void) { return PRT_RENDER_FORM_UNKNOWN; }
+extern "C" int prt_last_render_subform(void) { return PRT_RENDER_SUBFORM_UNKNOWN; }
 #endif
 
 #define PRT_HIP_AS(who, call)                                                                           \
@@ -186,6 +192,7 @@ struct PrtScene {
     int n_cu = 0;
     int blocks_wanted = 0; // what the production kernel's register allocation allows (occupancy without LDS tables)
     int feat = 0; // material features of the scene (1 textures, 2 Phong, 4 CookTorrance) -> K3 permutation
+    bool all_diffuse = false; // prt::materials_all_diffuse(mats), taken where the table is uploaded: the scene's PLAIN frames have the DIFFUSE form
     KernelConfig<double> k64;
     // fp32 fast mode: float copies of the tables, made on the first PRT_PRECISION_F32 call (ensure_f32)
     KernelConfig<float> k32;
@@ -533,6 +540,18 @@ static bool generic_forced() {
     const char* e = dev_env("PRT_TUNE_GENERIC");
     return e && std::atoi(e);
 }
+// ... and whether that PLAIN launch uses its DIFFUSE form: the launchers' render_diffuse decides, from the same values and the
+// flag of the scene's material table (PrtScene::all_diffuse).  fp64 only.  PRT_TUNE_NO_DIFFUSE=1 (developer): a qualifying
+// launch keeps the plain PLAIN kernel; PRT_TUNE_GENERIC=1 wins over both.
+template <typename R>
+static bool frame_diffuse(const PrtScene* s, const KernelConfig<R>& k, bool count, bool rays, int jitter, int scramble, int sample_lights) {
+    return std::is_same<R, double>::value &&
+           prt::render_diffuse(s->feat, count, rays, k.d.n_lights, k.ltri_lds, jitter, scramble, sample_lights, s->all_diffuse);
+}
+static bool diffuse_off() {
+    const char* e = dev_env("PRT_TUNE_NO_DIFFUSE");
+    return e && std::atoi(e);
+}
 
 // LDS tables and resident blocks per CU of the render kernels of one precision, for stacks of k.stack_depth entries.
 // drop_tables: render without the tables when they would cost the production kernel a resident block (the budget is an
@@ -548,16 +567,20 @@ static int size_kernels(const PrtScene* s, KernelConfig<R>& k, bool drop_tables)
                 &k.mat_lds, &k.ltri_lds, &k.light_lds);
     const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
     const bool extra = !s->lights.tab.empty() || k.d.tex_compact != 0;
-    auto blocks = [&](bool count, size_t tables, bool plain = false) { return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra, false, plain); };
+    auto blocks = [&](bool count, size_t tables, bool plain = false, bool diffuse = false) {
+        return blocks_per_cu(count, s->feat, tables, k.stack_depth, pad, extra, false, plain, diffuse);
+    };
     const size_t tables = table_bytes(k.light_lds, k.mat_lds, k.ltri_lds);
     k.blocks_per_cu[0] = blocks(false, tables);
     // a frame with default settings launches the PLAIN form where the scene has one: a function of its own, asked about on its own
     k.blocks_per_cu[2] = frame_plain(s, k, false, false, 0, 0, 1) ? blocks(false, tables, true) : 0;
+    k.blocks_per_cu[3] = frame_diffuse(s, k, false, false, 0, 0, 1) ? blocks(false, tables, true, true) : 0; // ... and so is its DIFFUSE form
     const int wanted = drop_tables && tables != 0 ? blocks(false, 0) : k.blocks_per_cu[0];
-    if (k.blocks_per_cu[0] < wanted || (k.blocks_per_cu[2] && k.blocks_per_cu[2] < wanted)) { // a block per CU is worth far more than the tables
+    if (k.blocks_per_cu[0] < wanted || (k.blocks_per_cu[2] && k.blocks_per_cu[2] < wanted) ||
+        (k.blocks_per_cu[3] && k.blocks_per_cu[3] < wanted)) { // a block per CU is worth far more than the tables
         k.mat_lds = k.ltri_lds = k.light_lds = 0;
         k.blocks_per_cu[0] = wanted;
-        k.blocks_per_cu[2] = 0; // (no light triangles in LDS: no PLAIN form)
+        k.blocks_per_cu[2] = k.blocks_per_cu[3] = 0; // (no light triangles in LDS: no PLAIN form)
     }
     k.blocks_per_cu[1] = blocks(true, table_bytes(k.light_lds, k.mat_lds, k.ltri_lds));
     if (dev_env("PRT_TUNE_VERBOSE")) {
@@ -590,7 +613,7 @@ static int rays_blocks_per_cu(const PrtScene* s, KernelConfig<R>& k) {
         constexpr bool f64 = std::is_same<R, double>::value;
         const size_t tables = (f64 ? prt::render_table_bytes : prt32::render_table_bytes)(k.light_lds, k.mat_lds, k.ltri_lds);
         const bool pad = k.d.tri_stride == PRT_TRI_PAD_STRIDE(R) && sizeof(DTriT<R>) != PRT_TRI_PAD_STRIDE(R);
-        k.blocks_per_cu_rays = (f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu)(false, s->feat, tables, k.stack_depth, pad, true, true, false);
+        k.blocks_per_cu_rays = (f64 ? prt::render_blocks_per_cu : prt32::render_blocks_per_cu)(false, s->feat, tables, k.stack_depth, pad, true, true, false, false);
     }
     return k.blocks_per_cu_rays;
 }
@@ -1213,6 +1236,7 @@ static int upload_impl(PrtScene* s, int device) {
     }
     if (const char* e = dev_env("PRT_TUNE_FEAT")) s->feat |= std::atoi(e); // developer: force a larger permutation
     s->feat = prt::render_permutation(s->feat);
+    s->all_diffuse = prt::materials_all_diffuse(s->mats); // (the table just uploaded; nothing changes it afterwards)
     // Small read-only tables of the shading code live in LDS (LLDS kernels): every read of them is otherwise a
     // texture-addresser instruction, and the light tree's descent is a chain of dependent reads.  In order of
     // value per byte: the material table (must fit, <= 8 KB), all light triangles if there are at most 32, then
@@ -2730,7 +2754,8 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
     const bool count = count_work != 0;
     const bool plain = !generic_forced() && (f32 ? frame_plain(s, s->k32, count, pass.rays, P.jitter, P.scramble, P.sample_lights)
                                                  : frame_plain(s, s->k64, count, pass.rays, P.jitter, P.scramble, P.sample_lights));
-    int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : plain ? 2 : 0];
+    const bool diffuse = plain && !diffuse_off() && !f32 && frame_diffuse(s, s->k64, count, pass.rays, P.jitter, P.scramble, P.sample_lights);
+    int bpc = (f32 ? s->k32.blocks_per_cu : s->k64.blocks_per_cu)[count ? 1 : diffuse ? 3 : plain ? 2 : 0];
     if (pass.rays) bpc = f32 ? rays_blocks_per_cu(s, s->k32) : rays_blocks_per_cu(s, s->k64);
     const uint64_t lanes = (uint64_t)s->n_cu * bpc * PRT_BLOCK;
     // Work item = (pixel, chunk of samples), dealt chunk-major from PRT_ITEM_QUEUES counters (prt_types.h).
@@ -2822,9 +2847,9 @@ static int render_impl(PrtScene* s, const char* who, const PrtCamera* cam, const
             }
         }
         // fp32: the same camera and parameters rounded to float (K5 below works from the fp64 originals: it only maps pixels)
-        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain);
-        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain);
-        note_render_form(plain);
+        if (f32) prt32::launch_render(s->k32.d, to_f32(C), to_f32(P, s->k32), d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain, false);
+        else prt::launch_render(s->k64.d, C, P, d_partial, q.d_ctr.get(), count, s->feat, grid, st, pass.rays, plain, diffuse);
+        note_render_form(plain, diffuse);
         PRT_HIP(hipGetLastError());
     }
     PRT_HIP(q.stop(st));
@@ -2928,8 +2953,8 @@ int prt_render_samples(PrtScene* s, const PrtCamera* cam, const PrtRenderParams*
         PRT_HIP_AS(who, q.start(nullptr));
         PRT_HIP_AS(who, q.set_pointers(nullptr, d_pix, d_trace));
         if (P.max_depth >= 0) {
-            prt::launch_render(s->k64.d, C, P, d_part, q.d_ctr.get(), count, s->feat, grid, nullptr, false, plain);
-            note_render_form(plain);
+            prt::launch_render(s->k64.d, C, P, d_part, q.d_ctr.get(), count, s->feat, grid, nullptr, false, plain, false); // (a list: never PLAIN, so never DIFFUSE)
+            note_render_form(plain, false);
         } else PRT_HIP_AS(who, hipMemset(d_part, 0, (size_t)P.n_items * 3 * sizeof(double)));
         PRT_HIP_AS(who, hipGetLastError());
         PRT_HIP_AS(who, q.stop(nullptr));

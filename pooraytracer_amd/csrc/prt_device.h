@@ -897,6 +897,10 @@ PRT_DEV d3 ct_sample_wm(const DMaterial& m, d3 w, d2 u) { // Material.h:412-435
 #define PRT_FEAT_NARROW 16 // not a material feature either: texture lookups of this caller fetch their footprint a row at a time (tex_value)
 #define PRT_FEAT_RAYS 32   // not a material feature either: K3 takes its primary rays from DCounters::ray_list instead of a camera (prt_ray_color)
 #define PRT_FEAT_PLAIN 64  // not a material feature either: K3 for a frame with default settings — what such a launch never does is compiled out (k_render, PLAIN)
+// Not a material feature either, and only on top of PRT_FEAT_PLAIN in the lean fp64 permutation: every material of the scene that
+// is not an emitter is an untextured Lambertian and none skips light sampling (render_diffuse() on the host decides, from a flag
+// of the material table), so Eval and Scatter are their Lambertian case without a test of m.type (k_render, DIFFUSE)
+#define PRT_FEAT_DIFFUSE 128
 template <int FEAT>
 PRT_DEV d3 mat_kd(const DScene& S, const DMaterial& m, d2 uv) {
     if ((FEAT & PRT_FEAT_TEX) && m.texture >= 0) return tex_value<(FEAT & PRT_FEAT_EXTRA) != 0, (FEAT & PRT_FEAT_NARROW) != 0>(S, m.texture, uv.x, uv.y);
@@ -909,7 +913,7 @@ PRT_DEV d3 mat_ks(const DScene& S, const DMaterial& m, d2 uv) { // Phong(mapKd,.
 }
 template <int FEAT>
 PRT_DEV d3 mat_eval(const DScene& S, const DMaterial& m, d3 wi, d3 wo, d2 uv, Rng& rng) {
-    if (m.type == 0) return mat_kd<FEAT>(S, m, uv) * PRT_INV_PI;
+    if ((FEAT & PRT_FEAT_DIFFUSE) || m.type == 0) return mat_kd<FEAT>(S, m, uv) * PRT_INV_PI;
     if ((FEAT & PRT_FEAT_PHONG) && m.type == 1) {
         real u = rng.next();
         if (u < m.pkd) {
@@ -943,9 +947,10 @@ PRT_DEV d3 mat_eval(const DScene& S, const DMaterial& m, d3 wi, d3 wo, d2 uv, Rn
 template <int FEAT>
 PRT_DEV bool mat_scatter(const DScene& S, const DMaterial& m, d3 rd, const Frame& f, d2 uv, Rng& rng, d3& att,
                          d3& wi_world, bool have_fr = false, d3 fr_pre = d3{RL(0.), RL(0.), RL(0.)}) {
-    if (!(FEAT & PRT_FEAT_PHONG) && m.type == 1) return false; // not reachable: the host picks a permutation that
-    if (!(FEAT & PRT_FEAT_CT) && m.type == 3) return false;    // covers every material type of the scene
-    switch (m.type) {
+    constexpr bool DIFFUSE = (FEAT & PRT_FEAT_DIFFUSE) != 0; // every material that scatters is a Lambertian: case 0, untested
+    if (!DIFFUSE && !(FEAT & PRT_FEAT_PHONG) && m.type == 1) return false; // not reachable: the host picks a permutation that
+    if (!DIFFUSE && !(FEAT & PRT_FEAT_CT) && m.type == 3) return false;    // covers every material type of the scene
+    switch (DIFFUSE ? 0 : m.type) {
     case 0: { // Lambertian, Material.h:106-151
         d3 wi = cosine_hemisphere(rng);
         while (wi.z <= RL(0.)) wi = cosine_hemisphere(rng);

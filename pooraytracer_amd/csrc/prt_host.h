@@ -93,6 +93,10 @@ void update_triangles(const double* vertices, const double* normals, std::vector
 void update_triangles_listed(const int32_t* prims, size_t n, const double* vertices, const double* normals, std::vector<HostTri>& tris);
 // Material table incl. SetProbabilitiesByNs / HasEmission / SkipLightSampling (Material.h).
 void setup_materials(const PrtSceneDesc& d, std::vector<DMaterial>& out);
+// The flag of a material table behind the DIFFUSE form of the render kernel (k_render; render_diffuse decides with it): every
+// material is an untextured Lambertian or an untextured DiffuseLight, and none skips light sampling.  Mirror, Phong, CookTorrance,
+// Debug and Empty materials and any texture say no; an empty table and a table of emitters only say yes (nothing in them scatters).
+bool materials_all_diffuse(const std::vector<DMaterial>& mats);
 // Binned-SAH BVH2, depth-bounded to PRT_STACK_DEPTH, child boxes rounded outward to fp32.
 // Returns false (with *err set) if a compiled-in limit is exceeded.
 bool build_bvh(const std::vector<HostTri>& tris, BuiltBVH& out, std::string* err);

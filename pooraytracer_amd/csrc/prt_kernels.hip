@@ -426,6 +426,14 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
 #define SAMPLE_LIGHTS (PLAIN || P.sample_lights)                   // bSampleLights
 #define HAS_LIGHTS (PLAIN || S.n_lights > 0)
 #define LTRI_LDS (PLAIN ? 1 : P.ltri_lds)                          // > 0: the light triangles are read from LDS (all or none are staged)
+    // DIFFUSE (PRT_FEAT_DIFFUSE on top of PLAIN, lean fp64 permutation only; render_diffuse() on the host decides, from a flag of
+    // the scene's material table): every material that is not an emitter is an untextured Lambertian and none skips light
+    // sampling.  Eval and Scatter are their Lambertian case without a test of m.type (mat_eval, mat_scatter), no vertex skips
+    // its light pick, and prev_skip is never set, so it is not carried.  Again only conditions differ: has_emission stays a
+    // per-lane test, the redraw loop of Scatter stays, every expression and draw is the generic kernel's.
+    constexpr bool DIFFUSE = (FEAT & PRT_FEAT_DIFFUSE) != 0;
+    static_assert(!DIFFUSE || (PLAIN && !(FEAT & PRT_FEAT_ALL) && !PRT_F32), "DIFFUSE: the lean fp64 PLAIN kernels only");
+#define SKIPS_LIGHTS(m) (!DIFFUSE && (m).skip_light_sampling != 0) // SkipLightSampling of the vertex's material
     __shared__ uint32_t s_qoff[PRT_BLOCK / 64];
     __shared__ unsigned long long s_rays[PRT_BLOCK / 64];
     __shared__ real s_center[4]; // Camera::center, the origin of every camera ray
@@ -747,14 +755,14 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                     TRACE_VERTEX(S.shade[tr.hit.tri].prim);
                     if (m.has_emission) {
                         // Camera.cpp:129-132; via a bounce only after SkipLightSampling materials (:191-195)
-                        if (first || !SAMPLE_LIGHTS || prev_skip) ADD_RADIANCE(ld3(m.emission));
+                        if (first || !SAMPLE_LIGHTS || (!DIFFUSE && prev_skip)) ADD_RADIANCE(ld3(m.emission));
                         end_sample = true;
                     } else {
                         rd = tr.d;
                         sh_tri = tr.hit.tri;
                         tr.o = tr.o + tr.d * tr.hit.t; // record.position = ray(t): from here on the origin of whatever comes next
                         do_scatter = true;
-                        if (SAMPLE_LIGHTS && HAS_LIGHTS && !m.skip_light_sampling) {
+                        if (SAMPLE_LIGHTS && HAS_LIGHTS && !SKIPS_LIGHTS(m)) {
                             // next-event estimation, Camera.cpp:137-155: pick the light point now (4 draws)
                             const d3 gn = ld3(tri_at<PAD>(S, (uint32_t)sh_tri)->n);
                             const d3 fn = dot(rd, gn) < RL(0.) ? gn : -gn;
@@ -900,7 +908,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                                 const d3 beta = (PST_LD(S_BETA) * att) * P.inv_rr;
                                 PST_ST(S_BETA, beta);
                                 if (!(beta.x == RL(0.) && beta.y == RL(0.) && beta.z == RL(0.))) {
-                                    prev_skip = m.skip_light_sampling != 0;
+                                    prev_skip = SKIPS_LIGHTS(m);
                                     first = false;
                                     end_sample = false;
                                 }
@@ -933,7 +941,7 @@ __global__ __launch_bounds__(PRT_BLOCK, render_waves(FEAT)) void k_render(Render
                             // a zero throughput (Phong bad sample) contributes exactly 0 from here on
                             if (!(beta.x == RL(0.) && beta.y == RL(0.) && beta.z == RL(0.))) {
                                 tr.d = wi;
-                                prev_skip = m.skip_light_sampling != 0;
+                                prev_skip = SKIPS_LIGHTS(m);
                                 first = false;
                                 end_sample = false;
                             }
@@ -1570,7 +1578,7 @@ namespace PRT_NS {
 // The compiled permutations: lean, textures only, Phong only, CookTorrance only, everything.  A scene gets the smallest one
 // that covers its materials.
 int render_permutation(int feat) {
-    feat &= ~(PRT_FEAT_RAYS | PRT_FEAT_PLAIN); // (not material features: the ray source of prt_ray_color, the PLAIN form)
+    feat &= ~(PRT_FEAT_RAYS | PRT_FEAT_PLAIN | PRT_FEAT_DIFFUSE); // (not material features: the ray source of prt_ray_color, the PLAIN form and its DIFFUSE form)
     if (feat == 0 || feat == PRT_FEAT_TEX || feat == PRT_FEAT_PHONG || feat == PRT_FEAT_CT) return feat;
     return PRT_FEAT_ALL;
 }
@@ -1597,12 +1605,25 @@ bool render_plain(int feat, bool count, bool rays, int n_lights, int ltri_lds, i
     return plain_permutation(render_permutation(feat)) && !count && !rays && n_lights > 0 && ltri_lds > 0 && !jitter &&
            scramble != PRT_ITEMS_FROM_LIST && sample_lights;
 }
+// The permutation whose PLAIN form has a DIFFUSE form: the lean fp64 one (the fp32 twin has no PLAIN form and gets none).
+constexpr bool diffuse_permutation(int perm) { return plain_permutation(perm) && perm == 0; }
+// ... and THE decision for it (k_render, DIFFUSE): a PLAIN launch of the lean permutation in a scene whose material table says
+// so (`all_diffuse`: every material an untextured Lambertian or an emitter, none skipping light sampling — computed by the host
+// where the table is made, never per launch).  prt_api.cpp asks here, for the occupancy query and for the launch.
+bool render_diffuse(int feat, bool count, bool rays, int n_lights, int ltri_lds, int jitter, int scramble, int sample_lights, bool all_diffuse) {
+    return render_plain(feat, count, rays, n_lights, ltri_lds, jitter, scramble, sample_lights) && diffuse_permutation(render_permutation(feat)) &&
+           all_diffuse;
+}
 // COUNT instantiations exist only with PRT_FEAT_EXTRA (statistics runs: speed is not what they are for); so do the
 // PRT_FEAT_RAYS ones (prt_ray_color: one kernel per permutation and layout, no counting form).  PLAIN ones exist with LDS
-// tables only (render_plain asks for the light triangles there), with and without PRT_FEAT_EXTRA.
+// tables only (render_plain asks for the light triangles there), with and without PRT_FEAT_EXTRA; so do the DIFFUSE ones.
 template <int FEAT, bool PAD>
-static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool rays, bool plain) {
+static RenderKernel render_kernel_feat(bool count, bool llds, bool extra, bool rays, bool plain, bool diffuse) {
     constexpr int X = FEAT | PRT_FEAT_EXTRA;
+    if constexpr (diffuse_permutation(FEAT)) {
+        constexpr int D = PRT_FEAT_PLAIN | PRT_FEAT_DIFFUSE;
+        if (plain && diffuse) return extra ? k_render<false, X | D, true, PAD> : k_render<false, FEAT | D, true, PAD>;
+    }
     if constexpr (plain_permutation(FEAT)) {
         if (plain) return extra ? k_render<false, X | PRT_FEAT_PLAIN, true, PAD> : k_render<false, FEAT | PRT_FEAT_PLAIN, true, PAD>;
     }
@@ -1615,17 +1636,18 @@ template <bool PAD>
 static RenderKernel render_kernel_pad(bool count, int feat, bool llds, bool extra) {
     const bool rays = (feat & PRT_FEAT_RAYS) != 0;
     const bool plain = (feat & PRT_FEAT_PLAIN) != 0 && llds && !count && !rays; // (what render_plain implies: said again for the instantiations' sake)
+    const bool diffuse = plain && (feat & PRT_FEAT_DIFFUSE) != 0;
     switch (render_permutation(feat)) {
-    case 0: return render_kernel_feat<0, PAD>(count, llds, extra, rays, plain);
-    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra, rays, plain);
-    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra, rays, plain);
-    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra, rays, plain);
-    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra, rays, plain);
+    case 0: return render_kernel_feat<0, PAD>(count, llds, extra, rays, plain, diffuse);
+    case PRT_FEAT_TEX: return render_kernel_feat<PRT_FEAT_TEX, PAD>(count, llds, extra, rays, plain, diffuse);
+    case PRT_FEAT_PHONG: return render_kernel_feat<PRT_FEAT_PHONG, PAD>(count, llds, extra, rays, plain, diffuse);
+    case PRT_FEAT_CT: return render_kernel_feat<PRT_FEAT_CT, PAD>(count, llds, extra, rays, plain, diffuse);
+    default: return render_kernel_feat<PRT_FEAT_ALL, PAD>(count, llds, extra, rays, plain, diffuse);
     }
 }
 // `pad`: the scene's intersection records sit 128 bytes apart (DScene::tri_stride); `extra`: the scene has light tables or
 // plain texel arrays (PRT_FEAT_EXTRA kernels); `feat` with PRT_FEAT_RAYS: the kernel of prt_ray_color; with PRT_FEAT_PLAIN: the
-// PLAIN form (render_plain said so)
+// PLAIN form (render_plain said so); with PRT_FEAT_DIFFUSE as well: its DIFFUSE form (render_diffuse said so)
 static RenderKernel render_kernel(bool count, int feat, bool llds, bool pad, bool extra) {
     return pad ? render_kernel_pad<true>(count, feat, llds, extra) : render_kernel_pad<false>(count, feat, llds, extra);
 }
@@ -1634,10 +1656,11 @@ static size_t stack_bytes(int stack_depth) { return PRT_DYN_STACK ? (size_t)PRT_
 
 // Resident blocks per CU of the instantiation a launch will use (`pad`: the scene's records sit at the padded stride —
 // a different function with its own register count).
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain) {
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain, bool diffuse) {
     int nb = 0;
     if (rays) feat |= PRT_FEAT_RAYS;
     if (plain) feat |= PRT_FEAT_PLAIN;
+    if (diffuse) feat |= PRT_FEAT_DIFFUSE;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, render_kernel(count, feat, table_bytes != 0, pad, extra), PRT_BLOCK,
                                                                 table_bytes + stack_bytes(stack_depth));
     if (e != hipSuccess || nb < 1) nb = 1;
@@ -1685,7 +1708,7 @@ hipError_t launch_trace(const DScene& S, const PrtRay* d_rays, size_t n, void* d
 
 // `rays`: the ray-batch kernels (prt_ray_color; DCounters::ray_list / key_list are set, C is not read)
 void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, double* d_partial, DCounters* d_ctr,
-                   bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain) {
+                   bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain, bool diffuse) {
     static_assert(sizeof(DMaterial) % 16 == 0, "materials are staged in 16-byte pieces");
     const size_t tables = render_table_bytes(P.light_lds, P.mat_lds, P.ltri_lds);
     const size_t dyn_lds = tables + stack_bytes(P.stack_depth);
@@ -1698,6 +1721,7 @@ void launch_render(const DScene& S, const DCamera& C, const DRenderParams& P, do
     A.ctr = d_ctr;
     if (rays) feat |= PRT_FEAT_RAYS;
     if (plain) feat |= PRT_FEAT_PLAIN;
+    if (diffuse) feat |= PRT_FEAT_DIFFUSE;
     hipLaunchKernelGGL(render_kernel(count, feat, tables != 0, pad, S.light_tab != nullptr || S.tex_compact != 0), dim3(grid), dim3(PRT_BLOCK), dyn_lds, st, A);
 }
 

@@ -13,9 +13,12 @@
 
 namespace prt {
 // prt_kernels.hip
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain);
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain, bool diffuse);
 // whether a K3 launch with these values uses the PLAIN form of its kernel (k_render): the one decision, for the occupancy query and the launch
 bool render_plain(int feat, bool count, bool rays, int n_lights, int ltri_lds, int jitter, int scramble, int sample_lights);
+// ... and its DIFFUSE form on top of the PLAIN one (k_render): render_plain holds, the permutation is the lean one, and the scene's
+// material table is all untextured Lambertians and emitters (`all_diffuse`, the host's flag of the table).  fp64 only.
+bool render_diffuse(int feat, bool count, bool rays, int n_lights, int ltri_lds, int jitter, int scramble, int sample_lights, bool all_diffuse);
 int render_permutation(int feat);
 int render_lds_budget(int feat, int stack_depth);
 size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
@@ -26,7 +29,7 @@ size_t ray_sort_scratch_bytes(size_t n, std::string* err);
 const uint32_t* ray_sort(const PrtRay* d_rays, size_t n, const float grid_origin[3], const float grid_step[3], void* scratch,
                          size_t scratch_bytes, hipStream_t st, std::string* err);
 void launch_render(const DSceneT<double>& S, const DCameraT<double>& C, const DRenderParamsT<double>& P, double* d_partial,
-                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain);
+                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain, bool diffuse);
 void launch_finalize(const DCameraT<double>& C, const DRenderParamsT<double>& P, const double* d_partial, double* d64, float* d32,
                      hipStream_t st);
 void launch_finalize_rays(const DRenderParamsT<double>& P, const double* d_partial, double* d64, float* d32, hipStream_t st);
@@ -153,7 +156,7 @@ hipError_t launch_multi_hit(const DSceneT<double>& S, const PrtRay* d_rays, cons
 
 // fp32 fast mode (prt_kernels_f32.hip): K1 and K3 on float records derived from the resident fp64 ones
 namespace prt32 {
-int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain);
+int render_blocks_per_cu(bool count, int feat, size_t table_bytes, int stack_depth, bool pad, bool extra, bool rays, bool plain, bool diffuse);
 // whether a K3 launch with these values uses the PLAIN form of its kernel (k_render): the one decision, for the occupancy query and the launch
 bool render_plain(int feat, bool count, bool rays, int n_lights, int ltri_lds, int jitter, int scramble, int sample_lights);
 int render_permutation(int feat);
@@ -162,7 +165,7 @@ size_t render_table_bytes(int light_lds, int mat_lds, int ltri_lds);
 hipError_t launch_trace(const DSceneT<float>& S, const PrtRay* d_rays, size_t n, void* d_out, DCounters* d_ctr, bool count, int mode,
                         int n_cu, hipStream_t st, const uint32_t* d_perm);
 void launch_render(const DSceneT<float>& S, const DCameraT<float>& C, const DRenderParamsT<float>& P, double* d_partial,
-                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain);
+                   DCounters* d_ctr, bool count, int feat, unsigned grid, hipStream_t st, bool rays, bool plain, bool diffuse);
 void launch_convert_tris(const void* in, uint32_t in_stride, uint32_t n, void* out, uint32_t out_stride, hipStream_t st);
 void launch_convert_shade(const DTriShadeT<double>* in, uint32_t n, DTriShadeT<float>* out, hipStream_t st);
 void launch_convert_reals(const double* in, size_t n, float* out, hipStream_t st);

@@ -159,6 +159,14 @@ void setup_materials(const PrtSceneDesc& d, std::vector<DMaterial>& out) {
     }
 }
 
+bool materials_all_diffuse(const std::vector<DMaterial>& mats) {
+    for (const DMaterial& m : mats) {
+        if (m.type != PRT_MAT_LAMBERTIAN && m.type != PRT_MAT_DIFFUSE_LIGHT) return false;
+        if (m.texture >= 0 || m.skip_light_sampling != 0) return false;
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Light tree.  NEE picks a light triangle by descending the reference's lights BVH with an area
 // CDF (BVH.cpp:86-100); which triangle a given `p` lands on therefore depends on that tree's shape:
